@@ -9,7 +9,11 @@ camera, InvDepth chart, fast Riccati — configs/EQVIO_config_EuRoC_stationary.y
 before the timed region; Sigma and the landmark arrays stay resident in HBM, only the per-frame measurement
 (<= 5 KB) crosses PCIe inside the timed region, as it does for any caller of the filter API.
 
-Prints ONE JSON line (rank 0). `value` = frames processed by all ranks / max-over-ranks wall time.
+Prints ONE JSON line (rank 0). `value` = frames processed by all ranks / max-over-ranks wall time, `ms_per_step` = milliseconds of one timed step.
+A plain run does only what that line needs: set-up, W warm-up steps, K timed steps, the line. `--full` adds everything else the benchmark measures
+or checks (post-run sanity of Sigma, factorisation counters, roofline and its rocprofv3 counter passes, CPU baselines, several filters per GPU, frame
+mix, reference-side binding, other state sizes; each leg can be dropped with its --no-* option). `--dump-outputs DIR` writes what the timed steps
+computed (rank 0's state estimate and Sigma after the last step) as DIR/<name>.npy; with the same arguments the inputs are the same from run to run.
 """
 import argparse
 import json
@@ -25,6 +29,28 @@ import numpy as np  # noqa: E402
 
 N_LANDMARKS = 200
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X datasheet fp64 matrix peak; the measured issue-rate ceiling is reported too
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(flt, out_dir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what a caller of the timed path holds after its last step - the state estimate (sensor state, landmark ids and positions: the
+    reference's VIOFilter::stateEstimate) and the covariance Sigma - as float64 .npy files, so that two builds can be compared output for output. A Sigma
+    beyond the byte budget is written as a fixed, seeded sample of its entries (sigma_sample, with the column-major flat indices in sigma_sample_index)."""
+    os.makedirs(out_dir, exist_ok=True)
+    sensor, ids, p = flt.state_estimate()
+    S = flt.get_sigma()
+    out = {"sensor_state": sensor, "landmark_ids": ids.astype(np.float64), "landmark_positions": p}
+    rest = budget - sum(a.nbytes for a in out.values())
+    if S.nbytes <= rest:
+        out["sigma"] = S
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(S.size, size=rest // 16, replace=False))  # 8 bytes of value + 8 of index per entry
+        out["sigma_sample"] = S.ravel(order="F")[idx]
+        out["sigma_sample_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def flops_propagate(n):  # BASELINE.md §2 / SURVEY.md §8(d): dense formulation
@@ -399,6 +425,10 @@ def main():
     ap.add_argument("--steps", type=int, default=8000)
     ap.add_argument("--warmup", type=int, default=500)
     ap.add_argument("--landmarks", type=int, default=N_LANDMARKS)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line, run every other measurement and check of the benchmark (the legs the --no-* options below drop)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what they computed (rank 0's state estimate and Sigma after the last step) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-multi-filter", action="store_true")
@@ -413,6 +443,10 @@ def main():
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and args.config != "headline":
+        sys.exit("bench.py: --dump-outputs writes the headline workload's outputs; --config %s has none" % args.config)
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:  # plain `python bench.py --gpus N`: this process is the launcher
             return self_launch(args.gpus)
@@ -445,6 +479,8 @@ def main():
         return backend.make_filter(settings, N, sensor, ids, p, t)
 
     value, elapsed, flt, world, frames, settings, mine = rank_pass(args, rank, world_size, dist, backend)
+    if rank == 0 and args.dump_outputs:  # before anything else runs frames on this filter
+        dump_outputs(flt, args.dump_outputs)
     per_rank, placements = [mine], [placement]
     if dist is not None:  # every rank's own wall time of the timed region, for the min / max next to the aggregate
         per_rank, placements = [None] * world_size, [None] * world_size
@@ -454,7 +490,7 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     frame_flops = flops_propagate(n) + flops_update(n, m)
     roofline = cpu = multi = mix = binding = factorisation = sizes = None
-    if not stand_in:
+    if args.full and not stand_in:
         lib = backend.lib
         cam = world.cam
         core = flt.core_handle()
@@ -869,7 +905,7 @@ def _pmc_pass(N, counters, steps=40, warmup=10):
     tmp = tempfile.mkdtemp(prefix="eqvio_pmc_", dir="/tmp")
     try:
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", *counters, "-d", tmp, "-o", "p", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--landmarks", str(N), "--steps", str(steps),
-               "--warmup", str(warmup), "--no-cpu-baseline", "--no-roofline", "--no-multi-filter", "--no-frame-mix", "--no-binding", "--no-sizes", "--no-pmc"]
+               "--warmup", str(warmup)]
         subprocess.run(cmd, cwd="/tmp", env={**os.environ, "TMPDIR": "/tmp"}, capture_output=True, timeout=600, check=True)
         dbs = glob.glob(os.path.join(tmp, "**", "*.db"), recursive=True)
         if not dbs:

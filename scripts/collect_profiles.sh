@@ -1,14 +1,14 @@
 # usage: collect_profiles.sh <tag> [landmarks] [full]
-#   tag        file prefix under gpurun_out/<tag>/ (e.g. r02_N500)
+#   tag        file prefix under $OUT_ROOT/<tag>/ (OUT_ROOT: relative to the repository root, default collect_out; e.g. r02_N500)
 #   landmarks  filter size (default 200)
 #   full       "full" also runs the frame trace / host share / bench.json (N=200 house-keeping)
 set -x
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 V=${1:-r02_v0}
 NL=${2:-200}
 FULL=${3:-}
-OUT=$R/gpurun_out/$V
+OUT=$R/${OUT_ROOT:-collect_out}/$V
 mkdir -p $OUT
 ST=50; WU=10
 if [ "$NL" -ge 400 ]; then ST=30; WU=5; fi
@@ -26,7 +26,7 @@ python $R/scripts/rocpd_pmc.py $(find /tmp/p_m -name "*.db" | head -1) > $OUT/${
 cd $R
 python scripts/frame_trace.py $NL 2000 > $OUT/${V}_frame_trace.txt 2>&1
 LST=2000; LWU=200; if [ "$NL" -ge 400 ]; then LST=600; LWU=100; fi
-python bench.py --landmarks $NL --steps $LST --warmup $LWU --no-multi-filter --no-binding --no-sizes > $OUT/${V}_bench.json 2> $OUT/bench.err
+python bench.py --full --landmarks $NL --steps $LST --warmup $LWU --no-multi-filter --no-binding --no-sizes > $OUT/${V}_bench.json 2> $OUT/bench.err
 if [ "$FULL" = "full" ]; then
   python scripts/host_share.py $NL 6000 > $OUT/${V}_host_share.txt 2>&1
   python scripts/propagate_vs_steps.py > $OUT/${V}_propagate_vs_steps.txt 2>&1
