@@ -1,0 +1,224 @@
+"""ctypes binding of the filter batch: include/eqf_batch.h (device level, libeqf_hip.so) and include/eqvio_batch.h (filter level, libeqvio_filter.so).
+
+VIOFilterBatch holds B independent reference VIOFilters (fast Riccati, at most 64 landmarks each) whose frames go to the GPU together: one kernel launch per
+step, one workgroup per slot. .slot(k) is a view with the method names of capi.VIOFilter, so the per-filter test helpers work on a slot unchanged.
+The prototypes are declared in lists of their own (_batch_declared), apart from the loaders' _declared lists of eqf_hip.h / eqvio_filter.h.
+"""
+import ctypes as C
+
+import numpy as np
+
+from eqvio_amd.capi import Camera, Settings, c_double_p, c_int_p, load_eqf_lib, load_filter_lib
+
+EQF_BATCH_MAX_LANDMARKS = 64
+BATCH_REMOVED_OLD, BATCH_REMOVED_OUTLIERS, BATCH_ADDED, BATCH_EMPTY, BATCH_UPDATED, BATCH_REMOVED_INVALID = 1, 2, 4, 8, 16, 32
+
+
+class BatchFrame(C.Structure):
+    """eqf_batch_frame (include/eqf_batch.h)."""
+
+    _fields_ = [("slot", C.c_int), ("cam", Camera), ("imu13_mean", c_double_p), ("dt_total", C.c_double), ("k", C.c_int), ("imu13_k", c_double_p),
+                ("dt_k", c_double_p), ("M", C.c_int), ("ids", c_int_p), ("y", c_double_p)]
+
+
+def load_batch_protos():
+    """Declare the prototypes of include/eqf_batch.h on libeqf_hip.so and of include/eqvio_batch.h on libeqvio_filter.so."""
+    elib, flib = load_eqf_lib(), load_filter_lib()
+    if getattr(flib, "_batch_declared", None):
+        return elib, flib
+    vp, P = C.c_void_p, C.POINTER
+    eprotos = {
+        "eqf_batch_create": (C.c_int, [P(vp), C.c_int, C.c_int, C.c_int, P(Settings)]),
+        "eqf_batch_destroy": (None, [vp]),
+        "eqf_batch_slots": (C.c_int, [vp]),
+        "eqf_batch_max_landmarks": (C.c_int, [vp]),
+        "eqf_batch_num_landmarks": (C.c_int, [vp, C.c_int]),
+        "eqf_batch_set_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
+        "eqf_batch_get_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
+        "eqf_batch_set_sigma": (C.c_int, [vp, C.c_int, c_double_p, C.c_int]),
+        "eqf_batch_get_sigma": (C.c_int, [vp, C.c_int, c_double_p, C.c_int]),
+        "eqf_batch_state_estimate": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int]),
+        "eqf_batch_step": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
+        "eqf_batch_last_result": (C.c_int, [vp, C.c_int, c_int_p, c_double_p]),
+        "eqf_batch_stream": (vp, [vp]),
+        "eqf_batch_synchronize": (C.c_int, [vp]),
+    }
+    fprotos = {
+        "eqvio_batch_create": (C.c_int, [P(vp), P(Settings), C.c_int, C.c_int, C.c_int]),
+        "eqvio_batch_create_slot_from_state": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int, C.c_double]),
+        "eqvio_batch_destroy": (None, [vp]),
+        "eqvio_batch_last_error": (C.c_char_p, [vp]),
+        "eqvio_batch_slots": (C.c_int, [vp]),
+        "eqvio_batch_process_imu": (C.c_int, [vp, C.c_int, c_double_p]),
+        "eqvio_batch_process_vision": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, P(Camera), c_int_p, c_int_p, c_double_p, c_int_p]),
+        "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
+        "eqvio_batch_state_estimate": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int]),
+        "eqvio_batch_get_eqf": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
+        "eqvio_batch_force_eqf": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int, c_double_p]),
+        "eqvio_batch_sigma_dim": (C.c_int, [vp, C.c_int]),
+        "eqvio_batch_get_sigma": (C.c_int, [vp, C.c_int, c_double_p, C.c_int]),
+        "eqvio_batch_get_time": (C.c_double, [vp, C.c_int]),
+        "eqvio_batch_is_initialised": (C.c_int, [vp, C.c_int]),
+        "eqvio_batch_core": (vp, [vp]),
+    }
+    for lib, protos in ((elib, eprotos), (flib, fprotos)):
+        for name, (res, args) in protos.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+    elib._batch_declared = sorted(eprotos)
+    flib._batch_declared = sorted(fprotos)
+    return elib, flib
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _dp(a):
+    return a.ctypes.data_as(c_double_p)
+
+
+def _ip(a):
+    return a.ctypes.data_as(c_int_p)
+
+
+class BatchError(RuntimeError):
+    def __init__(self, msg, code):
+        super().__init__(msg)
+        self.code = code
+
+
+class VIOFilterBatch:
+    """B reference VIOFilters on one MI355X, advanced together (include/eqvio_batch.h). Every slot starts as VIOFilter(settings) and initialises itself from
+    its first IMU sample, unless it is started from a state (start_slot)."""
+
+    def __init__(self, settings, slots, max_landmarks=EQF_BATCH_MAX_LANDMARKS, device=0):
+        self.elib, self.lib = load_batch_protos()
+        self.h = C.c_void_p()
+        self.settings = settings
+        self.max_landmarks = max_landmarks
+        rc = self.lib.eqvio_batch_create(C.byref(self.h), C.byref(settings), device, slots, max_landmarks)
+        if rc != 0:
+            raise BatchError(f"eqvio_batch_create: {rc} ({self.elib.eqf_error_string(rc).decode() if rc < 0 else 'see last error'})", rc)
+        self.slots = slots
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise BatchError("eqvio_batch: " + (self.lib.eqvio_batch_last_error(self.h).decode() if rc == -1 else self.elib.eqf_error_string(rc).decode()), rc)
+
+    def close(self):
+        if self.h:
+            self.lib.eqvio_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def start_slot(self, k, sensor, ids, p, time):
+        sensor, ids, p = _f64(sensor), _i32(ids), _f64(p)
+        self._chk(self.lib.eqvio_batch_create_slot_from_state(self.h, k, _dp(sensor), _ip(ids), _dp(p), len(ids), time))
+
+    def process_imu(self, k, imu13):
+        imu13 = _f64(imu13)
+        self._chk(self.lib.eqvio_batch_process_imu(self.h, k, _dp(imu13)))
+
+    def process_vision(self, entries):
+        """entries: list of (slot, stamp, camera, ids, y). One device step; returns the per-entry status codes."""
+        n = len(entries)
+        slots = _i32([e[0] for e in entries])
+        stamps = _f64([e[1] for e in entries])
+        cams = (Camera * max(n, 1))(*[e[2] for e in entries])
+        counts = _i32([len(e[3]) for e in entries])
+        ids = _i32(np.concatenate([np.asarray(e[3], np.int32) for e in entries]) if n else np.zeros(0, np.int32))
+        y = _f64(np.concatenate([np.asarray(e[4], np.float64).ravel() for e in entries]) if n else np.zeros(0))
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_process_vision(self.h, n, _ip(slots), _dp(stamps), cams, _ip(counts), _ip(ids), _dp(y), _ip(status)))
+        return status[:n].copy()
+
+    def run_prepared(self, sequences, first=0, count=None):
+        """Lockstep replay (eqvio_batch_run_prepared): sequences[k] is slot k's capi.PreparedFrames (or None); frame j of every slot goes in one device step, a
+        slot whose sequence has ended sits out. Returns the number of steps run."""
+        if len(sequences) > self.slots:
+            raise ValueError("more sequences than slots")
+        arr = (C.c_void_p * self.slots)(*([q.h if q is not None else None for q in sequences] + [None] * (self.slots - len(sequences))))
+        n = max(len(q) for q in sequences if q is not None)
+        count = n - first if count is None else count
+        rc = self.lib.eqvio_batch_run_prepared(self.h, arr, first, count)
+        if rc < 0:
+            self._chk(rc)
+        return rc
+
+    def synchronize(self):
+        self._chk(self.elib.eqf_batch_synchronize(self.core_handle()))
+
+    def core_handle(self):
+        return self.lib.eqvio_batch_core(self.h)
+
+    def last_result(self, k):
+        flags, depth = C.c_int(), C.c_double()
+        self._chk(self.elib.eqf_batch_last_result(self.core_handle(), k, C.byref(flags), C.byref(depth)))
+        return flags.value, depth.value
+
+    def slot(self, k):
+        if not 0 <= k < self.slots:
+            raise IndexError(k)
+        return BatchSlot(self, k)
+
+
+class BatchSlot:
+    """One slot of a VIOFilterBatch with capi.VIOFilter's method names. process_vision advances this slot alone (a step of one entry)."""
+
+    def __init__(self, batch, k):
+        self.b, self.k = batch, k
+        self.cap = EQF_BATCH_MAX_LANDMARKS
+
+    def process_imu(self, imu13):
+        self.b.process_imu(self.k, imu13)
+
+    def process_vision(self, stamp, cam, ids, y):
+        st = self.b.process_vision([(self.k, stamp, cam, ids, y)])
+        if st[0] != 0:
+            raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
+
+    def state_estimate(self):
+        s, ids, p = np.zeros(23), np.zeros(self.cap, np.int32), np.zeros(3 * self.cap)
+        N = self.b.lib.eqvio_batch_state_estimate(self.b.h, self.k, _dp(s), _ip(ids), _dp(p), self.cap)
+        if N < 0:
+            self.b._chk(N)
+        return s, ids[:N].copy(), p[: 3 * N].reshape(N, 3).copy()
+
+    def get_eqf(self):
+        xi0, Xs = np.zeros(23), np.zeros(23)
+        ids, q0, Q = np.zeros(self.cap, np.int32), np.zeros(3 * self.cap), np.zeros(5 * self.cap)
+        N = self.b.lib.eqvio_batch_get_eqf(self.b.h, self.k, _dp(xi0), _dp(Xs), _ip(ids), _dp(q0), _dp(Q), self.cap)
+        if N < 0:
+            self.b._chk(N)
+        return xi0, Xs, ids[:N].copy(), q0[: 3 * N].reshape(N, 3).copy(), Q[: 5 * N].reshape(N, 5).copy()
+
+    def force_eqf(self, xi0_sensor, X_sensor, ids, q0, Q, Sigma):
+        xi0_sensor, X_sensor, ids, q0, Q = _f64(xi0_sensor), _f64(X_sensor), _i32(ids), _f64(q0), _f64(Q)
+        S = np.asfortranarray(Sigma, dtype=np.float64)
+        self.b._chk(self.b.lib.eqvio_batch_force_eqf(self.b.h, self.k, _dp(xi0_sensor), _dp(X_sensor), _ip(ids), _dp(q0), _dp(Q), len(ids), S.ctypes.data_as(c_double_p)))
+
+    def sigma_dim(self):
+        return self.b.lib.eqvio_batch_sigma_dim(self.b.h, self.k)
+
+    def get_sigma(self):
+        n = self.sigma_dim()
+        out = np.zeros((n, n), order="F")
+        self.b._chk(self.b.lib.eqvio_batch_get_sigma(self.b.h, self.k, out.ctypes.data_as(c_double_p), n))
+        return out
+
+    def get_time(self):
+        return self.b.lib.eqvio_batch_get_time(self.b.h, self.k)
+
+    def is_initialised(self):
+        return bool(self.b.lib.eqvio_batch_is_initialised(self.b.h, self.k))

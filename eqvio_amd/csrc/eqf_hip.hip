@@ -2,6 +2,8 @@
 #include "eqf_hip.h"
 #include "eqf_kernels.hpp"
 #include "eqf_lookahead.hpp"
+#include "eqf_batch.hpp"
+#include "eqf_batch.h"
 #include "host_prof.hpp"
 #include <algorithm>
 #include <atomic>
@@ -619,11 +621,11 @@ bool camera_ok(const eqvio_camera* c) { return c->model >= EQVIO_CAMERA_PINHOLE 
 
 // Sensor-level terms of A and B (EqFStateMatrixA_euclid / EqFInputMatrixB_euclid sensor rows and the per-landmark
 // common factors; coordinateSuite/euclid.cpp:99-233 — identical for the inverse-depth suite, invdepth.cpp:47-63,152-166)
-void compute_common(const eqf_ctx* c, const double* imu13, Common& cm) {
-    const SensorState xh = sensor_action(c->X, c->xi0);
+void compute_common_at(const GroupSensor& X, const SensorState& xi0, const double* imu13, Common& cm, CommonK& ck) {
+    const SensorState xh = sensor_action(X, xi0);
     const V3 gyr = v3(imu13[1], imu13[2], imu13[3]) - xh.bgyr; // v_est = imu - bias (IMUVelocity.cpp:52-58)
     const V6 U_I{gyr, xh.vel};
-    const M3 R_A = q_mat(c->X.A.R);
+    const M3 R_A = q_mat(X.A.R);
     const M3 R_IC = q_mat(xh.cam.R);
     const M3 RTic = transpose(R_IC);
     auto put = [](const M3& A, double* d) {
@@ -634,9 +636,9 @@ void compute_common(const eqf_ctx* c, const double* imu13, Common& cm) {
     put(RTic, cm.RTic);
     put(RTic * skew(xh.cam.x), cm.RTicSx);
     // ad( Ad_{T0^-1} Ad_A U_I )
-    const V6 U1 = Ad_apply(pose_inv(c->xi0.cam), Ad_apply(c->X.A, U_I));
+    const V6 U1 = Ad_apply(pose_inv(xi0.cam), Ad_apply(X.A, U_I));
     const M6 adT = se3_adjoint(U1);
-    const M6 CT = m6_mul(se3_Adjoint(pose_inv(c->X.B)), adT);
+    const M6 CT = m6_mul(se3_Adjoint(pose_inv(X.B)), adT);
     std::memcpy(cm.CT, CT.a, sizeof(cm.CT));
     const V6 U_C = Ad_apply(pose_inv(xh.cam), U_I);
     pack_v3(U_C.v, cm.vC);
@@ -651,7 +653,7 @@ void compute_common(const eqf_ctx* c, const double* imu13, Common& cm) {
     for (int i = 0; i < 6; ++i)
         cm.Bs[i * 12 + 6 + i] = 1.0;
     setB(6, 0, R_A);
-    setB(9, 0, skew(c->X.A.x) * R_A);
+    setB(9, 0, skew(X.A.x) * R_A);
     setB(12, 0, R_A * skew(xh.vel));
     setB(12, 3, R_A);
     // A sensor block (21 x 21, row-major)
@@ -661,7 +663,7 @@ void compute_common(const eqf_ctx* c, const double* imu13, Common& cm) {
             cm.Ass[r * 21 + cc] = -cm.Bs[r * 12 + cc];
     for (int i = 0; i < 3; ++i)
         cm.Ass[(9 + i) * 21 + 12 + i] = 1.0;
-    const V3 gdir = q_rot(q_inv(c->xi0.pose.R), v3(0, 0, 1)); // xi0.sensor.gravityDir()
+    const V3 gdir = q_rot(q_inv(xi0.pose.R), v3(0, 0, 1)); // xi0.sensor.gravityDir()
     const M3 Gs = (-kGravity) * skew(gdir);
     const double g[9] = {Gs.a00, Gs.a01, Gs.a02, Gs.a10, Gs.a11, Gs.a12, Gs.a20, Gs.a21, Gs.a22};
     for (int i = 0; i < 3; ++i)
@@ -671,14 +673,15 @@ void compute_common(const eqf_ctx* c, const double* imu13, Common& cm) {
         for (int j = 0; j < 6; ++j)
             cm.Ass[(15 + i) * 21 + 15 + j] = adT.a[i * 6 + j];
     // kernel-argument form
-    CommonK& ck = const_cast<eqf_ctx*>(c)->ck;
     std::memcpy(ck.lm, cm.Mv, sizeof(double) * 66); // Mv, RTic, RTicSx, CT, vC are contiguous in Common
     put(R_A, ck.RA);
-    put(skew(c->X.A.x) * R_A, ck.SxRA);
+    put(skew(X.A.x) * R_A, ck.SxRA);
     put(R_A * skew(xh.vel), ck.RAsv);
     std::memcpy(ck.G, g, sizeof(g));
     std::memcpy(ck.adT, adT.a, sizeof(ck.adT));
 }
+
+void compute_common(const eqf_ctx* c, const double* imu13, Common& cm) { compute_common_at(c->X, c->xi0, imu13, cm, const_cast<eqf_ctx*>(c)->ck); }
 
 int upload_common(eqf_ctx* c, const double* imu13) {
     compute_common(c, imu13, *c->h_common); // h_common is host-only now (debug expansion); the kernels get c->ck by value
@@ -2327,18 +2330,16 @@ int eqf_integrate_riccati_discrete(eqf_ctx* c, const double* imu13, double dt, c
 
 // Host half of integrateObserverState for `chunk` consecutive IMU samples: the sensor-level group element Lambda of every
 // step (VIOGroup.cpp:190-271), applied to the host-authoritative X right away, and the per-step terms the landmark kernel needs.
-static void observer_host_steps(eqf_ctx* c, const double* imu13_k, const double* dt_k, int chunk, int discreteLift, ObsSteps& steps_arg) {
-    for (int s = 0; s < chunk; ++s) {
-        const double* imu = imu13_k + 13 * s;
-        const double dt = dt_k[s];
+// observer_host_step: one such step (X <- X * Lambda, st), shared with the filter batch.
+static void observer_host_step(GroupSensor& X, const SensorState& xi0, const double* imu, double dt, int discreteLift, ObsStep& st) {
+    {
         // stateEstimate() sensor part and the lift (VIOGroup.cpp:190-271)
-        const SensorState xh = sensor_action(c->X, c->xi0);
+        const SensorState xh = sensor_action(X, xi0);
         const V3 gyr = v3(imu[1], imu[2], imu[3]) - xh.bgyr;
         const V3 acc = v3(imu[4], imu[5], imu[6]) - xh.bacc;
         const V3 gbv = v3(imu[7], imu[8], imu[9]), abv = v3(imu[10], imu[11], imu[12]);
         const V3 gdir = q_rot(q_inv(xh.pose.R), v3(0, 0, 1));
         GroupSensor L;
-        ObsStep& st = steps_arg.s[s];
         st.discrete = discreteLift ? 1 : 0;
         st.dt = dt;
         if (discreteLift) {
@@ -2368,8 +2369,12 @@ static void observer_host_steps(eqf_ctx* c, const double* imu13_k, const double*
             st.omC = U_B.w;
             st.vC = U_B.v;
         }
-        c->X = group_mul(c->X, L);
+        X = group_mul(X, L);
     }
+}
+static void observer_host_steps(eqf_ctx* c, const double* imu13_k, const double* dt_k, int chunk, int discreteLift, ObsSteps& steps_arg) {
+    for (int s = 0; s < chunk; ++s)
+        observer_host_step(c->X, c->xi0, imu13_k + 13 * s, dt_k[s], discreteLift, steps_arg.s[s]);
 }
 // Device half: the landmark part runs on the second stream. It only has to wait for the last kernel that READS Q on the main
 // stream (k_assemble_AB of a preceding Riccati call: ev_early, else everything queued so far), so it overlaps the Sigma
@@ -3221,19 +3226,18 @@ static int settle_update(eqf_ctx* c) {
     }
     return 0;
 }
-static int apply_sensor_lift(eqf_ctx* c, int discreteCorr) {
-    std::memcpy(c->h_buf, c->h_res + 7 * (size_t)c->Ncap, sizeof(double) * 21);
-    const double* g = c->h_buf;
+// the sensor part of the innovation lift Delta from Gamma's 21 sensor rows (X <- Delta * X)
+static GroupSensor sensor_lift_delta(const double* g, const SensorState& xi0, int chart, int discreteCorr) {
     GroupSensor D;
     D.bgyr = v3(g[0], g[1], g[2]);
     D.bacc = v3(g[3], g[4], g[5]);
     V3 gw = v3(g[6], g[7], g[8]), gv = v3(g[9], g[10], g[11]), gvel = v3(g[12], g[13], g[14]);
     V3 cw = v3(g[15], g[16], g[17]), cv = v3(g[18], g[19], g[20]);
-    const bool normal = c->chart == EQVIO_COORD_NORMAL;
+    const bool normal = chart == EQVIO_COORD_NORMAL;
     if (normal && !discreteCorr) {
         // liftInnovation_normal = liftInnovation_euclid(M^-1 Gamma) (normal.cpp:47-50); sensor block of M^-1: [12:15,6:9] = skew(v0), [15:21,6:12] = -Ad(T0^-1)
-        gvel = gvel + cross(c->xi0.vel, gw);
-        const V6 UA = Ad_apply(pose_inv(c->xi0.cam), V6{gw, gv});
+        gvel = gvel + cross(xi0.vel, gw);
+        const V6 UA = Ad_apply(pose_inv(xi0.cam), V6{gw, gv});
         cw = cw - UA.w;
         cv = cv - UA.v;
     }
@@ -3248,17 +3252,23 @@ static int apply_sensor_lift(eqf_ctx* c, int discreteCorr) {
     } else if (discreteCorr) {
         // liftInnovationDiscrete sensor part (euclid.cpp:74-79 == invdepth.cpp:228-233)
         D.A = se3_exp(gw, gv);
-        D.w = c->xi0.vel - q_rot(D.A.R, c->xi0.vel + gvel);
-        D.B = pose_mul(pose_mul(pose_mul(pose_inv(c->xi0.cam), D.A), c->xi0.cam), se3_exp(cw, cv));
+        D.w = xi0.vel - q_rot(D.A.R, xi0.vel + gvel);
+        D.B = pose_mul(pose_mul(pose_mul(pose_inv(xi0.cam), D.A), xi0.cam), se3_exp(cw, cv));
     } else {
         // VIOExp(liftInnovation) sensor part (euclid.cpp:40-51, VIOGroup.cpp:273-283)
-        const V3 u_w = -gvel - cross(gw, c->xi0.vel);
-        const V6 UB0 = Ad_apply(pose_inv(c->xi0.cam), V6{gw, gv});
+        const V3 u_w = -gvel - cross(gw, xi0.vel);
+        const V6 UB0 = Ad_apply(pose_inv(xi0.cam), V6{gw, gv});
         const M3 V = so3_V(gw);
         D.A = Pose{so3_exp(gw), V * gv};
         D.w = V * u_w;
         D.B = se3_exp(cw + UB0.w, cv + UB0.v);
     }
+    return D;
+}
+static int apply_sensor_lift(eqf_ctx* c, int discreteCorr) {
+    std::memcpy(c->h_buf, c->h_res + 7 * (size_t)c->Ncap, sizeof(double) * 21);
+    const double* g = c->h_buf;
+    const GroupSensor D = sensor_lift_delta(g, c->xi0, c->chart, discreteCorr);
     c->X = group_mul(D, c->X);
     if (c->opt_check) { // the finite check ran after the result packet was written: fetch its verdict
         const int r = read_flags(c);
@@ -3997,3 +4007,460 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 }
 
 } // extern "C"
+
+// ===================================================================================================
+// Filter batch (include/eqf_batch.h, kernel in eqf_batch.hpp): B slots of <= 64 landmarks, one launch per step.
+struct eqf_batch {
+    struct Slot {
+        SensorState xi0{};
+        GroupSensor X{};
+        std::vector<int> ids;
+        int cur = 0;
+        int flags = 0;
+        double depth = 0.0;
+    };
+    int device = 0, slots = 0, cap = 0, ld = 0, chart = 0;
+    eqvio_settings set{};
+    double Qd[12], Pd[8];
+    hipStream_t stream = nullptr;
+    double *d_sig = nullptr, *d_lm = nullptr, *d_scr = nullptr;
+    size_t sig_stride = 0, lm_stride = 0, scr_stride = 0;
+    BatchIn *h_in = nullptr, *d_in = nullptr;
+    BatchOut *h_out = nullptr, *d_out = nullptr;
+    ObsStep *h_steps = nullptr, *d_steps = nullptr;
+    int in_cap = 0, steps_cap = 0;
+    std::vector<Slot> s;
+};
+
+namespace {
+GroupSensor group_identity() {
+    GroupSensor g;
+    g.bgyr = v3(0, 0, 0);
+    g.bacc = v3(0, 0, 0);
+    g.A = pose_identity();
+    g.w = v3(0, 0, 0);
+    g.B = pose_identity();
+    return g;
+}
+int batch_grow_packets(eqf_batch* b, int entries, int steps) {
+    if (entries > b->in_cap) {
+        if (b->h_in)
+            HIPCHK(hipHostFree(b->h_in));
+        if (b->d_in)
+            HIPCHK(hipFree(b->d_in));
+        if (b->h_out)
+            HIPCHK(hipHostFree(b->h_out));
+        if (b->d_out)
+            HIPCHK(hipFree(b->d_out));
+        b->h_in = nullptr, b->d_in = nullptr, b->h_out = nullptr, b->d_out = nullptr, b->in_cap = 0;
+        HIPCHK(hipHostMalloc((void**)&b->h_in, sizeof(BatchIn) * entries, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void**)&b->d_in, sizeof(BatchIn) * entries));
+        HIPCHK(hipHostMalloc((void**)&b->h_out, sizeof(BatchOut) * entries, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void**)&b->d_out, sizeof(BatchOut) * entries));
+        b->in_cap = entries;
+    }
+    if (steps > b->steps_cap) {
+        if (b->h_steps)
+            HIPCHK(hipHostFree(b->h_steps));
+        if (b->d_steps)
+            HIPCHK(hipFree(b->d_steps));
+        b->h_steps = nullptr, b->d_steps = nullptr, b->steps_cap = 0;
+        const int n = std::max(steps, 64);
+        HIPCHK(hipHostMalloc((void**)&b->h_steps, sizeof(ObsStep) * n, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void**)&b->d_steps, sizeof(ObsStep) * n));
+        b->steps_cap = n;
+    }
+    return 0;
+}
+double* batch_sig(eqf_batch* b, int slot, int which) { return b->d_sig + (2 * (size_t)slot + which) * b->sig_stride; }
+double* batch_lm(eqf_batch* b, int slot, int which) { return b->d_lm + (2 * (size_t)slot + which) * b->lm_stride; }
+// the slot's current landmark planes on the host: 8 doubles per landmark (q0[3], Q[4], a)
+int batch_fetch_landmarks(eqf_batch* b, int slot, std::vector<double>& out) {
+    const int N = (int)b->s[slot].ids.size();
+    std::vector<double> pl((size_t)BATCH_PLANES * BATCH_L);
+    HIPCHK(hipMemcpy(pl.data(), batch_lm(b, slot, b->s[slot].cur), sizeof(double) * pl.size(), hipMemcpyDeviceToHost));
+    out.assign(8 * (size_t)N, 0.0);
+    for (int i = 0; i < N; ++i) {
+        for (int c = 0; c < 3; ++c)
+            out[8 * i + c] = pl[c * BATCH_L + i];
+        for (int c = 0; c < 4; ++c)
+            out[8 * i + 3 + c] = pl[(BATCH_QQ + c) * BATCH_L + i];
+        out[8 * i + 7] = pl[BATCH_QA * BATCH_L + i];
+    }
+    return 0;
+}
+bool batch_slot_ok(const eqf_batch* b, int slot) { return b && slot >= 0 && slot < b->slots; }
+// every entry point that allocates, copies or launches runs on the batch's device, and leaves the caller's current device as it was
+struct BatchDevice {
+    int prev = -1;
+    explicit BatchDevice(const eqf_batch* b) {
+        if (hipGetDevice(&prev) != hipSuccess)
+            prev = -1;
+        if (b && prev != b->device)
+            (void)hipSetDevice(b->device);
+    }
+    ~BatchDevice() {
+        if (prev >= 0)
+            (void)hipSetDevice(prev);
+    }
+};
+} // namespace
+
+int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, const eqvio_settings* st) {
+    if (!out || !st || slots < 1 || max_landmarks < 1 || max_landmarks > EQF_BATCH_MAX_LANDMARKS || device < 0)
+        return EQF_E_BAD_ARG;
+    if (st->coordinateChoice != EQVIO_COORD_EUCLIDEAN && st->coordinateChoice != EQVIO_COORD_INVDEPTH && st->coordinateChoice != EQVIO_COORD_NORMAL)
+        return EQF_E_BAD_ARG;
+    if (!st->fastRiccati || st->coordinateChoice == EQVIO_COORD_NORMAL)
+        return EQF_E_UNSUPPORTED; // accurate / discrete Riccati and the Normal chart: the per-context path (eqf_hip.h)
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device >= ndev)
+        return EQF_E_NO_DEVICE;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
+        return EQF_E_NO_DEVICE;
+    HIPCHK(hipSetDevice(device));
+    eqf_batch* b = new eqf_batch();
+    b->device = device;
+    b->slots = slots;
+    b->cap = max_landmarks;
+    b->set = *st;
+    b->chart = st->coordinateChoice;
+    b->ld = pick_ld(BATCH_NMAX);
+    const double qv[4] = {st->velGyrNoise * st->velGyrNoise, st->velAccNoise * st->velAccNoise, st->velGyrBiasWalk * st->velGyrBiasWalk,
+                          st->velAccBiasWalk * st->velAccBiasWalk}; // constructInputGainMatrix (VIOFilterSettings.h:192-201)
+    for (int i = 0; i < 12; ++i)
+        b->Qd[i] = qv[i / 3];
+    const double pv[8] = {st->biasOmegaProcessVariance, st->biasAccelProcessVariance, st->attitudeProcessVariance, st->positionProcessVariance,
+                          st->velocityProcessVariance,  st->cameraAttitudeProcessVariance, st->cameraPositionProcessVariance, st->pointProcessVariance};
+    std::memcpy(b->Pd, pv, sizeof(pv));
+    b->sig_stride = (size_t)b->ld * BATCH_NMAX;
+    b->lm_stride = (size_t)BATCH_PLANES * BATCH_L;
+    b->scr_stride = batch_scr_doubles(b->ld);
+    b->s.resize(slots);
+    for (auto& sl : b->s) {
+        sl.xi0 = unpack_sensor(std::vector<double>{0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0}.data());
+        sl.X = group_identity();
+    }
+    auto fail = [&](int rc) {
+        eqf_batch_destroy(b);
+        return rc;
+    };
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+        return fail(EQF_E_CAPACITY);
+    if (hipMalloc((void**)&b->d_sig, sizeof(double) * b->sig_stride * 2 * slots) != hipSuccess ||
+        hipMalloc((void**)&b->d_lm, sizeof(double) * b->lm_stride * 2 * slots) != hipSuccess ||
+        hipMalloc((void**)&b->d_scr, sizeof(double) * b->scr_stride * slots) != hipSuccess)
+        return fail(EQF_E_CAPACITY);
+    if (hipMemsetAsync(b->d_sig, 0, sizeof(double) * b->sig_stride * 2 * slots, b->stream) != hipSuccess ||
+        hipMemsetAsync(b->d_lm, 0, sizeof(double) * b->lm_stride * 2 * slots, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
+        return fail(EQF_E_CAPACITY);
+    if (batch_grow_packets(b, std::min(slots, 64), 64 * 16))
+        return fail(EQF_E_CAPACITY);
+    *out = b;
+    return EQF_OK;
+}
+void eqf_batch_destroy(eqf_batch* b) {
+    if (!b)
+        return;
+    BatchDevice dev(b);
+    if (b->stream)
+        (void)hipStreamSynchronize(b->stream);
+    (void)hipFree(b->d_sig);
+    (void)hipFree(b->d_lm);
+    (void)hipFree(b->d_scr);
+    (void)hipFree(b->d_in);
+    (void)hipFree(b->d_out);
+    (void)hipFree(b->d_steps);
+    if (b->h_in)
+        (void)hipHostFree(b->h_in);
+    if (b->h_out)
+        (void)hipHostFree(b->h_out);
+    if (b->h_steps)
+        (void)hipHostFree(b->h_steps);
+    if (b->stream)
+        (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+int eqf_batch_slots(const eqf_batch* b) { return b ? b->slots : EQF_E_BAD_ARG; }
+int eqf_batch_max_landmarks(const eqf_batch* b) { return b ? b->cap : EQF_E_BAD_ARG; }
+int eqf_batch_num_landmarks(const eqf_batch* b, int slot) { return batch_slot_ok(b, slot) ? (int)b->s[slot].ids.size() : EQF_E_BAD_ARG; }
+void* eqf_batch_stream(eqf_batch* b) { return b ? (void*)b->stream : nullptr; }
+int eqf_batch_synchronize(eqf_batch* b) {
+    if (!b)
+        return EQF_E_BAD_ARG;
+    BatchDevice dev(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int eqf_batch_set_state(eqf_batch* b, int slot, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N) {
+    if (!batch_slot_ok(b, slot) || !xi0_sensor || !X_sensor || N < 0 || N > b->cap || (N > 0 && (!ids || !q0 || !Q)))
+        return EQF_E_BAD_ARG;
+    eqf_batch::Slot& sl = b->s[slot];
+    BatchDevice dev(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (N > 0) {
+        double *d_p = nullptr, *d_Q = nullptr;
+        HIPCHK(hipMalloc((void**)&d_p, sizeof(double) * 8 * N));
+        d_Q = d_p + 3 * N;
+        HIPCHK(hipMemcpy(d_p, q0, sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_Q, Q, sizeof(double) * 5 * N, hipMemcpyHostToDevice));
+        double* lm = batch_lm(b, slot, sl.cur);
+        hipLaunchKernelGGL(k_scatter_landmarks, dim3(1), dim3(64), 0, b->stream, N, 0, BATCH_L, d_p, d_Q, lm, lm + (size_t)BATCH_QQ * BATCH_L,
+                           lm + (size_t)BATCH_QA * BATCH_L);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(b->stream));
+        HIPCHK(hipFree(d_p));
+    }
+    sl.xi0 = unpack_sensor(xi0_sensor);
+    sl.X = unpack_group(X_sensor);
+    sl.ids.assign(ids, ids + N);
+    return 0;
+}
+int eqf_batch_get_state(eqf_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    eqf_batch::Slot& sl = b->s[slot];
+    const int N = (int)sl.ids.size();
+    if (N > cap)
+        return EQF_E_CAPACITY;
+    BatchDevice dev(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (xi0_sensor)
+        pack_sensor(sl.xi0, xi0_sensor);
+    if (X_sensor)
+        pack_group(sl.X, X_sensor);
+    std::vector<double> lm;
+    if (int rc = batch_fetch_landmarks(b, slot, lm))
+        return rc;
+    for (int i = 0; i < N; ++i) {
+        if (ids)
+            ids[i] = sl.ids[i];
+        if (q0)
+            for (int c = 0; c < 3; ++c)
+                q0[3 * i + c] = lm[8 * i + c];
+        if (Q)
+            for (int c = 0; c < 5; ++c)
+                Q[5 * i + c] = lm[8 * i + 3 + c];
+    }
+    return N;
+}
+int eqf_batch_set_sigma(eqf_batch* b, int slot, const double* sig, int n) {
+    if (!batch_slot_ok(b, slot) || !sig || n != 21 + 3 * (int)b->s[slot].ids.size())
+        return EQF_E_BAD_ARG;
+    BatchDevice dev(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemcpy2D(batch_sig(b, slot, b->s[slot].cur), sizeof(double) * b->ld, sig, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
+    return 0;
+}
+int eqf_batch_get_sigma(eqf_batch* b, int slot, double* sig, int n) {
+    if (!batch_slot_ok(b, slot) || !sig || n != 21 + 3 * (int)b->s[slot].ids.size())
+        return EQF_E_BAD_ARG;
+    BatchDevice dev(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemcpy2D(sig, sizeof(double) * n, batch_sig(b, slot, b->s[slot].cur), sizeof(double) * b->ld, sizeof(double) * n, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+int eqf_batch_state_estimate(eqf_batch* b, int slot, double* sensor, int* ids, double* p, int cap) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    eqf_batch::Slot& sl = b->s[slot];
+    const int N = (int)sl.ids.size();
+    if (N > cap)
+        return EQF_E_CAPACITY;
+    BatchDevice dev(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (sensor)
+        pack_sensor(sensor_action(sl.X, sl.xi0), sensor);
+    std::vector<double> lm;
+    if (int rc = batch_fetch_landmarks(b, slot, lm))
+        return rc;
+    for (int i = 0; i < N; ++i) {
+        if (ids)
+            ids[i] = sl.ids[i];
+        if (p) { // stateGroupAction landmark part: q_hat = Q^-1 q0 (VIOGroup.cpp:45-52)
+            const double* e = lm.data() + 8 * i;
+            const V3 qh = (1.0 / e[7]) * q_rot(q_inv(Qt{e[3], e[4], e[5], e[6]}), v3(e[0], e[1], e[2]));
+            pack_v3(qh, p + 3 * i);
+        }
+    }
+    return N;
+}
+int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    if (flags)
+        *flags = b->s[slot].flags;
+    if (depth)
+        *depth = b->s[slot].depth;
+    return 0;
+}
+
+int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
+    if (!b || count < 0 || (count > 0 && (!frames || !status)))
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchDevice dev(b);
+    int total_steps = 0;
+    for (int e = 0; e < count; ++e)
+        total_steps += std::max(frames[e].k, 0);
+    if (int rc = batch_grow_packets(b, count, total_steps))
+        return rc;
+    // host half: validation, the landmark bookkeeping the ids decide, the sensor-level terms and the observer steps' sensor part
+    std::vector<int> entry_of(b->slots, -1), listed;
+    std::vector<GroupSensor> X_after(count);
+    std::vector<std::vector<int>> surv_ids(count), new_ids(count);
+    std::vector<int> removed_old(count, 0);
+    int nin = 0, nsteps = 0;
+    std::vector<int> in_of(count, -1);
+    for (int e = 0; e < count; ++e) {
+        const eqf_batch_frame& f = frames[e];
+        status[e] = 0;
+        if (!batch_slot_ok(b, f.slot) || entry_of[f.slot] >= 0 || f.M < 0 || f.k < 0 || (f.M > 0 && (!f.ids || !f.y)) || !f.imu13_mean ||
+            (f.k > 0 && (!f.imu13_k || !f.dt_k)) || !camera_ok(&f.cam)) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        bool asc = true;
+        for (int j = 1; j < f.M; ++j)
+            asc = asc && f.ids[j] > f.ids[j - 1];
+        if (!asc) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        entry_of[f.slot] = e;
+        eqf_batch::Slot& sl = b->s[f.slot];
+        const int N0 = (int)sl.ids.size();
+        // removeOldLandmarks (VIOFilter.cpp:280-302) and the ids addNewLandmarks will append (:258-278)
+        std::vector<int> surv;
+        for (int i = 0; i < N0; ++i)
+            if (!b->set.removeLostLandmarks || std::binary_search(f.ids, f.ids + f.M, sl.ids[i]))
+                surv.push_back(i);
+        std::vector<int> midx(f.M);
+        int nnew = 0;
+        for (int j = 0; j < f.M; ++j) {
+            int found = -1;
+            for (size_t t = 0; t < surv.size(); ++t)
+                if (sl.ids[surv[t]] == f.ids[j]) {
+                    found = (int)t;
+                    break;
+                }
+            if (found < 0)
+                for (int i = 0; i < N0 && found < 0; ++i)
+                    if (sl.ids[i] == f.ids[j])
+                        found = -2; // unmeasured-and-removed cannot happen: a measured id survives
+            midx[j] = found >= 0 ? found : -(1 + nnew++);
+        }
+        if ((int)surv.size() + nnew > b->cap || f.M > b->cap) {
+            status[e] = EQF_E_CAPACITY;
+            entry_of[f.slot] = -1;
+            continue;
+        }
+        BatchIn& in = b->h_in[nin];
+        in.slot = f.slot;
+        in.cur = sl.cur;
+        in.Ns = (int)surv.size();
+        in.M = f.M;
+        in.nnew = nnew;
+        in.k = f.k;
+        in.obs_off = nsteps;
+        in.max_outliers = (int)(size_t)((1.0 - b->set.featureRetention) * f.M); // removeOutliers (VIOFilter.cpp:305)
+        Cam cam = make_cam(&f.cam);
+        in.cam = cam;
+        in.dt = f.dt_total;
+        for (size_t t = 0; t < surv.size(); ++t)
+            in.surv[t] = (int)surv[t];
+        for (int j = 0; j < f.M; ++j) {
+            in.midx[j] = midx[j];
+            in.y[2 * j] = f.y[2 * j];
+            in.y[2 * j + 1] = f.y[2 * j + 1];
+            if (midx[j] < 0) {
+                const V3 br = cam_undistort(cam, f.y[2 * j], f.y[2 * j + 1]); // measurement.cameraPtr->undistortPoint (VIOFilter.cpp:264)
+                const int r = -midx[j] - 1;
+                in.bear[3 * r] = br.x, in.bear[3 * r + 1] = br.y, in.bear[3 * r + 2] = br.z;
+                new_ids[e].push_back(f.ids[j]);
+            }
+        }
+        Common cm;
+        compute_common_at(sl.X, sl.xi0, f.imu13_mean, cm, in.ck); // integrateRiccatiStateFast at the current X
+        GroupSensor X = sl.X;
+        for (int s = 0; s < f.k; ++s)
+            observer_host_step(X, sl.xi0, f.imu13_k + 13 * s, f.dt_k[s], b->set.useDiscreteVelocityLift, b->h_steps[nsteps + s]);
+        nsteps += f.k;
+        X_after[e] = X;
+        for (int i : surv)
+            surv_ids[e].push_back(sl.ids[i]);
+        removed_old[e] = (int)surv.size() < N0;
+        in_of[e] = nin++;
+    }
+    if (nin == 0)
+        return 0;
+    BatchArgs ba;
+    ba.chart = b->chart;
+    ba.star = b->set.useEquivariantOutput;
+    ba.discrete = b->set.useDiscreteInnovationLift;
+    ba.median = b->set.useMedianDepth;
+    ba.ld = b->ld;
+    ba.thrAbs = b->set.outlierThresholdAbs;
+    ba.thrProb = b->set.outlierThresholdProb;
+    ba.meas_var = b->set.measurementNoise * b->set.measurementNoise;
+    ba.init_var = b->set.initialPointVariance;
+    ba.init_depth = b->set.initialSceneDepth;
+    std::memcpy(ba.Qd, b->Qd, sizeof(ba.Qd));
+    std::memcpy(ba.Pd, b->Pd, sizeof(ba.Pd));
+    ba.sig = b->d_sig;
+    ba.lm = b->d_lm;
+    ba.scr = b->d_scr;
+    ba.sig_stride = b->sig_stride;
+    ba.lm_stride = b->lm_stride;
+    ba.scr_stride = b->scr_stride;
+    ba.in = b->d_in;
+    ba.steps = b->d_steps;
+    ba.out = b->d_out;
+    HIPCHK(hipMemcpyAsync(b->d_in, b->h_in, sizeof(BatchIn) * nin, hipMemcpyHostToDevice, b->stream));
+    if (nsteps)
+        HIPCHK(hipMemcpyAsync(b->d_steps, b->h_steps, sizeof(ObsStep) * nsteps, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_frame, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, sizeof(BatchOut) * nin, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    // host half of the results: landmark ids, the sensor lift
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        const BatchOut& o = b->h_out[in_of[e]];
+        eqf_batch::Slot& sl = b->s[frames[e].slot];
+        sl.X = X_after[e];
+        std::vector<int> ids;
+        for (size_t t = 0; t < surv_ids[e].size(); ++t)
+            if (!((o.outliers >> t) & 1ull))
+                ids.push_back(surv_ids[e][t]);
+        ids.insert(ids.end(), new_ids[e].begin(), new_ids[e].end());
+        int flags = (removed_old[e] ? EQF_BATCH_REMOVED_OLD : 0) | ((o.did & BATCH_DID_OUTLIERS) ? EQF_BATCH_REMOVED_OUTLIERS : 0) |
+                    ((o.did & BATCH_DID_ADDED) ? EQF_BATCH_ADDED : 0) | ((o.did & BATCH_DID_EMPTY) ? EQF_BATCH_EMPTY : 0);
+        if (o.status == 0 && (o.did & BATCH_DID_UPDATE)) {
+            sl.X = group_mul(sensor_lift_delta(o.gamma, sl.xi0, b->chart, b->set.useDiscreteInnovationLift), sl.X);
+            flags |= EQF_BATCH_UPDATED;
+            if (o.did & BATCH_DID_INVALID) {
+                std::vector<int> kept;
+                for (size_t t = 0; t < ids.size(); ++t)
+                    if (!((o.invalid >> t) & 1ull))
+                        kept.push_back(ids[t]);
+                ids.swap(kept);
+                flags |= EQF_BATCH_REMOVED_INVALID;
+            }
+        } else if (o.status != 0) {
+            status[e] = o.status;
+        }
+        sl.ids.swap(ids);
+        sl.cur = o.cur;
+        sl.flags = flags;
+        sl.depth = o.depth;
+        if ((int)sl.ids.size() != o.N)
+            status[e] = EQF_E_BAD_ARG; // bookkeeping disagreement: cannot happen
+    }
+    return 0;
+}

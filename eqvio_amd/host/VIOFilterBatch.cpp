@@ -1,0 +1,326 @@
+// VIOFilterBatch (VIOFilterBatch.hpp) and its C-ABI (include/eqvio_batch.h).
+#include "VIOFilterBatch.hpp"
+#include "eqvio_batch.h"
+#include "PreparedFrames.hpp"
+#include <algorithm>
+#include <cstring>
+#include <array>
+#include <stdexcept>
+#include <string>
+
+namespace eqvio_amd {
+
+ImuSelection selectImu(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime) { // VIOFilter.cpp:134-156
+    ImuSelection s;
+    s.dts.resize(buffer.size());
+    for (size_t i = 0; i < buffer.size(); ++i) {
+        const double t0 = std::max(buffer.at(i).stamp, currentTime);
+        const double t1 = i + 1 < buffer.size() ? std::min(buffer.at(i + 1).stamp, newTime) : newTime;
+        s.dts[i] = std::max(t1 - t0, 0.0);
+    }
+    IMUVelocity acc = IMUVelocity::Zero();
+    for (size_t i = 0; i < buffer.size(); ++i) {
+        s.total += s.dts[i];
+        acc = acc + buffer.at(i) * s.dts[i];
+    }
+    s.mean = acc * (1.0 / s.total);
+    return s;
+}
+void trimImuBuffer(std::vector<IMUVelocity>& buffer, double currentTime) { // VIOFilter.cpp:182-189
+    auto it = std::find_if(buffer.begin(), buffer.end(), [currentTime](const IMUVelocity& v) { return v.stamp >= currentTime; });
+    if (it != buffer.begin()) {
+        --it;
+        buffer.erase(buffer.begin(), it);
+    }
+}
+
+namespace {
+// constructInitialStateCovarianceDiag (VIOFilterSettings.h:208-229)
+std::vector<double> initialCovariance(const eqvio_settings& s, int N) {
+    std::vector<double> d(21 + 3 * (size_t)N, s.initialPointVariance);
+    const double v[7] = {s.initialBiasOmegaVariance, s.initialBiasAccelVariance, s.initialAttitudeVariance, s.initialPositionVariance,
+                         s.initialVelocityVariance,  s.initialCameraAttitudeVariance, s.initialCameraPositionVariance};
+    for (int b = 0; b < 7; ++b)
+        for (int k = 0; k < 3; ++k)
+            d[3 * b + k] = v[b];
+    if (s.initialPointDepthVariance > 0)
+        for (int i = 0; i < N; ++i)
+            d[21 + 3 * i + 2] = s.initialPointDepthVariance;
+    return d;
+}
+std::vector<double> diagonal(const std::vector<double>& d) {
+    const size_t n = d.size();
+    std::vector<double> m(n * n, 0.0);
+    for (size_t i = 0; i < n; ++i)
+        m[i * n + i] = d[i];
+    return m;
+}
+const double kIdentityGroup[23] = {0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
+struct BatchFailure : std::runtime_error {
+    int code;
+    BatchFailure(const std::string& m, int c) : std::runtime_error(m), code(c) {}
+};
+void check(int rc, const char* what) {
+    if (rc != 0)
+        throw BatchFailure(std::string(what) + ": " + eqf_error_string(rc), rc);
+}
+} // namespace
+
+VIOFilterBatch::VIOFilterBatch(const eqvio_settings& s, eqf_batch* b) : settings(s), batch(b) {
+    const int slots = eqf_batch_slots(b);
+    slotv.resize(slots);
+    // VIOFilter(const Settings&) (VIOFilter.cpp:31-41): xi0 with the camera offset, X = identity, Sigma = the initial sensor covariance
+    double xi0[23];
+    std::memcpy(xi0, kIdentityGroup, sizeof(xi0));
+    std::memcpy(xi0 + 16, s.cameraOffset, sizeof(double) * 7);
+    const std::vector<double> S = diagonal(initialCovariance(s, 0));
+    for (int k = 0; k < slots; ++k) {
+        const int rc = eqf_batch_set_state(batch, k, xi0, kIdentityGroup, nullptr, nullptr, nullptr, 0);
+        const int rc2 = rc ? rc : eqf_batch_set_sigma(batch, k, S.data(), 21);
+        if (rc2) {
+            eqf_batch_destroy(batch);
+            batch = nullptr;
+            check(rc2, "eqf_batch_set_state / eqf_batch_set_sigma");
+        }
+    }
+}
+VIOFilterBatch::~VIOFilterBatch() { eqf_batch_destroy(batch); }
+
+void VIOFilterBatch::startFromState(int k, const double* sensor, const int* ids, const double* p, int N, double time) { // VIOFilter.cpp:43-56
+    Slot& sl = slotv.at(k);
+    std::vector<double> Q(5 * (size_t)N);
+    for (int i = 0; i < N; ++i) {
+        const double q[5] = {1, 0, 0, 0, 1};
+        std::memcpy(Q.data() + 5 * i, q, sizeof(q));
+    }
+    check(eqf_batch_set_state(batch, k, sensor, kIdentityGroup, ids, p, Q.data(), N), "eqf_batch_set_state");
+    const std::vector<double> S = diagonal(initialCovariance(settings, N));
+    check(eqf_batch_set_sigma(batch, k, S.data(), 21 + 3 * N), "eqf_batch_set_sigma");
+    sl.velocityBuffer.clear();
+    sl.currentTime = time;
+    sl.initialised = true;
+}
+void VIOFilterBatch::processIMUData(int k, const IMUVelocity& imu) { // VIOFilter.cpp:58-63
+    Slot& sl = slotv.at(k);
+    if (!sl.initialised)
+        initialiseFromIMUData(k, imu);
+    sl.velocityBuffer.emplace_back(imu);
+}
+void VIOFilterBatch::initialiseFromIMUData(int k, const IMUVelocity& imu) { // VIOFilter.cpp:65-78
+    const int N = eqf_batch_num_landmarks(batch, k);
+    std::vector<double> xi0(23), X(23), q0(3 * (size_t)N), Q(5 * (size_t)N);
+    std::vector<int> ids(N);
+    check(eqf_batch_get_state(batch, k, xi0.data(), X.data(), ids.data(), q0.data(), Q.data(), N) < 0 ? -1 : 0, "eqf_batch_get_state");
+    for (int i = 0; i < 6; ++i)
+        xi0[i] = 0.0;
+    const Qt R = so3_from_vectors(normalized(imu.acc), V3{0, 0, 1});
+    const double pose[7] = {R.w, R.x, R.y, R.z, 0, 0, 0};
+    std::memcpy(xi0.data() + 6, pose, sizeof(pose));
+    xi0[13] = xi0[14] = xi0[15] = 0.0;
+    check(eqf_batch_set_state(batch, k, xi0.data(), X.data(), ids.data(), q0.data(), Q.data(), N), "eqf_batch_set_state");
+    slotv.at(k).initialised = true;
+    slotv.at(k).currentTime = imu.stamp;
+}
+
+// processVisionData's early returns (VIOFilter.cpp:135-136, 198-199) and the IMU selection of integrateUpToTime; adds slot k's frame as entry e
+bool VIOFilterBatch::prepareFrame(int e, int k, double stamp, const eqvio_camera& cam, int M, const int* ids, const double* y, int* status) {
+    status[e] = 0;
+    if (k < 0 || k >= (int)slotv.size()) {
+        status[e] = EQF_E_BAD_ARG;
+        return false;
+    }
+    Slot& sl = slotv[k];
+    if (stamp <= sl.currentTime || sl.currentTime < 0 || sl.velocityBuffer.empty() || !sl.initialised)
+        return false;
+    const size_t t = frames_.size();
+    if (imus_.size() <= t)
+        imus_.resize(t + 1), dts_.resize(t + 1), means_.resize(t + 1);
+    const ImuSelection sel = selectImu(sl.velocityBuffer, sl.currentTime, stamp);
+    means_[t].resize(13);
+    sel.mean.pack(means_[t].data());
+    imus_[t].resize(13 * sl.velocityBuffer.size());
+    for (size_t i = 0; i < sl.velocityBuffer.size(); ++i)
+        sl.velocityBuffer[i].pack(imus_[t].data() + 13 * i);
+    dts_[t] = sel.dts;
+    eqf_batch_frame f;
+    f.slot = k;
+    f.cam = cam;
+    f.dt_total = sel.total;
+    f.k = (int)sl.velocityBuffer.size();
+    f.M = M;
+    f.ids = ids;
+    f.y = y;
+    frames_.push_back(f);
+    entry_.push_back(e);
+    return true;
+}
+void VIOFilterBatch::stepPrepared(const int* slots, const double* stamps, int* status) {
+    if (frames_.empty())
+        return;
+    for (size_t t = 0; t < frames_.size(); ++t) { // the vectors have their final addresses now
+        frames_[t].imu13_mean = means_[t].data();
+        frames_[t].imu13_k = imus_[t].data();
+        frames_[t].dt_k = dts_[t].data();
+    }
+    st_.resize(frames_.size());
+    check(eqf_batch_step(batch, (int)frames_.size(), frames_.data(), st_.data()), "eqf_batch_step");
+    for (size_t t = 0; t < frames_.size(); ++t) {
+        const int e = entry_[t];
+        status[e] = st_[t];
+        if (st_[t] == EQF_E_BAD_ARG || st_[t] == EQF_E_CAPACITY)
+            continue; // refused before the launch: the slot, its time and its IMU buffer are untouched
+        Slot& sl = slotv[slots[e]];
+        sl.currentTime = stamps[e];
+        trimImuBuffer(sl.velocityBuffer, sl.currentTime);
+    }
+}
+void VIOFilterBatch::processVisionData(int count, const int* slots, const double* stamps, const eqvio_camera* cams, const int* meas_counts, const int* ids_all,
+                                       const double* y_all, int* status) {
+    frames_.clear(), entry_.clear();
+    size_t mo = 0;
+    for (int e = 0; e < count; ++e) {
+        prepareFrame(e, slots[e], stamps[e], cams[e], meas_counts[e], ids_all + mo, y_all + 2 * mo, status);
+        mo += meas_counts[e];
+    }
+    stepPrepared(slots, stamps, status);
+}
+void VIOFilterBatch::processVisionData(int count, const int* slots, const VisionMeasurement* const* meas, int* status) {
+    frames_.clear(), entry_.clear();
+    std::vector<double> stamps(count);
+    for (int e = 0; e < count; ++e) {
+        const VisionMeasurement& m = *meas[e];
+        const auto fl = m.flat(); // validated against the measurement's map
+        stamps[e] = m.stamp;
+        prepareFrame(e, slots[e], m.stamp, m.cameraPtr->c, (int)fl.first->size(), fl.first->data(), fl.second->data(), status);
+    }
+    stepPrepared(slots, stamps.data(), status);
+}
+
+} // namespace eqvio_amd
+
+// ------------------------------------------------------------------------------------------------ C-ABI
+using eqvio_amd::IMUVelocity;
+using eqvio_amd::VIOFilterBatch;
+struct eqvio_batch {
+    VIOFilterBatch* f = nullptr;
+    std::string err;
+    ~eqvio_batch() { delete f; }
+};
+namespace {
+template <typename Fn> int guarded(eqvio_batch* b, Fn&& fn) {
+    if (!b)
+        return -1;
+    try {
+        fn();
+        return 0;
+    } catch (const std::exception& e) {
+        b->err = e.what();
+        return -1;
+    }
+}
+bool slot_ok(const eqvio_batch* b, int k) { return b && k >= 0 && k < b->f->slots(); }
+} // namespace
+
+int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* s, int device, int slots, int max_landmarks) {
+    if (!out || !s)
+        return EQF_E_BAD_ARG;
+    *out = nullptr;
+    { // the checks of eqf_batch_create, before anything touches a device
+        if (slots < 1 || max_landmarks < 1 || max_landmarks > EQF_BATCH_MAX_LANDMARKS || device < 0)
+            return EQF_E_BAD_ARG;
+        if (s->coordinateChoice < EQVIO_COORD_EUCLIDEAN || s->coordinateChoice > EQVIO_COORD_NORMAL)
+            return EQF_E_BAD_ARG;
+        if (!s->fastRiccati || s->coordinateChoice == EQVIO_COORD_NORMAL)
+            return EQF_E_UNSUPPORTED;
+    }
+    eqf_batch* core = nullptr;
+    const int rc = eqf_batch_create(&core, device, slots, max_landmarks, s); // EQF_E_NO_DEVICE without a gfx950 device
+    if (rc)
+        return rc;
+    auto* b = new eqvio_batch;
+    try {
+        b->f = new VIOFilterBatch(*s, core); // releases core itself if it throws
+    } catch (const eqvio_amd::BatchFailure& e) {
+        delete b;
+        return e.code;
+    }
+    *out = b;
+    return 0;
+}
+int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time) {
+    if (!slot_ok(b, slot) || !sensor || N < 0 || (N > 0 && (!ids || !p)))
+        return EQF_E_BAD_ARG;
+    return guarded(b, [&] { b->f->startFromState(slot, sensor, ids, p, N, time); });
+}
+void eqvio_batch_destroy(eqvio_batch* b) { delete b; }
+const char* eqvio_batch_last_error(const eqvio_batch* b) { return b ? b->err.c_str() : "null batch"; }
+int eqvio_batch_slots(const eqvio_batch* b) { return b ? b->f->slots() : EQF_E_BAD_ARG; }
+int eqvio_batch_process_imu(eqvio_batch* b, int slot, const double* imu13) {
+    if (!slot_ok(b, slot) || !imu13)
+        return EQF_E_BAD_ARG;
+    return guarded(b, [&] {
+        IMUVelocity r;
+        r.stamp = imu13[0];
+        r.gyr = eqf::V3{imu13[1], imu13[2], imu13[3]};
+        r.acc = eqf::V3{imu13[4], imu13[5], imu13[6]};
+        r.gyrBiasVel = eqf::V3{imu13[7], imu13[8], imu13[9]};
+        r.accBiasVel = eqf::V3{imu13[10], imu13[11], imu13[12]};
+        b->f->processIMUData(slot, r);
+    });
+}
+int eqvio_batch_process_vision(eqvio_batch* b, int count, const int* slots, const double* stamps, const eqvio_camera* cams, const int* meas_counts, const int* ids_all,
+                               const double* y_all, int* status) {
+    if (!b || count < 0 || (count > 0 && (!slots || !stamps || !cams || !meas_counts || !status)))
+        return EQF_E_BAD_ARG;
+    return guarded(b, [&] { b->f->processVisionData(count, slots, stamps, cams, meas_counts, ids_all, y_all, status); });
+}
+int eqvio_batch_state_estimate(eqvio_batch* b, int slot, double* sensor, int* ids, double* p, int cap) {
+    return slot_ok(b, slot) ? eqf_batch_state_estimate(b->f->core(), slot, sensor, ids, p, cap) : EQF_E_BAD_ARG;
+}
+int eqvio_batch_get_eqf(eqvio_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap) {
+    return slot_ok(b, slot) ? eqf_batch_get_state(b->f->core(), slot, xi0_sensor, X_sensor, ids, q0, Q, cap) : EQF_E_BAD_ARG;
+}
+int eqvio_batch_force_eqf(eqvio_batch* b, int slot, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N,
+                          const double* sigma) {
+    if (!slot_ok(b, slot) || !sigma)
+        return EQF_E_BAD_ARG;
+    const int rc = eqf_batch_set_state(b->f->core(), slot, xi0_sensor, X_sensor, ids, q0, Q, N);
+    return rc ? rc : eqf_batch_set_sigma(b->f->core(), slot, sigma, 21 + 3 * N);
+}
+int eqvio_batch_sigma_dim(const eqvio_batch* b, int slot) { return slot_ok(b, slot) ? 21 + 3 * eqf_batch_num_landmarks(b->f->core(), slot) : EQF_E_BAD_ARG; }
+int eqvio_batch_get_sigma(eqvio_batch* b, int slot, double* out, int n) { return slot_ok(b, slot) ? eqf_batch_get_sigma(b->f->core(), slot, out, n) : EQF_E_BAD_ARG; }
+double eqvio_batch_get_time(const eqvio_batch* b, int slot) { return slot_ok(b, slot) ? b->f->slot(slot).currentTime : -1.0; }
+int eqvio_batch_is_initialised(const eqvio_batch* b, int slot) { return slot_ok(b, slot) ? (b->f->slot(slot).initialised ? 1 : 0) : EQF_E_BAD_ARG; }
+eqf_batch* eqvio_batch_core(eqvio_batch* b) { return b ? b->f->core() : nullptr; }
+int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count) {
+    if (!b || !per_slot || first < 0 || count < 0)
+        return EQF_E_BAD_ARG;
+    const int B = b->f->slots();
+    int steps = 0;
+    const int rc = guarded(b, [&] {
+        std::vector<int> slots, status;
+        std::vector<const eqvio_amd::VisionMeasurement*> meas;
+        slots.reserve(B), status.reserve(B), meas.reserve(B);
+        for (int j = first; j < first + count; ++j) {
+            slots.clear(), meas.clear();
+            for (int k = 0; k < B; ++k) {
+                const eqvio_frames* fr = per_slot[k];
+                if (!fr || j >= (int)fr->meas.size())
+                    continue; // this slot's sequence has ended (or it has none): it sits the step out
+                for (size_t s = fr->imuBegin[j]; s < fr->imuBegin[j + 1]; ++s)
+                    b->f->processIMUData(k, fr->imus[s]);
+                slots.push_back(k);
+                meas.push_back(&fr->meas[j]);
+            }
+            if (slots.empty())
+                break;
+            status.assign(slots.size(), 0);
+            b->f->processVisionData((int)slots.size(), slots.data(), meas.data(), status.data());
+            for (size_t e = 0; e < slots.size(); ++e)
+                if (status[e] != 0)
+                    throw std::runtime_error("frame " + std::to_string(j) + ", slot " + std::to_string(slots[e]) + ": " + eqf_error_string(status[e]));
+            ++steps;
+        }
+    });
+    return rc ? rc : steps;
+}

@@ -1,0 +1,56 @@
+// VIOFilterBatch: the batched counterpart of VIOFilter (VIOFilter.hpp) - B slots, each the host state of one reference VIOFilter (IMU buffer, current
+// time, initialised flag; the EqF state lives in the device batch of include/eqf_batch.h), whose frames go to the device in one step.
+#pragma once
+#include "VIOFilter.hpp"
+#include "eqf_batch.h"
+#include <vector>
+
+namespace eqvio_amd {
+
+// IMU selection of VIOFilter::integrateUpToTime, fast-Riccati branch (src/VIOFilter.cpp:134-192): the dt of every buffered sample up to newTime, the mean
+// sample of the Riccati step over their sum, and the samples the buffer keeps afterwards. Same expressions as VIOFilter.cpp's mirror.
+struct ImuSelection {
+    std::vector<double> dts;
+    IMUVelocity mean;
+    double total = 0;
+};
+ImuSelection selectImu(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime);
+void trimImuBuffer(std::vector<IMUVelocity>& buffer, double currentTime);
+
+class VIOFilterBatch {
+  public:
+    struct Slot {
+        std::vector<IMUVelocity> velocityBuffer;
+        double currentTime = -1.0;
+        bool initialised = false;
+    };
+    // takes ownership of a batch made by eqf_batch_create with the same settings
+    VIOFilterBatch(const eqvio_settings& s, eqf_batch* batch);
+    ~VIOFilterBatch();
+    VIOFilterBatch(const VIOFilterBatch&) = delete;
+    VIOFilterBatch& operator=(const VIOFilterBatch&) = delete;
+    void startFromState(int slot, const double* sensor, const int* ids, const double* p, int N, double time);
+    void processIMUData(int slot, const IMUVelocity& imu);
+    // processVisionData for `count` slots in one device step; status per entry
+    void processVisionData(int count, const int* slots, const double* stamps, const eqvio_camera* cams, const int* meas_counts, const int* ids_all,
+                           const double* y_all, int* status);
+    // the same for measurements already built (a replay's VisionMeasurement objects): one device step for every listed slot
+    void processVisionData(int count, const int* slots, const VisionMeasurement* const* meas, int* status);
+    eqf_batch* core() { return batch; }
+    Slot& slot(int k) { return slotv.at(k); }
+    const Slot& slot(int k) const { return slotv.at(k); }
+    int slots() const { return (int)slotv.size(); }
+
+  private:
+    std::vector<eqf_batch_frame> frames_;
+    std::vector<int> entry_, st_;
+    std::vector<std::vector<double>> imus_, dts_, means_;
+    bool prepareFrame(int e, int k, double stamp, const eqvio_camera& cam, int M, const int* ids, const double* y, int* status);
+    void stepPrepared(const int* slots, const double* stamps, int* status);
+    void initialiseFromIMUData(int slot, const IMUVelocity& imu);
+    eqvio_settings settings;
+    eqf_batch* batch = nullptr;
+    std::vector<Slot> slotv;
+};
+
+} // namespace eqvio_amd

@@ -1,6 +1,7 @@
 // C-ABI wrapper of the host VIOFilter mirror (include/eqvio_filter.h).
 #include "eqvio_filter.h"
 #include "VIOFilter.hpp"
+#include "PreparedFrames.hpp"
 #include <cstring>
 
 using namespace eqvio_amd;
@@ -196,14 +197,6 @@ int eqvio_filter_last_timing(const eqvio_filter* f, double* a, double* b, double
         *c = f->t_corr;
     return 0;
 }
-// Prepared replay: the IMU samples and the VisionMeasurement objects (a std::map per frame, as the reference's tracker / data
-// server hands them to the filter, main_opt.cpp:196-214) are built once, outside any timed region.
-struct eqvio_frames {
-    GICameraPtr camPtr;
-    std::vector<VisionMeasurement> meas;
-    std::vector<IMUVelocity> imus;
-    std::vector<size_t> imuBegin; // nframes + 1 offsets into imus
-};
 eqvio_frames* eqvio_frames_create(const eqvio_camera* cam, int nframes, const int* imu_counts, const double* imu13_all, const double* stamps, const int* meas_counts,
                                   const int* ids_all, const double* y_all) {
     if (!cam || nframes < 0 || (nframes > 0 && (!imu_counts || !stamps || !meas_counts)))

@@ -1,0 +1,88 @@
+/* eqf_batch.h — C-ABI of the filter batch: B independent EqF filters ("slots") of at most 64 landmarks each on one MI355X (gfx950),
+ * advanced by one frame with ONE kernel launch (one workgroup per slot) and one host synchronisation per step.
+ *
+ * A slot is what one reference VIOFilter does in processVisionData with fast Riccati (src/VIOFilter.cpp:194-241): integrateRiccatiStateFast with the
+ * frame's mean IMU sample, the k observer steps, removeOldLandmarks (settings.removeLostLandmarks), removeOutliers, addNewLandmarks (median or fixed depth),
+ * performVisionUpdate and removeInvalidLandmarks. Its state is the one eqf_hip.h's context holds (xi0, X, Sigma; same flat layouts, eqvio_types.h).
+ * The sensor-level work (the 46 doubles of xi0 / X, the terms of A and B, the observer steps' sensor part, the sensor lift) is done on the host, the
+ * rest by the slot's workgroup. Only the accurate / discrete Riccati modes and the Normal chart are not available (EQF_E_UNSUPPORTED at creation).
+ *
+ * Return codes are eqf_hip.h's. Argument and settings checks come BEFORE the device is looked at: a call with bad arguments returns EQF_E_BAD_ARG /
+ * EQF_E_UNSUPPORTED on a machine without a GPU as well; with valid arguments and no gfx950 device, eqf_batch_create returns EQF_E_NO_DEVICE.
+ * A batch is bound to one device and one stream and must be used from one thread at a time.
+ */
+#ifndef EQF_BATCH_H
+#define EQF_BATCH_H
+#include "eqf_hip.h"
+#include "eqvio_types.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define EQF_BATCH_MAX_LANDMARKS 64
+
+typedef struct eqf_batch eqf_batch;
+
+/* One slot's frame for eqf_batch_step. The measurement's ids are strictly ascending (the order of the reference's std::map). */
+typedef struct eqf_batch_frame {
+    int slot;
+    eqvio_camera cam;
+    const double* imu13_mean; /* the mean IMU sample of the Riccati step (VIOFilter.cpp:141-156) */
+    double dt_total;
+    int k;                    /* observer steps */
+    const double* imu13_k;    /* k samples of 13 doubles */
+    const double* dt_k;       /* their dts */
+    int M;                    /* features */
+    const int* ids;
+    const double* y;          /* 2 M pixel coordinates */
+} eqf_batch_frame;
+
+/* Per-slot outcome of the last step (eqf_batch_last_result): which of removeOldLandmarks .. removeInvalidLandmarks happened */
+enum {
+    EQF_BATCH_REMOVED_OLD = 1,
+    EQF_BATCH_REMOVED_OUTLIERS = 2,
+    EQF_BATCH_ADDED = 4,
+    EQF_BATCH_EMPTY = 8, /* the matched measurement was empty: no update (the reference's early return) */
+    EQF_BATCH_UPDATED = 16,
+    EQF_BATCH_REMOVED_INVALID = 32
+};
+
+/* slots >= 1, 1 <= max_landmarks <= 64; settings: fastRiccati must be 1 and the chart Euclidean or InvDepth. The settings' gains, thresholds, depth and
+ * lift choices hold for every slot. Every slot starts with no landmark, Sigma = 0 and xi0 = X = identity (set them with eqf_batch_set_state / _set_sigma). */
+int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, const eqvio_settings* s);
+void eqf_batch_destroy(eqf_batch* b);
+int eqf_batch_slots(const eqf_batch* b);
+int eqf_batch_max_landmarks(const eqf_batch* b);
+
+/* The slot's xi0 / X / landmarks (eqf_set_state's layout: ids, q0 3 and Q 5 doubles per landmark). N <= max_landmarks. Sigma is NOT changed by set_state:
+ * set it afterwards with eqf_batch_set_sigma (n = 21 + 3 N). get_state returns N or < 0. */
+int eqf_batch_set_state(eqf_batch* b, int slot, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N);
+int eqf_batch_get_state(eqf_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap);
+int eqf_batch_set_sigma(eqf_batch* b, int slot, const double* sigma_colmajor, int n);
+int eqf_batch_get_sigma(eqf_batch* b, int slot, double* sigma_colmajor, int n);
+int eqf_batch_num_landmarks(const eqf_batch* b, int slot);
+/* stateGroupAction(X, xi0): the 23 sensor doubles, ids and landmark points (3 per landmark). Returns N or < 0. */
+int eqf_batch_state_estimate(eqf_batch* b, int slot, double* sensor, int* ids, double* p, int cap);
+
+/* Advances the `count` listed slots (distinct) by one frame each: one packet to the device, one launch, one copy back, one synchronisation.
+ * A slot that is not listed is not touched, bit for bit. status[e] (count entries) is the result of entry e:
+ *   0                  done;
+ *   EQF_E_BAD_ARG      bad slot index, repeated slot, ids not strictly ascending, bad camera: nothing of that slot was touched;
+ *   EQF_E_CAPACITY     the frame would take the slot past max_landmarks (landmarks that stay + new ids), or its measurement has more than max_landmarks
+ *                      features: refused before the launch, the slot is untouched;
+ *   EQF_E_NOT_SPD      a pivot of the Cholesky factorisation of S = C Sigma C^T + R was <= 0;
+ *   EQF_E_NONFINITE    Gamma was not finite. After these two the slot holds the frame's propagation and landmark bookkeeping (removeOldLandmarks,
+ *                      removeOutliers, addNewLandmarks) without the vision update; the other slots are not affected.
+ * The call itself returns 0 when the step ran (whatever the per-slot codes), EQF_E_BAD_ARG for null arguments, or a HIP error. */
+int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status);
+/* flags (EQF_BATCH_*) of the slot's last step, and the depth its new landmarks got */
+int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth);
+/* the hipStream_t the batch launches on, as void* */
+void* eqf_batch_stream(eqf_batch* b);
+int eqf_batch_synchronize(eqf_batch* b);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,56 @@
+/* eqvio_batch.h — C-ABI of the filter-level batch (eqvio_amd/host/VIOFilterBatch.hpp): B reference VIOFilters (fast Riccati, <= 64 landmarks each) whose
+ * frames go to the device together, one kernel launch per step (include/eqf_batch.h). Each slot keeps what the reference's VIOFilter keeps on the host:
+ * its IMU buffer, current time, initialised flag and landmark ids.
+ *
+ * Return values: 0 / a count on success, -1 when the C++ layer threw (message via eqvio_batch_last_error), an EQF_E_* code for refused arguments
+ * (eqvio_batch_create checks them before it looks for a device, see eqf_batch_create).
+ */
+#ifndef EQVIO_BATCH_H
+#define EQVIO_BATCH_H
+#include "eqf_batch.h"
+#include "eqvio_filter.h"
+#include "eqvio_types.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct eqvio_batch eqvio_batch;
+
+/* every slot as VIOFilter(const Settings&) (src/VIOFilter.cpp:31-41): it initialises itself from its first IMU sample */
+int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* settings, int device, int slots, int max_landmarks);
+/* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56) */
+int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time);
+void eqvio_batch_destroy(eqvio_batch* b);
+const char* eqvio_batch_last_error(const eqvio_batch* b);
+int eqvio_batch_slots(const eqvio_batch* b);
+
+/* processIMUData (VIOFilter.cpp:58-63) of one slot */
+int eqvio_batch_process_imu(eqvio_batch* b, int slot, const double* imu13);
+/* processVisionData (VIOFilter.cpp:194-241) of `count` distinct slots in ONE device step. Entry e: slot slots[e], stamp stamps[e], camera cams[e],
+ * meas_counts[e] features (ids ascending) taken in order from ids_all / y_all. A slot whose frame the reference would skip (stale stamp, no IMU yet, not
+ * initialised) sits the step out with status 0. status[e]: 0 or the slot's EQF_E_* code (include/eqf_batch.h). Returns 0 or -1. */
+int eqvio_batch_process_vision(eqvio_batch* b, int count, const int* slots, const double* stamps, const eqvio_camera* cams, const int* meas_counts, const int* ids_all,
+                               const double* y_all, int* status);
+
+/* Lockstep replay of prepared sequences (eqvio_frames_create, include/eqvio_filter.h): per_slot[k] is slot k's sequence or NULL. For j in [first, first + count)
+ * frame j of every slot that has one - its IMU samples, then its measurement - goes in one device step; a slot whose sequence has ended sits out. Returns the
+ * number of steps run, or -1 (a slot's frame was refused or failed: message via eqvio_batch_last_error). */
+int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count);
+
+/* per slot: stateEstimate, viewEqFState (xi0, X, Sigma), getTime, isInitialised, and the forcing of a whole EqF state (teacher forcing) */
+int eqvio_batch_state_estimate(eqvio_batch* b, int slot, double* sensor, int* ids, double* p, int cap); /* returns N or < 0 */
+int eqvio_batch_get_eqf(eqvio_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap);
+int eqvio_batch_force_eqf(eqvio_batch* b, int slot, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N,
+                          const double* sigma_colmajor);
+int eqvio_batch_sigma_dim(const eqvio_batch* b, int slot);
+int eqvio_batch_get_sigma(eqvio_batch* b, int slot, double* out_colmajor, int n);
+double eqvio_batch_get_time(const eqvio_batch* b, int slot);
+int eqvio_batch_is_initialised(const eqvio_batch* b, int slot);
+/* the device batch behind it */
+eqf_batch* eqvio_batch_core(eqvio_batch* b);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
