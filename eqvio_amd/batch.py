@@ -21,6 +21,18 @@ class BatchFrame(C.Structure):
                 ("dt_k", c_double_p), ("M", C.c_int), ("ids", c_int_p), ("y", c_double_p)]
 
 
+class BatchTruth(C.Structure):
+    """eqf_batch_truth (include/eqf_batch.h)."""
+
+    _fields_ = [("slot", C.c_int), ("sensor", c_double_p), ("n_true", C.c_int), ("ids", c_int_p), ("p", c_double_p)]
+
+
+class BatchAugmentEntry(C.Structure):
+    """eqf_batch_augment_entry (include/eqf_batch.h)."""
+
+    _fields_ = [("slot", C.c_int), ("n_new", C.c_int), ("new_ids", c_int_p), ("n_prov", C.c_int), ("prov_ids", c_int_p), ("prov_p", c_double_p)]
+
+
 def load_batch_protos():
     """Declare the prototypes of include/eqf_batch.h on libeqf_hip.so and of include/eqvio_batch.h on libeqvio_filter.so."""
     elib, flib = load_eqf_lib(), load_filter_lib()
@@ -42,6 +54,9 @@ def load_batch_protos():
         "eqf_batch_last_result": (C.c_int, [vp, C.c_int, c_int_p, c_double_p]),
         "eqf_batch_stream": (vp, [vp]),
         "eqf_batch_synchronize": (C.c_int, [vp]),
+        "eqf_batch_nees": (C.c_int, [vp, C.c_int, P(BatchTruth), c_double_p, c_int_p]),
+        "eqf_batch_nees_lu_fallbacks": (C.c_int, [vp, C.c_int, P(C.c_long)]),
+        "eqf_batch_augment": (C.c_int, [vp, C.c_int, P(BatchAugmentEntry), c_int_p]),
     }
     fprotos = {
         "eqvio_batch_create": (C.c_int, [P(vp), P(Settings), C.c_int, C.c_int, C.c_int]),
@@ -60,6 +75,9 @@ def load_batch_protos():
         "eqvio_batch_get_time": (C.c_double, [vp, C.c_int]),
         "eqvio_batch_is_initialised": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_core": (vp, [vp]),
+        "eqvio_batch_compute_nees": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
+        "eqvio_batch_augment_landmark_states": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p]),
+        "eqvio_batch_run_sim": (C.c_int, [vp, P(vp), C.c_int, c_double_p, c_int_p]),
     }
     for lib, protos in ((elib, eprotos), (flib, fprotos)):
         for name, (res, args) in protos.items():
@@ -156,6 +174,50 @@ class VIOFilterBatch:
             self._chk(rc)
         return rc
 
+    def compute_nees(self, entries):
+        """entries: list of (slot, true_sensor[23], true_ids, true_p[n, 3]). viewEqFState().computeNEES of every listed slot in ONE launch; returns the NEES
+        values and the per-entry status codes (eqf_batch_nees; NaN where the status is not 0)."""
+        n = len(entries)
+        slots = _i32([e[0] for e in entries])
+        sensors = _f64(np.concatenate([np.asarray(e[1], np.float64).ravel() for e in entries]) if n else np.zeros(0))
+        counts = _i32([len(e[2]) for e in entries])
+        ids = _i32(np.concatenate([np.asarray(e[2], np.int32) for e in entries]) if n else np.zeros(0, np.int32))
+        p = _f64(np.concatenate([np.asarray(e[3], np.float64).ravel() for e in entries]) if n else np.zeros(0))
+        nees, status = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_compute_nees(self.h, n, _ip(slots), _dp(sensors), _ip(counts), _ip(ids), _dp(p), _dp(nees), _ip(status)))
+        return nees[:n].copy(), status[:n].copy()
+
+    def augment_landmark_states(self, entries):
+        """entries: list of (slot, new_ids, provided_ids, provided_p[n, 3]). augmentLandmarkStates of every listed slot in ONE launch; returns the per-entry
+        status codes (eqf_batch_augment)."""
+        n = len(entries)
+        slots = _i32([e[0] for e in entries])
+        new_counts = _i32([len(e[1]) for e in entries])
+        new_ids = _i32(np.concatenate([np.asarray(e[1], np.int32) for e in entries]) if n else np.zeros(0, np.int32))
+        prov_counts = _i32([len(e[2]) for e in entries])
+        prov_ids = _i32(np.concatenate([np.asarray(e[2], np.int32) for e in entries]) if n else np.zeros(0, np.int32))
+        prov_p = _f64(np.concatenate([np.asarray(e[3], np.float64).ravel() for e in entries]) if n else np.zeros(0))
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_augment_landmark_states(self.h, n, _ip(slots), _ip(new_counts), _ip(new_ids), _ip(prov_counts), _ip(prov_ids), _dp(prov_p),
+                                                               _ip(status)))
+        return status[:n].copy()
+
+    def run_sim(self, sims, max_frames):
+        """The reference's main_sim loop over the slots in lockstep (eqvio_batch_run_sim): sims[k] is slot k's capi.SimulationDataServer (or None). Returns the
+        NEES of every frame and slot, shape (frames run, slots), NaN where a slot had no frame."""
+        if len(sims) > self.slots:
+            raise ValueError("more simulations than slots")
+        arr = (C.c_void_p * self.slots)(*([s.h if s is not None else None for s in sims] + [None] * (self.slots - len(sims))))
+        nees = np.zeros(max(max_frames, 1) * self.slots)
+        done = C.c_int()
+        self._chk(self.lib.eqvio_batch_run_sim(self.h, arr, max_frames, _dp(nees), C.byref(done)))
+        return nees[: done.value * self.slots].reshape(done.value, self.slots).copy()
+
+    def nees_lu_fallbacks(self, k):
+        out = C.c_long()
+        self._chk(self.elib.eqf_batch_nees_lu_fallbacks(self.core_handle(), k, C.byref(out)))
+        return out.value
+
     def synchronize(self):
         self._chk(self.elib.eqf_batch_synchronize(self.core_handle()))
 
@@ -185,6 +247,18 @@ class BatchSlot:
 
     def process_vision(self, stamp, cam, ids, y):
         st = self.b.process_vision([(self.k, stamp, cam, ids, y)])
+        if st[0] != 0:
+            raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
+
+    def compute_nees(self, sensor, ids, p):
+        nees, st = self.b.compute_nees([(self.k, sensor, ids, p)])
+        if st[0] != 0:
+            raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
+        return float(nees[0])
+
+    def augment_landmark_states(self, new_ids, sensor, ids, p):
+        """capi.VIOFilter's signature; the provided state's sensor part is not used (nor is it by the reference)."""
+        st = self.b.augment_landmark_states([(self.k, new_ids, ids, p)])
         if st[0] != 0:
             raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
 

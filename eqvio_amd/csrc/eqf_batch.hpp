@@ -581,4 +581,284 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     }
 }
 
+// ===================================================================================================
+// eqf_batch_nees and eqf_batch_augment (include/eqf_batch.h): one workgroup per entry, each touching its own slot only.
+// The scratch area holds nothing live between launches: k_batch_frame writes every scratch word before it reads it in the same launch (G in phase 1, the
+// statistics rows in phase 2, T / W and L in phase 4, the lift estimates over the statistics rows), so k_batch_nees may use it freely. k_batch_nees writes
+// nothing else; k_batch_augment writes the slot's other buffer pair, which the host then names current.
+
+// computeNEES (VIO_eqf.cpp:153-170): eps = stateChart(stateError); NEES = eps^T Sigma^-1 eps / n. The host gives the 21 sensor entries and the true point of
+// every state landmark in state order; the landmark entries (pe = a R p, point_chart against q0) are computed here.
+struct NeesIn {
+    int slot, cur, N;
+    double eps[21];
+    double p[3 * BATCH_L];
+};
+struct NeesOut {
+    double sumsq; // eps^T Sigma^-1 eps
+    int lu;       // 1: a pivot was <= 0 and the partial-pivot elimination gave the value
+};
+struct NeesArgs {
+    int chart, ld;
+    const double* sig;
+    const double* lm;
+    double* scr;
+    size_t sig_stride, lm_stride, scr_stride;
+    const NeesIn* in;
+    NeesOut* out;
+};
+constexpr int NEES_PW = 16;  // panel width
+constexpr int NEES_PLD = 228; // LDS panel column stride: rows k0 .. np (<= 215) and the zero rows of the last 16-row tile (< 224)
+constexpr int NEES_NP = BATCH_NMAX + 1;
+
+// sum over the workgroup; every thread gets it (s_red: BATCH_T / 64 doubles)
+__device__ __forceinline__ double nees_block_sum(double v, double* s_red) {
+    for (int o = 32; o > 0; o >>= 1)
+        v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0)
+        s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < BATCH_T / 64; ++w)
+        t += s_red[w];
+    __syncthreads();
+    return t;
+}
+
+// Z = [Sigma ; eps^T] in the slot's scratch area (np + 1 rows, leading dimension ld >= 216 > np + 1, np columns: ld * 214 <= batch_scr_doubles(ld)), Sigma padded
+// to the even dimension np with a unit diagonal entry as the context path's k_build_nees does. lower: only r >= c (the Cholesky reads no more).
+__device__ __forceinline__ void nees_build_z(int n, int np, int ld, const double* S, const double* eps, double* Z, bool lower) {
+    for (int t = threadIdx.x; t < (np + 1) * np; t += BATCH_T) {
+        const int r = t % (np + 1), c = t / (np + 1);
+        if (lower && r < c)
+            continue;
+        Z[r + (size_t)c * ld] = r == np ? eps[c] : (r < n && c < n ? S[r + (size_t)c * ld] : (r == c ? 1.0 : 0.0));
+    }
+}
+
+// Blocked right-looking Cholesky of Z = [Sigma ; eps^T] with the eps row carried along as an extra row: after the factorisation that row holds z = L^-1 eps,
+// and |z|^2 = eps^T Sigma^-1 eps. Per 16-column panel: rows k0 .. np of the panel into LDS, the panel factored on the VALU (one lane per row), the eps row's
+// entries summed, and the trailing lower triangle (the eps row included) updated by Z -= L21 L21^T in 16 x 16 tiles on the matrix cores (mfma16_nt, one wave
+// per tile, operands from LDS). A pivot <= 0 (or not finite) sends the slot to partial-pivot Gaussian elimination on [Sigma | eps], in the same workgroup: what
+// k_ge_step / k_ge_back do over np launches in the context path, so a number comes back whenever the reference's Sigma.inverse() gives one.
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) {
+    __shared__ double P[NEES_PLD * NEES_PW]; // the panel; x of the back substitution in the fallback
+    __shared__ double s_eps[NEES_NP + 1];
+    __shared__ double s_red[BATCH_T];
+    __shared__ int s_idx[BATCH_T];
+    __shared__ int s_perm[NEES_NP];
+    const NeesIn& in = na.in[blockIdx.x];
+    const int tid = threadIdx.x, L = BATCH_L, ld = na.ld;
+    const int N = in.N, n = 21 + 3 * N, np = n + (n & 1);
+    const double* S = na.sig + (2 * (size_t)in.slot + in.cur) * na.sig_stride;
+    const double* lm = na.lm + (2 * (size_t)in.slot + in.cur) * na.lm_stride;
+    double* Z = na.scr + (size_t)in.slot * na.scr_stride;
+
+    for (int r = tid; r < np; r += BATCH_T)
+        if (r < 21 || r >= n)
+            s_eps[r] = r < 21 ? in.eps[r] : 0.0;
+    if (tid < N) {
+        const int i = tid;
+        const V3 pe = lm[BATCH_QA * L + i] * q_rot(ldq(lm + BATCH_QQ * L, L, i), V3{in.p[3 * i], in.p[3 * i + 1], in.p[3 * i + 2]}); // (Q_i^-1)^-1 p = a R p
+        const V3 e = point_chart(na.chart == EQVIO_COORD_INVDEPTH, pe, ld3(lm, L, i));
+        s_eps[21 + 3 * i] = e.x;
+        s_eps[22 + 3 * i] = e.y;
+        s_eps[23 + 3 * i] = e.z;
+    }
+    __syncthreads();
+    nees_build_z(n, np, ld, S, s_eps, Z, true);
+    __syncthreads();
+
+    double acc = 0.0; // |z|^2, kept by thread 0
+    bool fail = false;
+    for (int k0 = 0; k0 < np && !fail; k0 += NEES_PW) {
+        const int w = min(NEES_PW, np - k0), R = np + 1 - k0; // panel columns, rows (the last one is the eps row)
+        for (int t = tid; t < NEES_PLD * NEES_PW; t += BATCH_T) {
+            const int r = t % NEES_PLD, c = t / NEES_PLD;
+            P[t] = (r < R && c < w && r >= c) ? Z[k0 + r + (size_t)(k0 + c) * ld] : 0.0;
+        }
+        __syncthreads();
+        for (int j = 0; j < w; ++j) {
+            const double d = P[j + j * NEES_PLD]; // the same value in every lane: the exit is uniform
+            if (!(d > 0.0) || !(d - d == 0.0)) {
+                fail = true;
+                break;
+            }
+            const double ljj = sqrt(d);
+            for (int r = j + 1 + tid; r < R; r += BATCH_T)
+                P[r + j * NEES_PLD] /= ljj;
+            __syncthreads();
+            for (int r = j + 1 + tid; r < R; r += BATCH_T) {
+                const double lrj = P[r + j * NEES_PLD];
+                for (int c = j + 1; c < w && c <= r; ++c)
+                    P[r + c * NEES_PLD] -= lrj * P[c + j * NEES_PLD];
+            }
+            if (tid == 0)
+                P[j + j * NEES_PLD] = ljj;
+            __syncthreads();
+        }
+        if (fail)
+            break;
+        if (tid == 0)
+            for (int c = 0; c < w; ++c)
+                acc += P[(R - 1) + c * NEES_PLD] * P[(R - 1) + c * NEES_PLD];
+        const int t0 = k0 + NEES_PW; // first trailing row and column
+        if (t0 < np) {               // then w == 16: the product's K is the whole panel
+            const int ntr = (np + 1 - t0 + 15) / 16, ntc = (np - t0 + 15) / 16, tri = ntc * (ntc + 1) / 2;
+            const int ntiles = tri + (ntr > ntc ? ntc : 0);
+            const int wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
+            for (int t = wave; t < ntiles; t += BATCH_T / 64) {
+                int bi, bj;
+                if (t < tri) {
+                    bi = 0;
+                    while ((bi + 1) * (bi + 2) / 2 <= t)
+                        ++bi;
+                    bj = t - bi * (bi + 1) / 2;
+                } else {
+                    bi = ntc;
+                    bj = t - tri;
+                }
+                const d4 a = mfma16_nt(P + NEES_PW + 16 * bi, NEES_PLD, P + NEES_PW + 16 * bj, NEES_PLD);
+                const int r = t0 + 16 * bi + lr;
+                for (int q = 0; q < 4; ++q) {
+                    const int c = t0 + 16 * bj + lk + 4 * q;
+                    if (r <= np && c < np && r >= c)
+                        Z[r + (size_t)c * ld] -= a[q];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!fail) {
+        if (tid == 0) {
+            na.out[blockIdx.x].sumsq = acc;
+            na.out[blockIdx.x].lu = 0;
+        }
+        return;
+    }
+
+    // fallback: [Sigma | eps] read as rows M[i][j] = Z[j + i ld] (Sigma is symmetric; j = np is the right-hand side). Rows are never moved: s_perm maps
+    // logical to physical rows. The pivot is the first row of largest |M[i][k]| (k_ge_step's rule).
+    __syncthreads();
+    nees_build_z(n, np, ld, S, s_eps, Z, false);
+    for (int i = tid; i < np; i += BATCH_T)
+        s_perm[i] = i;
+    __syncthreads();
+    for (int k = 0; k < np; ++k) {
+        double best = -1.0;
+        int bi = k;
+        for (int i = k + tid; i < np; i += BATCH_T) {
+            const double v = fabs(Z[k + (size_t)s_perm[i] * ld]);
+            if (v > best) {
+                best = v;
+                bi = i;
+            }
+        }
+        s_red[tid] = best;
+        s_idx[tid] = bi;
+        __syncthreads();
+        for (int st = BATCH_T / 2; st > 0; st >>= 1) {
+            if (tid < st) {
+                const double o = s_red[tid + st];
+                const int oi = s_idx[tid + st];
+                if (o > s_red[tid] || (o == s_red[tid] && oi < s_idx[tid])) {
+                    s_red[tid] = o;
+                    s_idx[tid] = oi;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const int p = s_idx[0], t = s_perm[k];
+            s_perm[k] = s_perm[p];
+            s_perm[p] = t;
+        }
+        __syncthreads();
+        const double* prow = Z + (size_t)s_perm[k] * ld;
+        const double piv = prow[k];
+        const int w = np - k; // columns k + 1 .. np
+        for (int t = tid; t < (np - k - 1) * w; t += BATCH_T) {
+            double* row = Z + (size_t)s_perm[k + 1 + t / w] * ld;
+            const int j = k + 1 + t % w;
+            const double l = row[k] / piv;
+            row[j] -= l * prow[j];
+        }
+        __syncthreads();
+    }
+    // back substitution U x = b (x in P), then eps . x
+    double* x = P;
+    for (int k = np - 1; k >= 0; --k) {
+        const double* row = Z + (size_t)s_perm[k] * ld;
+        double s = 0.0;
+        for (int j = k + 1 + tid; j < np; j += BATCH_T)
+            s += row[j] * x[j];
+        s = nees_block_sum(s, s_red);
+        if (tid == 0)
+            x[k] = (row[np] - s) / row[k];
+        __syncthreads();
+    }
+    double s = 0.0;
+    for (int j = tid; j < n; j += BATCH_T)
+        s += s_eps[j] * x[j];
+    s = nees_block_sum(s, s_red);
+    if (tid == 0) {
+        na.out[blockIdx.x].sumsq = s;
+        na.out[blockIdx.x].lu = 1;
+    }
+}
+
+// augmentLandmarkStates (VIOFilter.cpp:112-132): removeOldLandmarks' compaction and addNewLandmarks (VIO_eqf.cpp:225-245), the two halves of k_batch_frame's
+// phase 3 (kept landmarks by index; new ones with q0 = the provided point, its chart constants, Q = identity; Sigma with zero cross terms and
+// initialPointVariance I), written into the slot's other buffer pair.
+struct AugIn {
+    int slot, cur, Nk, nnew; // landmarks kept, appended
+    int keep[BATCH_L];       // state index of kept landmark i
+    double p[3 * BATCH_L];   // provided point of the r-th appended landmark
+};
+struct AugArgs {
+    int ld;
+    double init_var;
+    double* sig;
+    double* lm;
+    size_t sig_stride, lm_stride;
+    const AugIn* in;
+};
+__global__ void __launch_bounds__(BATCH_T) k_batch_augment(const AugArgs aa) {
+    __shared__ int s_gidx[BATCH_NMAX];
+    const AugIn& in = aa.in[blockIdx.x];
+    const int tid = threadIdx.x, L = BATCH_L, ld = aa.ld;
+    const int nk = in.Nk, N2 = nk + in.nnew, n2 = 21 + 3 * N2, cur = in.cur, nxt = cur ^ 1;
+    const double* S0 = aa.sig + (2 * (size_t)in.slot + cur) * aa.sig_stride;
+    double* S1 = aa.sig + (2 * (size_t)in.slot + nxt) * aa.sig_stride;
+    const double* L0 = aa.lm + (2 * (size_t)in.slot + cur) * aa.lm_stride;
+    double* L1 = aa.lm + (2 * (size_t)in.slot + nxt) * aa.lm_stride;
+    for (int r = tid; r < n2; r += BATCH_T)
+        s_gidx[r] = r < 21 ? r : ((r - 21) / 3 < nk ? 21 + 3 * in.keep[(r - 21) / 3] + (r - 21) % 3 : -1);
+    __syncthreads();
+    for (int t = tid; t < n2 * n2; t += BATCH_T) {
+        const int r = t % n2, c = t / n2;
+        const int gr = s_gidx[r], gc = s_gidx[c];
+        S1[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S0[gr + (size_t)gc * ld] : (r == c ? aa.init_var : 0.0);
+    }
+    if (tid < N2) {
+        const int i = tid;
+        if (i < nk) {
+            for (int pl = 0; pl < BATCH_PLANES; ++pl)
+                L1[pl * L + i] = L0[pl * L + in.keep[i]];
+        } else {
+            const int r = i - nk;
+            const double px = in.p[3 * r], py = in.p[3 * r + 1], pz = in.p[3 * r + 2];
+            L1[i] = px;
+            L1[L + i] = py;
+            L1[2 * L + i] = pz;
+            store_chart_constants(L1 + (size_t)CC_OFF * L, L, i, px, py, pz, nullptr);
+            L1[BATCH_QQ * L + i] = 1.0;
+            L1[(BATCH_QQ + 1) * L + i] = 0.0;
+            L1[(BATCH_QQ + 2) * L + i] = 0.0;
+            L1[(BATCH_QQ + 3) * L + i] = 0.0;
+            L1[BATCH_QA * L + i] = 1.0;
+        }
+    }
+}
+
 } // namespace eqf

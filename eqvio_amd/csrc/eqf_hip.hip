@@ -738,6 +738,34 @@ int index_of(eqf_ctx* c, int id) {
     return (it != c->lookup.end() && it->first == id) ? it->second : -1;
 }
 
+// computeNEES's sensor entries eps[0, 21) (eqf_compute_nees, eqf_batch_nees): stateError = stateGroupAction(X^-1, truncated true state) (VIOGroup.cpp:25-55,
+// 108-120), then sensorChart_std (VIOState.cpp:104-113) or, for the Normal chart, sensorChart_normal (:123-137)
+void nees_sensor_error(const SensorState& xi0, const GroupSensor& X, int chart, const double* ts, double* eps) {
+    const SensorState tsn = unpack_sensor(ts);
+    GroupSensor Xi;
+    Xi.bgyr = -X.bgyr;
+    Xi.bacc = -X.bacc;
+    Xi.A = pose_inv(X.A);
+    Xi.B = pose_inv(X.B);
+    Xi.w = -q_rot(q_inv(X.A.R), X.w);
+    const SensorState se = sensor_action(Xi, tsn);
+    const V3 db = se.bgyr - xi0.bgyr, da = se.bacc - xi0.bacc;
+    V3 dv = se.vel - xi0.vel;
+    V3 om, tr, omc, trc;
+    const Pose Arel = pose_mul(pose_inv(xi0.pose), se.pose);
+    se3_log(Arel, om, tr);
+    if (chart == EQVIO_COORD_NORMAL) {
+        // SE_2(3).log(A.R, A.x, v_A), v_A = R0^T (R v - R0 v0); B = T0^-1 A T
+        const V3 vA = q_rot(q_inv(xi0.pose.R), q_rot(se.pose.R, se.vel) - q_rot(xi0.pose.R, xi0.vel));
+        dv = so3_Vinv(om) * vA;
+        se3_log(pose_mul(pose_mul(pose_inv(xi0.cam), Arel), se.cam), omc, trc);
+    } else
+        se3_log(pose_mul(pose_inv(xi0.cam), se.cam), omc, trc);
+    const V3 parts[7] = {db, da, om, tr, dv, omc, trc};
+    for (int b = 0; b < 7; ++b)
+        pack_v3(parts[b], eps + 3 * b);
+}
+
 } // namespace
 
 extern "C" {
@@ -3595,32 +3623,8 @@ int eqf_compute_nees(eqf_ctx* c, const double* ts, const int* tids, const double
     int rc = eqf_get_state(c, s0, g0, ids.data(), q0.data(), Q.data(), N);
     if (rc < 0)
         return rc;
-    // stateError = stateGroupAction(X^-1, truncated true state) (VIOGroup.cpp:25-55, 108-120)
-    const SensorState tsn = unpack_sensor(ts);
-    GroupSensor Xi;
-    Xi.bgyr = -c->X.bgyr;
-    Xi.bacc = -c->X.bacc;
-    Xi.A = pose_inv(c->X.A);
-    Xi.B = pose_inv(c->X.B);
-    Xi.w = -q_rot(q_inv(c->X.A.R), c->X.w);
-    const SensorState se = sensor_action(Xi, tsn);
     std::vector<double> eps(np, 0.0);
-    // sensorChart_std (VIOState.cpp:104-113); Normal chart: sensorChart_normal (:123-137)
-    const V3 db = se.bgyr - c->xi0.bgyr, da = se.bacc - c->xi0.bacc;
-    V3 dv = se.vel - c->xi0.vel;
-    V3 om, tr, omc, trc;
-    const Pose Arel = pose_mul(pose_inv(c->xi0.pose), se.pose);
-    se3_log(Arel, om, tr);
-    if (c->chart == EQVIO_COORD_NORMAL) {
-        // SE_2(3).log(A.R, A.x, v_A), v_A = R0^T (R v - R0 v0); B = T0^-1 A T
-        const V3 vA = q_rot(q_inv(c->xi0.pose.R), q_rot(se.pose.R, se.vel) - q_rot(c->xi0.pose.R, c->xi0.vel));
-        dv = so3_Vinv(om) * vA;
-        se3_log(pose_mul(pose_mul(pose_inv(c->xi0.cam), Arel), se.cam), omc, trc);
-    } else
-        se3_log(pose_mul(pose_inv(c->xi0.cam), se.cam), omc, trc);
-    const V3 parts[7] = {db, da, om, tr, dv, omc, trc};
-    for (int b = 0; b < 7; ++b)
-        pack_v3(parts[b], eps.data() + 3 * b);
+    nees_sensor_error(c->xi0, c->X, c->chart, ts, eps.data());
     for (int i = 0; i < N; ++i) {
         int jt = -1;
         for (int t = 0; t < ntrue; ++t)
@@ -4018,6 +4022,7 @@ struct eqf_batch {
         int cur = 0;
         int flags = 0;
         double depth = 0.0;
+        long nees_lu = 0; // eqf_batch_nees entries answered by the partial-pivot fallback
     };
     int device = 0, slots = 0, cap = 0, ld = 0, chart = 0;
     eqvio_settings set{};
@@ -4029,6 +4034,10 @@ struct eqf_batch {
     BatchOut *h_out = nullptr, *d_out = nullptr;
     ObsStep *h_steps = nullptr, *d_steps = nullptr;
     int in_cap = 0, steps_cap = 0;
+    NeesIn *h_nin = nullptr, *d_nin = nullptr; // eqf_batch_nees packets
+    NeesOut *h_nout = nullptr, *d_nout = nullptr;
+    AugIn *h_ain = nullptr, *d_ain = nullptr; // eqf_batch_augment packets
+    int nin_cap = 0, nout_cap = 0, aug_cap = 0;
     std::vector<Slot> s;
 };
 
@@ -4179,6 +4188,15 @@ void eqf_batch_destroy(eqf_batch* b) {
         (void)hipHostFree(b->h_out);
     if (b->h_steps)
         (void)hipHostFree(b->h_steps);
+    (void)hipFree(b->d_nin);
+    (void)hipFree(b->d_nout);
+    (void)hipFree(b->d_ain);
+    if (b->h_nin)
+        (void)hipHostFree(b->h_nin);
+    if (b->h_nout)
+        (void)hipHostFree(b->h_nout);
+    if (b->h_ain)
+        (void)hipHostFree(b->h_ain);
     if (b->stream)
         (void)hipStreamDestroy(b->stream);
     delete b;
@@ -4461,6 +4479,196 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         sl.depth = o.depth;
         if ((int)sl.ids.size() != o.N)
             status[e] = EQF_E_BAD_ARG; // bookkeeping disagreement: cannot happen
+    }
+    return 0;
+}
+
+namespace {
+// a pinned host packet and its device copy, grown to n entries
+template <typename T> int batch_grow_pair(T*& h, T*& d, int& cap, int n) {
+    if (n <= cap)
+        return 0;
+    if (h)
+        HIPCHK(hipHostFree(h));
+    if (d)
+        HIPCHK(hipFree(d));
+    h = nullptr, d = nullptr, cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h, sizeof(T) * n, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&d, sizeof(T) * n));
+    cap = n;
+    return 0;
+}
+} // namespace
+
+int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, double* nees, int* status) {
+    if (!b || count < 0 || (count > 0 && (!truths || !nees || !status)))
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = batch_grow_pair(b->h_nin, b->d_nin, b->nin_cap, count))
+        return rc;
+    if (int rc = batch_grow_pair(b->h_nout, b->d_nout, b->nout_cap, count))
+        return rc;
+    // host half: the sensor entries of eps (eqf_compute_nees's code), the true points in state order
+    std::vector<int> listed(b->slots, 0), in_of(count, -1), jt;
+    std::vector<std::pair<int, int>> order;
+    int nin = 0;
+    for (int e = 0; e < count; ++e) {
+        const eqf_batch_truth& t = truths[e];
+        status[e] = 0;
+        nees[e] = std::nan("");
+        if (!batch_slot_ok(b, t.slot) || listed[t.slot] || !t.sensor || t.n_true < 0 || (t.n_true > 0 && (!t.ids || !t.p))) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        listed[t.slot] = 1;
+        const eqf_batch::Slot& sl = b->s[t.slot];
+        const int N = (int)sl.ids.size();
+        order.resize(N);
+        for (int i = 0; i < N; ++i)
+            order[i] = {sl.ids[i], i};
+        std::sort(order.begin(), order.end());
+        jt.assign(N, -1);
+        for (int k = 0; k < t.n_true; ++k) { // the first true landmark of an id, as eqf_compute_nees
+            const auto it = std::lower_bound(order.begin(), order.end(), std::make_pair(t.ids[k], -1));
+            if (it != order.end() && it->first == t.ids[k] && jt[it->second] < 0)
+                jt[it->second] = k;
+        }
+        if (std::find(jt.begin(), jt.end(), -1) != jt.end()) {
+            status[e] = EQF_E_BAD_ARG; // the reference asserts the true state holds every filter landmark
+            continue;
+        }
+        NeesIn& in = b->h_nin[nin];
+        in.slot = t.slot;
+        in.cur = sl.cur;
+        in.N = N;
+        nees_sensor_error(sl.xi0, sl.X, b->chart, t.sensor, in.eps);
+        for (int i = 0; i < N; ++i)
+            for (int c = 0; c < 3; ++c)
+                in.p[3 * i + c] = t.p[3 * jt[i] + c];
+        in_of[e] = nin++;
+    }
+    if (nin == 0)
+        return 0;
+    NeesArgs na;
+    na.chart = b->chart;
+    na.ld = b->ld;
+    na.sig = b->d_sig;
+    na.lm = b->d_lm;
+    na.scr = b->d_scr;
+    na.sig_stride = b->sig_stride;
+    na.lm_stride = b->lm_stride;
+    na.scr_stride = b->scr_stride;
+    na.in = b->d_nin;
+    na.out = b->d_nout;
+    HIPCHK(hipMemcpyAsync(b->d_nin, b->h_nin, sizeof(NeesIn) * nin, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_nees, dim3(nin), dim3(BATCH_T), 0, b->stream, na);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_nout, b->d_nout, sizeof(NeesOut) * nin, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        const NeesOut& o = b->h_nout[in_of[e]];
+        eqf_batch::Slot& sl = b->s[truths[e].slot];
+        nees[e] = o.sumsq / (double)(21 + 3 * (int)sl.ids.size());
+        sl.nees_lu += o.lu;
+    }
+    return 0;
+}
+int eqf_batch_nees_lu_fallbacks(const eqf_batch* b, int slot, long* count) {
+    if (!batch_slot_ok(b, slot) || !count)
+        return EQF_E_BAD_ARG;
+    *count = b->s[slot].nees_lu;
+    return 0;
+}
+
+int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* entries, int* status) {
+    if (!b || count < 0 || (count > 0 && (!entries || !status)))
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = batch_grow_pair(b->h_ain, b->d_ain, b->aug_cap, count))
+        return rc;
+    std::vector<int> listed(b->slots, 0), in_of(count, -1);
+    std::vector<std::vector<int>> ids_after(count);
+    int nin = 0;
+    for (int e = 0; e < count; ++e) {
+        const eqf_batch_augment_entry& a = entries[e];
+        status[e] = 0;
+        if (!batch_slot_ok(b, a.slot) || listed[a.slot] || a.n_new < 0 || a.n_prov < 0 || (a.n_new > 0 && !a.new_ids) || (a.n_prov > 0 && (!a.prov_ids || !a.prov_p))) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        listed[a.slot] = 1;
+        const eqf_batch::Slot& sl = b->s[a.slot];
+        const int N0 = (int)sl.ids.size();
+        // removeOldLandmarks(newIds) (VIOFilter.cpp:280-302): the landmarks whose id is in newIds stay, in state order
+        std::vector<int> keep, ids;
+        for (int i = 0; i < N0; ++i)
+            if (std::find(a.new_ids, a.new_ids + a.n_new, sl.ids[i]) != a.new_ids + a.n_new) {
+                keep.push_back(i);
+                ids.push_back(sl.ids[i]);
+            }
+        const int nk = (int)keep.size();
+        // the ids of newIds not in the state, in newIds order, with the provided state's first landmark of that id (VIOFilter.cpp:118-127)
+        std::vector<int> from;
+        bool missing = false;
+        for (int j = 0; j < a.n_new && !missing; ++j) {
+            const int id = a.new_ids[j];
+            if (std::find(ids.begin(), ids.begin() + nk, id) != ids.begin() + nk)
+                continue;
+            const int* it = std::find(a.prov_ids, a.prov_ids + a.n_prov, id);
+            if (it == a.prov_ids + a.n_prov)
+                missing = true;
+            from.push_back((int)(it - a.prov_ids));
+            ids.push_back(id);
+        }
+        if (missing) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        if ((int)ids.size() > b->cap) {
+            status[e] = EQF_E_CAPACITY;
+            continue;
+        }
+        if (nk == N0 && from.empty())
+            continue; // nothing leaves, nothing comes: the slot stays as it is
+        AugIn& in = b->h_ain[nin];
+        in.slot = a.slot;
+        in.cur = sl.cur;
+        in.Nk = nk;
+        in.nnew = (int)from.size();
+        for (int i = 0; i < nk; ++i)
+            in.keep[i] = keep[i];
+        for (size_t r = 0; r < from.size(); ++r)
+            for (int c = 0; c < 3; ++c)
+                in.p[3 * r + c] = a.prov_p[3 * (size_t)from[r] + c];
+        ids_after[e].swap(ids);
+        in_of[e] = nin++;
+    }
+    if (nin == 0)
+        return 0;
+    AugArgs aa;
+    aa.ld = b->ld;
+    aa.init_var = b->set.initialPointVariance;
+    aa.sig = b->d_sig;
+    aa.lm = b->d_lm;
+    aa.sig_stride = b->sig_stride;
+    aa.lm_stride = b->lm_stride;
+    aa.in = b->d_ain;
+    HIPCHK(hipMemcpyAsync(b->d_ain, b->h_ain, sizeof(AugIn) * nin, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_augment, dim3(nin), dim3(BATCH_T), 0, b->stream, aa);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        eqf_batch::Slot& sl = b->s[entries[e].slot];
+        sl.ids.swap(ids_after[e]);
+        sl.cur ^= 1;
     }
     return 0;
 }

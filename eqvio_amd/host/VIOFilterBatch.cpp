@@ -3,6 +3,7 @@
 #include "eqvio_batch.h"
 #include "PreparedFrames.hpp"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <array>
 #include <stdexcept>
@@ -219,6 +220,15 @@ template <typename Fn> int guarded(eqvio_batch* b, Fn&& fn) {
     }
 }
 bool slot_ok(const eqvio_batch* b, int k) { return b && k >= 0 && k < b->f->slots(); }
+IMUVelocity imu_from13(const double* imu13) {
+    IMUVelocity r;
+    r.stamp = imu13[0];
+    r.gyr = eqf::V3{imu13[1], imu13[2], imu13[3]};
+    r.acc = eqf::V3{imu13[4], imu13[5], imu13[6]};
+    r.gyrBiasVel = eqf::V3{imu13[7], imu13[8], imu13[9]};
+    r.accBiasVel = eqf::V3{imu13[10], imu13[11], imu13[12]};
+    return r;
+}
 } // namespace
 
 int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* s, int device, int slots, int max_landmarks) {
@@ -258,15 +268,7 @@ int eqvio_batch_slots(const eqvio_batch* b) { return b ? b->f->slots() : EQF_E_B
 int eqvio_batch_process_imu(eqvio_batch* b, int slot, const double* imu13) {
     if (!slot_ok(b, slot) || !imu13)
         return EQF_E_BAD_ARG;
-    return guarded(b, [&] {
-        IMUVelocity r;
-        r.stamp = imu13[0];
-        r.gyr = eqf::V3{imu13[1], imu13[2], imu13[3]};
-        r.acc = eqf::V3{imu13[4], imu13[5], imu13[6]};
-        r.gyrBiasVel = eqf::V3{imu13[7], imu13[8], imu13[9]};
-        r.accBiasVel = eqf::V3{imu13[10], imu13[11], imu13[12]};
-        b->f->processIMUData(slot, r);
-    });
+    return guarded(b, [&] { b->f->processIMUData(slot, imu_from13(imu13)); });
 }
 int eqvio_batch_process_vision(eqvio_batch* b, int count, const int* slots, const double* stamps, const eqvio_camera* cams, const int* meas_counts, const int* ids_all,
                                const double* y_all, int* status) {
@@ -323,4 +325,167 @@ int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot
         }
     });
     return rc ? rc : steps;
+}
+
+int eqvio_batch_compute_nees(eqvio_batch* b, int count, const int* slots, const double* true_sensor_all, const int* true_counts, const int* true_ids_all,
+                             const double* true_p_all, double* nees, int* status) {
+    if (!b || count < 0 || (count > 0 && (!slots || !true_sensor_all || !true_counts || !nees || !status)))
+        return EQF_E_BAD_ARG;
+    std::vector<eqf_batch_truth> t(count);
+    size_t o = 0;
+    for (int e = 0; e < count; ++e) {
+        t[e].slot = slots[e];
+        t[e].sensor = true_sensor_all + 23 * (size_t)e;
+        t[e].n_true = true_counts[e];
+        t[e].ids = true_ids_all ? true_ids_all + o : nullptr;
+        t[e].p = true_p_all ? true_p_all + 3 * o : nullptr;
+        o += std::max(true_counts[e], 0);
+    }
+    return eqf_batch_nees(b->f->core(), count, t.data(), nees, status);
+}
+int eqvio_batch_augment_landmark_states(eqvio_batch* b, int count, const int* slots, const int* new_counts, const int* new_ids_all, const int* prov_counts,
+                                        const int* prov_ids_all, const double* prov_p_all, int* status) {
+    if (!b || count < 0 || (count > 0 && (!slots || !new_counts || !prov_counts || !status)))
+        return EQF_E_BAD_ARG;
+    std::vector<eqf_batch_augment_entry> a(count);
+    size_t on = 0, op = 0;
+    for (int e = 0; e < count; ++e) {
+        a[e].slot = slots[e];
+        a[e].n_new = new_counts[e];
+        a[e].new_ids = new_ids_all ? new_ids_all + on : nullptr;
+        a[e].n_prov = prov_counts[e];
+        a[e].prov_ids = prov_ids_all ? prov_ids_all + op : nullptr;
+        a[e].prov_p = prov_p_all ? prov_p_all + 3 * op : nullptr;
+        on += std::max(new_counts[e], 0);
+        op += std::max(prov_counts[e], 0);
+    }
+    return eqf_batch_augment(b->f->core(), count, a.data(), status);
+}
+
+int eqvio_batch_run_sim(eqvio_batch* b, eqvio_sim* const* sims, int max_frames, double* nees, int* frames_run) {
+    if (!b || !sims || max_frames < 0 || (max_frames > 0 && !nees) || !frames_run)
+        return EQF_E_BAD_ARG;
+    *frames_run = 0;
+    const int B = b->f->slots();
+    for (size_t i = 0; i < (size_t)max_frames * B; ++i)
+        nees[i] = std::nan("");
+    return guarded(b, [&] {
+        VIOFilterBatch& f = *b->f;
+        struct SimSlot {
+            int np = 0, M = 0;
+            bool image = false; // an image is in hand
+            double stamp = 0, sensor[23];
+            std::vector<int> tids, ids;
+            std::vector<double> tp, y;
+            eqvio_camera cam;
+        };
+        std::vector<SimSlot> ss(B);
+        // slot k's measurements up to its next image: the IMU samples go to the slot (or to `held`); false at the end of the sequence
+        auto next_image = [&](int k, std::vector<IMUVelocity>* held) {
+            SimSlot& s = ss[k];
+            for (;;) {
+                const int type = eqvio_sim_next_measurement_type(sims[k]);
+                if (type == EQVIO_MEAS_NONE)
+                    return false;
+                if (type == EQVIO_MEAS_IMAGE) {
+                    s.M = eqvio_sim_get_vision(sims[k], &s.stamp, s.ids.data(), s.y.data(), s.np);
+                    if (s.M < 0)
+                        throw std::runtime_error("slot " + std::to_string(k) + ": more features than world points");
+                    return true;
+                }
+                double imu[13];
+                eqvio_sim_get_imu(sims[k], imu);
+                if (held)
+                    held->push_back(imu_from13(imu));
+                else
+                    f.processIMUData(k, imu_from13(imu));
+            }
+        };
+        auto truth = [&](int k, double stamp, int noise) {
+            SimSlot& s = ss[k];
+            if (eqvio_sim_true_state(sims[k], stamp, noise, s.sensor, s.tids.data(), s.tp.data(), s.np) != s.np)
+                throw std::runtime_error("eqvio_sim_true_state");
+        };
+        // start: getInitialCondition() (main_sim.cpp:105) trimmed to the first image's ids, in the initial condition's order
+        for (int k = 0; k < B; ++k) {
+            if (!sims[k])
+                continue;
+            SimSlot& s = ss[k];
+            s.np = eqvio_sim_num_points(sims[k]);
+            s.tids.resize(s.np + 1), s.tp.resize(3 * (size_t)s.np + 3), s.ids.resize(s.np + 1), s.y.resize(2 * (size_t)s.np + 2);
+            eqvio_sim_camera(sims[k], &s.cam);
+            truth(k, 0.0, 1);
+            std::vector<double> s0(s.sensor, s.sensor + 23);
+            std::vector<IMUVelocity> held;
+            s.image = next_image(k, &held);
+            std::vector<int> ids;
+            std::vector<double> p;
+            for (int i = 0; i < s.np && s.image; ++i)
+                if (std::binary_search(s.ids.begin(), s.ids.begin() + s.M, s.tids[i])) {
+                    ids.push_back(s.tids[i]);
+                    p.insert(p.end(), s.tp.begin() + 3 * i, s.tp.begin() + 3 * i + 3);
+                }
+            f.startFromState(k, s0.data(), ids.data(), p.data(), (int)ids.size(), 0.0);
+            for (const IMUVelocity& u : held)
+                f.processIMUData(k, u);
+        }
+        std::vector<int> slots, status, counts, ids_all, tcounts, tids_all;
+        std::vector<double> stamps, y_all, sensors, tp_all, out;
+        std::vector<eqvio_camera> cams;
+        std::vector<eqf_batch_augment_entry> aug;
+        std::vector<eqf_batch_truth> tr;
+        auto fail = [&](const char* what, size_t e, int code) {
+            throw std::runtime_error(std::string(what) + ", frame " + std::to_string(*frames_run) + ", slot " + std::to_string(slots[e]) + ": " + eqf_error_string(code));
+        };
+        while (*frames_run < max_frames) {
+            slots.clear();
+            for (int k = 0; k < B; ++k)
+                if (sims[k] && ss[k].image)
+                    slots.push_back(k);
+            if (slots.empty())
+                break;
+            const size_t n = slots.size();
+            // augmentLandmarkStates(ids, getTrueState(stamp, true)) (main_sim.cpp:137-140)
+            aug.resize(n), status.assign(n, 0);
+            for (size_t e = 0; e < n; ++e) {
+                SimSlot& s = ss[slots[e]];
+                truth(slots[e], s.stamp, 1);
+                aug[e] = eqf_batch_augment_entry{slots[e], s.M, s.ids.data(), s.np, s.tids.data(), s.tp.data()};
+            }
+            eqvio_amd::check(eqf_batch_augment(f.core(), (int)n, aug.data(), status.data()), "eqf_batch_augment");
+            for (size_t e = 0; e < n; ++e)
+                if (status[e])
+                    fail("augment", e, status[e]);
+            // processVisionData
+            stamps.clear(), cams.clear(), counts.clear(), ids_all.clear(), y_all.clear();
+            for (int k : slots) {
+                const SimSlot& s = ss[k];
+                stamps.push_back(s.stamp);
+                cams.push_back(s.cam);
+                counts.push_back(s.M);
+                ids_all.insert(ids_all.end(), s.ids.begin(), s.ids.begin() + s.M);
+                y_all.insert(y_all.end(), s.y.begin(), s.y.begin() + 2 * s.M);
+            }
+            f.processVisionData((int)n, slots.data(), stamps.data(), cams.data(), counts.data(), ids_all.data(), y_all.data(), status.data());
+            for (size_t e = 0; e < n; ++e)
+                if (status[e])
+                    fail("vision", e, status[e]);
+            // computeNEES(getTrueState(getTime())) (main_sim.cpp:145-147)
+            tr.resize(n), out.resize(n);
+            for (size_t e = 0; e < n; ++e) {
+                SimSlot& s = ss[slots[e]];
+                truth(slots[e], f.slot(slots[e]).currentTime, 0);
+                tr[e] = eqf_batch_truth{slots[e], s.sensor, s.np, s.tids.data(), s.tp.data()};
+            }
+            eqvio_amd::check(eqf_batch_nees(f.core(), (int)n, tr.data(), out.data(), status.data()), "eqf_batch_nees");
+            for (size_t e = 0; e < n; ++e) {
+                if (status[e])
+                    fail("nees", e, status[e]);
+                nees[(size_t)*frames_run * B + slots[e]] = out[e];
+            }
+            ++*frames_run;
+            for (int k : slots)
+                ss[k].image = next_image(k, nullptr);
+        }
+    });
 }

@@ -5,6 +5,8 @@
 #include "VIOSimulator.hpp"
 #include "VIOWriter.hpp"
 #include "cli.hpp"
+#include "eqvio_batch.h"
+#include <algorithm>
 #include <fstream>
 #include <iomanip>
 #include <chrono>
@@ -19,8 +21,99 @@ using namespace eqvio_amd;
 static void usage() {
     std::puts("usage: eqvio_sim [--duration S] [--trajectory wave|square|sine|line] [--numPoints N] [--numWalls W] [--wallDistance D]\n"
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
-              "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)");
+              "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
+              "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
+              "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
+              "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
+              "              shipped EuRoC / UZH-FPV configurations); the Normal chart, --maxFeatures above 64, --fullState, --landmarkReset and\n"
+              "              --output are refused.");
+}
+
+// --batch B: the default-mode loop of main() for B seeds in lockstep, through eqvio_batch_run_sim (augment, vision step and NEES: one launch each per frame)
+static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet) {
+    eqvio_sim_settings ss;
+    eqvio_sim_default_settings(&ss);
+    ss.numPoints = sim.numPoints;
+    ss.wallDistance = sim.wallDistance;
+    ss.numWalls = sim.numWalls;
+    ss.maxFeatures = (int)sim.maxFeatures;
+    ss.initialNoise = sim.initialNoise, ss.inputNoise = sim.inputNoise, ss.outputNoise = sim.outputNoise;
+    ss.duration = sim.duration;
+    const char* names[4] = {"wave", "square", "sine", "line"};
+    ss.trajectory = (int)(std::find(names, names + 4, sim.trajectory) - names);
+    ss.imuFreq = sim.imuFreq;
+    ss.imageFreq = sim.imageFreq;
+    eqvio_settings es;
+    std::memset(&es, 0, sizeof(es));
+    es.biasOmegaProcessVariance = fs.biasOmegaProcessVariance, es.biasAccelProcessVariance = fs.biasAccelProcessVariance;
+    es.attitudeProcessVariance = fs.attitudeProcessVariance, es.positionProcessVariance = fs.positionProcessVariance;
+    es.velocityProcessVariance = fs.velocityProcessVariance, es.cameraAttitudeProcessVariance = fs.cameraAttitudeProcessVariance;
+    es.cameraPositionProcessVariance = fs.cameraPositionProcessVariance, es.pointProcessVariance = fs.pointProcessVariance;
+    es.velGyrNoise = fs.velGyrNoise, es.velAccNoise = fs.velAccNoise, es.velGyrBiasWalk = fs.velGyrBiasWalk, es.velAccBiasWalk = fs.velAccBiasWalk;
+    es.measurementNoise = fs.measurementNoise, es.outlierThresholdAbs = fs.outlierThresholdAbs, es.outlierThresholdProb = fs.outlierThresholdProb;
+    es.featureRetention = fs.featureRetention;
+    es.initialAttitudeVariance = fs.initialAttitudeVariance, es.initialPositionVariance = fs.initialPositionVariance;
+    es.initialVelocityVariance = fs.initialVelocityVariance, es.initialCameraAttitudeVariance = fs.initialCameraAttitudeVariance;
+    es.initialCameraPositionVariance = fs.initialCameraPositionVariance, es.initialPointVariance = fs.initialPointVariance;
+    es.initialPointDepthVariance = fs.initialPointDepthVariance, es.initialBiasOmegaVariance = fs.initialBiasOmegaVariance;
+    es.initialBiasAccelVariance = fs.initialBiasAccelVariance, es.initialSceneDepth = fs.initialSceneDepth;
+    es.useDiscreteInnovationLift = fs.useDiscreteInnovationLift, es.useDiscreteVelocityLift = fs.useDiscreteVelocityLift;
+    es.useDiscreteStateMatrix = fs.useDiscreteStateMatrix, es.fastRiccati = fs.fastRiccati, es.useMedianDepth = fs.useMedianDepth;
+    es.useFeaturePredictions = fs.useFeaturePredictions, es.useEquivariantOutput = fs.useEquivariantOutput, es.removeLostLandmarks = fs.removeLostLandmarks;
+    es.coordinateChoice = (int)fs.coordinateChoice;
+    const double offset[7] = {fs.cameraOffset.R.w, fs.cameraOffset.R.x, fs.cameraOffset.R.y, fs.cameraOffset.R.z, fs.cameraOffset.x.x, fs.cameraOffset.x.y, fs.cameraOffset.x.z};
+    std::memcpy(es.cameraOffset, offset, sizeof(offset));
+    std::vector<eqvio_sim*> sims(B, nullptr);
+    auto release = [&] {
+        for (eqvio_sim* s : sims)
+            eqvio_sim_destroy(s);
+    };
+    for (int k = 0; k < B; ++k) {
+        ss.randomSeed = sim.randomSeed + (unsigned)k;
+        sims[k] = eqvio_sim_create(&ss, &es);
+        if (!sims[k]) {
+            std::fprintf(stderr, "eqvio_sim: eqvio_sim_create failed\n");
+            release();
+            return 1;
+        }
+    }
+    eqvio_sim_camera_offset(sims[0], es.cameraOffset); // camera extrinsics of the data server (main_sim.cpp:97-101)
+    eqvio_batch* b = nullptr;
+    int rc = eqvio_batch_create(&b, &es, fs.device, B, (int)sim.maxFeatures);
+    if (rc) {
+        std::fprintf(stderr, "eqvio_sim: eqvio_batch_create: %s\n", eqf_error_string(rc));
+        release();
+        return 1;
+    }
+    const int maxFrames = (int)std::ceil(sim.duration * sim.imageFreq) + 2;
+    std::vector<double> nees((size_t)maxFrames * B);
+    int frames = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = eqvio_batch_run_sim(b, sims.data(), maxFrames, nees.data(), &frames);
+    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) {
+        std::fprintf(stderr, "eqvio_sim: eqvio_batch_run_sim: %s\n", rc == -1 ? eqvio_batch_last_error(b) : eqf_error_string(rc));
+        eqvio_batch_destroy(b);
+        release();
+        return 1;
+    }
+    double sumOfMeans = 0;
+    for (int k = 0; k < B; ++k) {
+        double s = 0;
+        int n = 0;
+        for (int j = 0; j < frames; ++j) {
+            const double v = nees[(size_t)j * B + k];
+            if (v == v)
+                s += v, ++n;
+        }
+        const double mean = s / std::max(n, 1);
+        sumOfMeans += mean;
+        std::printf("run %d seed %u: mean NEES %.9g over %d frames\n", k, sim.randomSeed + (unsigned)k, mean, n);
+    }
+    std::printf("batch of %d runs: mean of the runs' mean NEES %.9g  frames %d  runs x frames/s %.1f\n", B, sumOfMeans / B, frames, (double)B * frames / elapsed);
+    eqvio_batch_destroy(b);
+    release();
+    return 0;
 }
 
 int main(int argc, char** argv) {
@@ -29,6 +122,7 @@ int main(int argc, char** argv) {
     VIOFilter::Settings fs;
     bool fullState = false, quiet = false, sigmaFP32 = false;
     double landmarkResetTime = -1.0;
+    int batch = 0;
     std::string outputDir, datasetDir;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -57,11 +151,29 @@ int main(int argc, char** argv) {
         else if (a == "--writeDataset") datasetDir = val();
         else if (a == "--quiet") quiet = true;
         else if (a == "--sigmaFP32") sigmaFP32 = true;
+        else if (a == "--batch") batch = std::atoi(val());
         else if (parseFilterFlag(a, val, fs)) {
         } else {
             usage();
             return a == "--help" ? 0 : 2;
         }
+    }
+    if (batch != 0) { // what the filter batch refuses, before any device is opened
+        const char* why = batch < 1 ? "--batch needs B >= 1"
+                          : !fs.fastRiccati ? "--batch needs --fastRiccati 1 (the batch has fast Riccati only; the default is 0)"
+                          : fs.coordinateChoice == CoordinateChoice::Normal ? "--batch does not support the Normal chart"
+                          : sim.maxFeatures > EQF_BATCH_MAX_LANDMARKS ? "--batch holds at most 64 landmarks per run: --maxFeatures <= 64"
+                          : fullState ? "--batch does not support --fullState"
+                          : landmarkResetTime >= 0 ? "--batch does not support --landmarkReset"
+                          : !outputDir.empty() ? "--batch does not support --output"
+                          : !datasetDir.empty() ? "--batch does not support --writeDataset"
+                          : sigmaFP32 ? "--batch does not support --sigmaFP32"
+                          : nullptr;
+        if (why) {
+            std::fprintf(stderr, "eqvio_sim: %s\n", why);
+            return 2;
+        }
+        return runBatch(sim, fs, batch, quiet);
     }
     double lastLandmarkReset = landmarkResetTime > 0 ? 0.0 : std::nan("");
 

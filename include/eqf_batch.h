@@ -78,6 +78,46 @@ int eqf_batch_state_estimate(eqf_batch* b, int slot, double* sensor, int* ids, d
 int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status);
 /* flags (EQF_BATCH_*) of the slot's last step, and the depth its new landmarks got */
 int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth);
+
+/* One slot's true state for eqf_batch_nees: the 23 sensor doubles (eqvio_types.h layout) and n_true landmarks, ids in any order, camera-frame points. */
+typedef struct eqf_batch_truth {
+    int slot;
+    const double* sensor;
+    int n_true;
+    const int* ids;
+    const double* p; /* 3 n_true */
+} eqf_batch_truth;
+
+/* computeNEES (VIO_eqf.cpp:153-170) of the `count` listed slots (distinct): one packet to the device, one launch (one workgroup per entry), one copy back,
+ * one synchronisation. nees[e] is entry e's NEES; status[e]:
+ *   0                  done: a Cholesky factorisation of [Sigma ; eps^T], or, when a pivot was <= 0, partial-pivot elimination on [Sigma | eps]
+ *                      (eqf_batch_nees_lu_fallbacks counts those), as eqf_compute_nees;
+ *   EQF_E_BAD_ARG      bad slot index, repeated slot, null pointers, or a filter landmark id missing from the truth (the reference asserts there).
+ * The call is read-only: no slot's state, Sigma or landmark planes change. Returns 0 when the launch ran (whatever the per-entry codes), EQF_E_BAD_ARG for
+ * null arguments or count < 0, or a HIP error. */
+int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, double* nees, int* status);
+/* how many eqf_batch_nees entries of the slot took the partial-pivot fallback */
+int eqf_batch_nees_lu_fallbacks(const eqf_batch* b, int slot, long* count);
+
+/* One slot's augmentLandmarkStates for eqf_batch_augment: the ids the slot keeps and adds (n_new), and the provided state's landmarks (n_prov ids and
+ * camera-frame points) the new ones are taken from. */
+typedef struct eqf_batch_augment_entry {
+    int slot;
+    int n_new;
+    const int* new_ids;
+    int n_prov;
+    const int* prov_ids;
+    const double* prov_p; /* 3 n_prov */
+} eqf_batch_augment_entry;
+
+/* VIOFilter::augmentLandmarkStates(newIds, providedState) (VIOFilter.cpp:112-132) of the `count` listed slots (distinct), one launch (one workgroup per entry
+ * that changes its slot): landmarks whose id is not in new_ids leave the state; ids of new_ids not in the state are appended in new_ids order, q0 = the
+ * provided point, Q = identity, with zero cross terms and initialPointVariance I in Sigma. status[e]:
+ *   0                  done (an entry that neither removes nor adds leaves its slot as it is, bit for bit);
+ *   EQF_E_BAD_ARG      bad or repeated slot, null pointers, or a new id without a provided point: the slot is untouched;
+ *   EQF_E_CAPACITY     the result would hold more than max_landmarks: the slot is untouched.
+ * Returns 0, EQF_E_BAD_ARG for null arguments or count < 0, or a HIP error. */
+int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* entries, int* status);
 /* the hipStream_t the batch launches on, as void* */
 void* eqf_batch_stream(eqf_batch* b);
 int eqf_batch_synchronize(eqf_batch* b);

@@ -9,6 +9,7 @@
 #define EQVIO_BATCH_H
 #include "eqf_batch.h"
 #include "eqvio_filter.h"
+#include "eqvio_sim.h"
 #include "eqvio_types.h"
 
 #ifdef __cplusplus
@@ -37,6 +38,23 @@ int eqvio_batch_process_vision(eqvio_batch* b, int count, const int* slots, cons
  * frame j of every slot that has one - its IMU samples, then its measurement - goes in one device step; a slot whose sequence has ended sits out. Returns the
  * number of steps run, or -1 (a slot's frame was refused or failed: message via eqvio_batch_last_error). */
 int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count);
+
+/* viewEqFState().computeNEES(trueState) of `count` distinct slots in ONE launch (eqf_batch_nees). Entry e: slot slots[e], the 23 sensor doubles at
+ * true_sensor_all + 23 e, true_counts[e] landmarks taken in order from true_ids_all / true_p_all (3 doubles each). nees[e], status[e] as eqf_batch_nees.
+ * Returns 0, EQF_E_BAD_ARG or a HIP error. */
+int eqvio_batch_compute_nees(eqvio_batch* b, int count, const int* slots, const double* true_sensor_all, const int* true_counts, const int* true_ids_all,
+                             const double* true_p_all, double* nees, int* status);
+/* augmentLandmarkStates(newIds, providedState) (VIOFilter.cpp:112-132) of `count` distinct slots in ONE launch (eqf_batch_augment). Entry e: slot slots[e],
+ * new_counts[e] ids from new_ids_all, prov_counts[e] provided landmarks from prov_ids_all / prov_p_all. status[e] as eqf_batch_augment. Returns 0,
+ * EQF_E_BAD_ARG or a HIP error. */
+int eqvio_batch_augment_landmark_states(eqvio_batch* b, int count, const int* slots, const int* new_counts, const int* new_ids_all, const int* prov_counts,
+                                        const int* prov_ids_all, const double* prov_p_all, int* status);
+/* The reference's main_sim loop (src/main_sim.cpp:128-184, default mode) over the slots in lockstep: sims[k] is slot k's data server (NULL: the slot sits out).
+ * Slot k starts from getInitialCondition() trimmed to the ids of its first image (initial-condition order: what the first augmentLandmarkStates leaves).
+ * Per vision frame: every slot's IMU samples up to its next image, then ONE augment call (the image's ids, getTrueState(stamp, true)), ONE step and ONE NEES
+ * call (getTrueState(time)) for every slot that has a frame. nees: max_frames x slots, row-major [frame][slot], NaN where a slot has no frame. Runs until
+ * every sim has ended or max_frames frames have run; *frames_run = frames run. Returns 0, EQF_E_BAD_ARG, or -1 (a call failed: eqvio_batch_last_error). */
+int eqvio_batch_run_sim(eqvio_batch* b, eqvio_sim* const* sims, int max_frames, double* nees, int* frames_run);
 
 /* per slot: stateEstimate, viewEqFState (xi0, X, Sigma), getTime, isInitialised, and the forcing of a whole EqF state (teacher forcing) */
 int eqvio_batch_state_estimate(eqvio_batch* b, int slot, double* sensor, int* ids, double* p, int cap); /* returns N or < 0 */
