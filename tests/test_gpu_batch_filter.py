@@ -3,8 +3,9 @@ result does not depend on the batch around it; errors stay in their slot."""
 import numpy as np
 import pytest
 
+from batch_scenarios import CAMERAS, reference_defaults, shipped_euroc
 from eqvio_amd.batch import VIOFilterBatch
-from eqvio_amd.capi import COORD_EUCLIDEAN, COORD_INVDEPTH, Camera, Settings
+from eqvio_amd.capi import COORD_INVDEPTH
 from eqvio_amd.simworld import SimWorld
 from oracle_binding import OracleFilter
 from run_configs import parity
@@ -15,31 +16,6 @@ EQF_E_NOT_SPD, EQF_E_CAPACITY = -2, -4
 TOL = 1e-9
 
 
-def shipped_euroc(**kw):  # the shipped EuRoC configuration's filter settings: InvDepth, fixed depth, shipped thresholds
-    s = Settings.defaults()
-    vals = dict(coordinateChoice=COORD_INVDEPTH, fastRiccati=1, useDiscreteInnovationLift=0, useMedianDepth=0, initialSceneDepth=4.0, initialPointVariance=0.05,
-                measurementNoise=1.5, outlierThresholdAbs=6.0, outlierThresholdProb=4.0, featureRetention=0.5)
-    vals.update(kw)
-    for k, v in vals.items():
-        setattr(s, k, v)
-    s.cameraOffset[:] = [0.5, -0.5, 0.5, -0.5, 0, 0, 0]
-    return s
-
-
-def reference_defaults(**kw):  # VIOFilterSettings.h defaults (Euclidean, median depth, thresholds 1e8), fast Riccati
-    s = Settings.defaults()
-    s.fastRiccati = 1
-    s.cameraOffset[:] = [0.5, -0.5, 0.5, -0.5, 0, 0, 0]
-    for k, v in kw.items():
-        setattr(s, k, v)
-    return s
-
-
-CAMERAS = {
-    "pinhole": None,
-    "radtan": Camera.radtan(458.654, 457.296, 367.215, 248.375, 752, 480, -0.28, 0.07, 2e-4, 2e-5),
-    "equidistant": Camera.equidistant(458.654, 457.296, 367.215, 248.375, 752, 480, -0.01, 0.02, -0.005, 0.001),
-}
 CONFIGS = {
     "shipped_euroc": (shipped_euroc, {}, "pinhole"),
     "reference_defaults": (reference_defaults, {}, "pinhole"),

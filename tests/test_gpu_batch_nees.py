@@ -8,12 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from batch_scenarios import reference_defaults, shipped_euroc
 from eqvio_amd.batch import VIOFilterBatch
 from eqvio_amd.capi import COORD_EUCLIDEAN, COORD_INVDEPTH, EqfCore, SimSettings, SimulationDataServer
 from eqvio_amd.simworld import SimWorld
 from oracle_binding import OracleFilter
 from run_configs import parity
-from test_gpu_batch_filter import reference_defaults, shipped_euroc
 from util import reasonable_state, teacher_force
 
 pytestmark = pytest.mark.gpu

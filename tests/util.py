@@ -138,6 +138,22 @@ def random_imu(rng, stamp=0.0, bias_vel=False):
     return imu
 
 
+def imu_selection(imus, t0, stamp):
+    """dts, mean sample and total time of a frame's buffered IMU samples (rows of 13, stamp first), in fp64 as integrateUpToTime computes them
+    (src/VIOFilter.cpp:134-156)."""
+    k = len(imus)
+    dts = np.zeros(k)
+    for i in range(k):
+        a = max(imus[i][0], t0)
+        b = min(imus[i + 1][0], stamp) if i + 1 < k else stamp
+        dts[i] = max(b - a, 0.0)
+    total, acc = 0.0, np.zeros(13)
+    for i in range(k):
+        total += dts[i]
+        acc = acc + np.asarray(imus[i]) * dts[i]
+    return dts, acc * (1.0 / total), total
+
+
 def settings_for(chart, **kw):
     s = Settings.defaults()
     s.coordinateChoice = chart
