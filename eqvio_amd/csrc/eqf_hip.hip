@@ -187,6 +187,7 @@ struct eqf_ctx {
     int opt_prop_tpw = 1;                    // EQF_OPT_TILES_PER_WORKGROUP
     int opt_gather = 1;                      // EQF_OPT_GATHER_IN_PROPAGATE
     int opt_early_door = 1;                  // EQF_OPT_EARLY_DOORBELL
+    int opt_quiet_wait = 1;                  // EQF_OPT_QUIET_DOOR_WAIT
     int opt_la_watch_ahead = 1;              // (debug knob, option 102) LaArgs::watch_ahead
     int early_seq_next = 0, early_armed_seq = 0; // the doorbell sequence the next look-ahead launch carries / the one the launch in flight carries
     bool early_allowed = false;              // the call in progress can take the early doorbell (eqf_stats_then_update / eqf_stats_select_update)
@@ -560,6 +561,10 @@ int door_wait(eqf_ctx* c, int which, int seq, bool* early = nullptr) {
     volatile int* bell = reinterpret_cast<volatile int*>(c->h_door) + which;
     long spins_after_done = 0;
     const auto t0 = std::chrono::steady_clock::now();
+    // EQF_OPT_QUIET_DOOR_WAIT: the stream is not looked at before a wait has lasted kQuietWait, far longer than any frame. hipStreamQuery on a stream whose last
+    // command has no completion signal yet makes the runtime queue a marker behind it - a barrier packet of its own between the covariance update and the next
+    // propagation kernel, which the command processor works off in series (scripts/ubench/kernel_boundary.hip, profiles/r09_kernel_boundary_ubench.txt).
+    constexpr auto kQuietWait = std::chrono::milliseconds(2);
     // EQF_OPT_EARLY_DOORBELL: a caller that passes `early` also takes the look-ahead kernel's own doorbell (h_door[3]) - the update WILL be applied, Gamma's sensor rows are in
     // the packet, the lift's results are not - and is told so
     volatile int* bell_early = (which == 1 && early && c->early_armed_seq == seq) ? reinterpret_cast<volatile int*>(c->h_door) + 3 : nullptr;
@@ -584,7 +589,7 @@ int door_wait(eqf_ctx* c, int which, int seq, bool* early = nullptr) {
             }
             return 0;
         }
-        if ((it & 0xfff) == 0 || spins_after_done) {
+        if (spins_after_done || ((it & 0xfff) == 0 && (!c->opt_quiet_wait || std::chrono::steady_clock::now() - t0 >= kQuietWait))) {
             const hipError_t e = hipStreamQuery(c->stream);
             if (e == hipSuccess) {
                 if (++spins_after_done > 1000000) {
@@ -1170,6 +1175,7 @@ int eqf_get_option(const eqf_ctx* c, int option, int* value) {
     case EQF_OPT_GATHER_IN_PROPAGATE: *value = c->opt_gather; return 0;
     case EQF_OPT_HOLD_NEW_LANDMARKS: *value = c->opt_hold; return 0;
     case EQF_OPT_EARLY_DOORBELL: *value = c->opt_early_door; return 0;
+    case EQF_OPT_QUIET_DOOR_WAIT: *value = c->opt_quiet_wait; return 0;
     case EQF_OPT_SELECT_ONE_WORKGROUP: *value = c->opt_sel_one; return 0;
     case EQF_OPT_LIVE_COLUMNS_FIRST: *value = c->opt_live_first; return 0;
     case EQF_OPT_LA_HOME: *value = c->opt_la_home; return 0;
@@ -1236,6 +1242,9 @@ int eqf_set_option(eqf_ctx* c, int option, int value) {
         return 0;
     case EQF_OPT_EARLY_DOORBELL:
         c->opt_early_door = value ? 1 : 0;
+        return 0;
+    case EQF_OPT_QUIET_DOOR_WAIT:
+        c->opt_quiet_wait = value ? 1 : 0;
         return 0;
     case EQF_OPT_MEASURE_IN_PROPAGATE:
         c->opt_measure_prop = value ? 1 : 0;
@@ -1513,7 +1522,7 @@ static int grow_capacity(eqf_ctx* c, int new_cap) {
     // EVERY option of eqf_set_option (tests/test_gpu_edge_cases.py: test_options_and_counters_survive_capacity_growth walks the enum)
     const int opts[][2] = {{EQF_OPT_SIGMA_FP32, c->opt_f32}, {EQF_OPT_RICCATI_DENSE, c->opt_dense}, {EQF_OPT_CHECK_FINITE, c->opt_check}, {EQF_OPT_SPECULATIVE, c->opt_spec},
                            {EQF_OPT_DOORBELL, c->opt_door}, {EQF_OPT_EARLY_LIFT, c->opt_early}, {EQF_OPT_FUSED_ASSEMBLY, c->opt_fuse_asm}, {EQF_OPT_LOOKAHEAD, c->opt_lookahead},
-                           {EQF_OPT_LA_TIMEOUT_US, (int)(c->la_timeout_ticks / 100)}, {EQF_OPT_Z_IN_LOOKAHEAD, c->opt_zb ? (c->opt_zb_large ? 1 : 2) : 0}, {EQF_OPT_LA_SPLIT_ROWS, c->opt_la_split}, {EQF_OPT_LA_HOME, c->opt_la_home}, {EQF_OPT_TILES_PER_WORKGROUP, c->opt_prop_tpw}, {EQF_OPT_GATHER_IN_PROPAGATE, c->opt_gather}, {EQF_OPT_HOLD_NEW_LANDMARKS, c->opt_hold}, {EQF_OPT_EARLY_DOORBELL, c->opt_early_door}, {EQF_OPT_SELECT_ONE_WORKGROUP, c->opt_sel_one}, {EQF_OPT_LIVE_COLUMNS_FIRST, c->opt_live_first}, {EQF_OPT_MEASURE_IN_PROPAGATE, c->opt_measure_prop}, {EQF_OPT_LIFT_WITH_SYRK, c->opt_lift_syrk}, {EQF_OPT_TRACE, c->d_trace ? 1 : 0}, {100, c->opt_timing}};
+                           {EQF_OPT_LA_TIMEOUT_US, (int)(c->la_timeout_ticks / 100)}, {EQF_OPT_Z_IN_LOOKAHEAD, c->opt_zb ? (c->opt_zb_large ? 1 : 2) : 0}, {EQF_OPT_LA_SPLIT_ROWS, c->opt_la_split}, {EQF_OPT_LA_HOME, c->opt_la_home}, {EQF_OPT_TILES_PER_WORKGROUP, c->opt_prop_tpw}, {EQF_OPT_GATHER_IN_PROPAGATE, c->opt_gather}, {EQF_OPT_HOLD_NEW_LANDMARKS, c->opt_hold}, {EQF_OPT_EARLY_DOORBELL, c->opt_early_door}, {EQF_OPT_QUIET_DOOR_WAIT, c->opt_quiet_wait}, {EQF_OPT_SELECT_ONE_WORKGROUP, c->opt_sel_one}, {EQF_OPT_LIVE_COLUMNS_FIRST, c->opt_live_first}, {EQF_OPT_MEASURE_IN_PROPAGATE, c->opt_measure_prop}, {EQF_OPT_LIFT_WITH_SYRK, c->opt_lift_syrk}, {EQF_OPT_TRACE, c->d_trace ? 1 : 0}, {100, c->opt_timing}};
     for (const auto& o : opts)
         if ((rc = eqf_set_option(t, o[0], o[1])) != 0)
             break;

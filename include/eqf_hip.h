@@ -121,6 +121,10 @@ enum {
                                   Built in round 5 and not taken (level at 200 landmarks, where the next propagation waits for the covariance update anyway; the counting cost the
                                   factorisation 2 us); taken in round 6 with a count that needs no barrier, acknowledgement or release: +3 .. 4.5 % at 50, +2.8 % at 100 landmarks -
                                   the sizes the reference's own configurations run at, where the GPU idled 10 us per frame behind the host -, level at 200 */
+    EQF_OPT_QUIET_DOOR_WAIT = 29, /* 1 (default): a host wait on a doorbell does not look at the stream (hipStreamQuery, there to report a kernel fault instead of spinning for ever)
+                                  before it has lasted 2 ms. The query makes the runtime queue a marker with a completion signal behind the last launch: a barrier packet between the
+                                  covariance update and the next propagation kernel, worked off in series by the command processor. Same launches, same
+                                  arguments: bit-identical. 0: the stream is queried every 4096 polls of the doorbell, as before */
     EQF_OPT_SELECT_ONE_WORKGROUP = 25, /* 1 (default): up to 512 landmarks, the outlier statistics and the device-side outlier decision of eqf_stats_select_update are one
                                   launch of one workgroup (k_stats_select); 0: two launches (k_outlier_stats, k_select_outliers), as above 512 landmarks. Same results */
     EQF_OPT_LIVE_COLUMNS_FIRST = 26, /* 1 (default): in eqf_stats_select_update up to 16 panels (256 measurements), k_stats_select puts the measurements of the landmarks that stay in
