@@ -44,6 +44,9 @@ def load_batch_protos():
         "eqf_batch_destroy": (None, [vp]),
         "eqf_batch_slots": (C.c_int, [vp]),
         "eqf_batch_max_landmarks": (C.c_int, [vp]),
+        "eqf_batch_set_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
+        "eqf_batch_get_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
+        "eqf_batch_check_settings": (C.c_int, [P(Settings)]),
         "eqf_batch_num_landmarks": (C.c_int, [vp, C.c_int]),
         "eqf_batch_set_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
         "eqf_batch_get_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
@@ -64,6 +67,8 @@ def load_batch_protos():
         "eqvio_batch_destroy": (None, [vp]),
         "eqvio_batch_last_error": (C.c_char_p, [vp]),
         "eqvio_batch_slots": (C.c_int, [vp]),
+        "eqvio_batch_set_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
+        "eqvio_batch_get_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
         "eqvio_batch_process_imu": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqvio_batch_process_vision": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, P(Camera), c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
@@ -139,6 +144,19 @@ class VIOFilterBatch:
             self.close()
         except Exception:
             pass
+
+    def set_slot_settings(self, k, settings):
+        """Slot k's own settings from its next frame on (eqvio_batch_set_slot_settings): gains, thresholds, depth, lift choices and chart are per slot, so one
+        step runs B different tunings. A refusal (fastRiccati 0, the Normal chart, a chart change on a slot that holds landmarks) raises BatchError with the
+        EQF_E_* code and leaves the slot as it was. The initial-value fields only matter to a slot that has not initialised yet."""
+        rc = self.lib.eqvio_batch_set_slot_settings(self.h, k, C.byref(settings))
+        if rc != 0:
+            raise BatchError(f"set_slot_settings({k}): " + (self.lib.eqvio_batch_last_error(self.h).decode() if rc == -1 else self.elib.eqf_error_string(rc).decode()), rc)
+
+    def get_slot_settings(self, k):
+        out = Settings()
+        self._chk(self.lib.eqvio_batch_get_slot_settings(self.h, k, C.byref(out)))
+        return out
 
     def start_slot(self, k, sensor, ids, p, time):
         sensor, ids, p = _f64(sensor), _i32(ids), _f64(p)
@@ -241,6 +259,12 @@ class BatchSlot:
     def __init__(self, batch, k):
         self.b, self.k = batch, k
         self.cap = EQF_BATCH_MAX_LANDMARKS
+
+    def set_slot_settings(self, settings):
+        self.b.set_slot_settings(self.k, settings)
+
+    def get_slot_settings(self):
+        return self.b.get_slot_settings(self.k)
 
     def process_imu(self, imu13):
         self.b.process_imu(self.k, imu13)

@@ -6,6 +6,8 @@
 // the statistics): 1.2 MB per slot, more than the Infinity Cache holds at 256 slots.
 // The slot's current buffers are named by the host (BatchIn::cur); the frame ends in the same pair or, when removeInvalidLandmarks drops a landmark, in the other.
 // A workgroup only ever touches its own slot's memory: no flags, no spin, no co-residency needed; the grid may exceed the compute units.
+// The filter settings a frame reads (chart, output, lifts, depth choice, thresholds, R, initial variance and depth, Q, P) are the SLOT's: BatchIn::ss, copied by
+// the host from the slot's settings into the packet entry of every step (eqf_batch_set_slot_settings), so one launch runs B different tunings.
 //
 // The phases of k_batch_frame (VIOFilter::processVisionData, fast Riccati, src/VIOFilter.cpp:194-241):
 //   0  rows of A and B of the surviving landmarks (assemble_landmark, sensor_Ass_entry / sensor_Bs_entry) into LDS; origin planes copied to the other
@@ -39,6 +41,12 @@ constexpr int BATCH_SPACK = BATCH_MAXM * (BATCH_MAXM + 1) / 2;
 // result flags (BatchOut::did)
 enum { BATCH_DID_OUTLIERS = 1, BATCH_DID_ADDED = 2, BATCH_DID_UPDATE = 4, BATCH_DID_INVALID = 8, BATCH_DID_EMPTY = 16 };
 
+// The settings a slot's frame reads (eqf_batch_set_slot_settings): the slot's own values, carried by its packet entry, so one launch runs B different tunings.
+struct BatchSlotSet {
+    int chart, star, discrete, median;
+    double thrAbs, thrProb, meas_var, init_var, init_depth;
+    double Qd[12], Pd[8];
+};
 // one slot's frame, prepared by the host (eqf_batch_step)
 struct BatchIn {
     int slot, cur;
@@ -54,6 +62,7 @@ struct BatchIn {
     double dt;                // dt_total of the Riccati step
     Cam cam;
     CommonK ck;               // sensor-level terms of A and B at the current X (compute_common)
+    BatchSlotSet ss;          // the slot's settings
 };
 struct BatchOut {
     int status, N, cur, did;
@@ -63,9 +72,7 @@ struct BatchOut {
     double depth;                // depth the new landmarks got
 };
 struct BatchArgs {
-    int chart, star, discrete, median, ld;
-    double thrAbs, thrProb, meas_var, init_var, init_depth;
-    double Qd[12], Pd[8];
+    int ld;
     double* sig;
     double* lm;
     double* scr;
@@ -83,6 +90,7 @@ __device__ __forceinline__ int bt_tri(int i, int j) { return i * (i + 1) / 2 + j
 constexpr int BATCH_SM_PROP = 441 + 252 + 66 + BATCH_L * 45 + BATCH_L * 9;
 constexpr int BATCH_SM_UPD = BATCH_SPACK + BATCH_L * 6 + BATCH_MAXM + BATCH_MAXM + BATCH_NMAX + 3;
 constexpr int BATCH_SM = BATCH_SM_PROP > BATCH_SM_UPD ? BATCH_SM_PROP : BATCH_SM_UPD;
+static_assert(BATCH_SM_PROP + 20 <= BATCH_SM, "the slot's Qd / Pd sit behind the propagation rows");
 
 __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) {
     __shared__ double sm[BATCH_SM];
@@ -94,7 +102,10 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     const BatchIn& in = ba.in[blockIdx.x];
     BatchOut* out = ba.out + blockIdx.x;
     const int tid = threadIdx.x;
-    const int L = BATCH_L, ld = ba.ld, chart = ba.chart;
+    const int L = BATCH_L, ld = ba.ld;
+    // the slot's settings: read once, before the first store of the launch
+    const int chart = in.ss.chart, star = in.ss.star, discrete = in.ss.discrete, median = in.ss.median;
+    const double thrAbs = in.ss.thrAbs, thrProb = in.ss.thrProb, meas_var = in.ss.meas_var, init_var = in.ss.init_var, init_depth = in.ss.init_depth;
     const bool ind = chart == EQVIO_COORD_INVDEPTH;
     const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
     double* S0 = ba.sig + (2 * (size_t)slot + cur) * ba.sig_stride;
@@ -111,6 +122,12 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     double* lm66 = sm + 693;
     double* Al = sm + 759;
     double* Bl = Al + BATCH_L * 45;
+    double* Qd = sm + BATCH_SM_PROP; // the slot's input gains and process variances, behind the rows (the update's region is the larger one)
+    double* Pd = Qd + 12;
+    if (tid < 12)
+        Qd[tid] = in.ss.Qd[tid];
+    else if (tid < 20)
+        Pd[tid - 12] = in.ss.Pd[tid - 12];
     for (int t = tid; t < 441; t += BATCH_T)
         Ass[t] = sensor_Ass_entry(in.ck, t);
     for (int t = tid; t < 252; t += BATCH_T)
@@ -205,9 +222,9 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         double v = f_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
         double nz = 0.0;
         for (int e = 0; e < 12; ++e)
-            nz += b_entry(r, e) * ba.Qd[e] * b_entry(c, e);
+            nz += b_entry(r, e) * Qd[e] * b_entry(c, e);
         if (r == c)
-            nz += ba.Pd[r < 21 ? r / 3 : 7];
+            nz += Pd[r < 21 ? r / 3 : 7];
         v += dt * nz;
         S1[r + (size_t)c * ld] = v;
         S1[c + (size_t)r * ld] = v;
@@ -241,7 +258,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
             const double ae = stats[i], pe = stats[Ns + i];
             if (ylm[2 * L + i] < 0.0)
                 continue;
-            if (ae > ba.thrAbs || pe > ba.thrProb)
+            if (ae > thrAbs || pe > thrProb)
                 cand |= 1ull << i;
         }
         for (int t = 0; t < in.max_outliers && cand; ++t) {
@@ -251,7 +268,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
             for (int i = 0; i < Ns; ++i) {
                 if (!((cand >> i) & 1ull))
                     continue;
-                const bool isabs = stats[i] > ba.thrAbs;
+                const bool isabs = stats[i] > thrAbs;
                 const double v = isabs ? stats[i] : stats[Ns + i];
                 if (best < 0 || (isabs && !best_abs) || (isabs == best_abs && v > best_v)) {
                     best = i;
@@ -267,8 +284,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
             if (!((drop >> i) & 1ull))
                 s_keep[nk++] = i;
         // getMedianSceneDepth over the landmarks that stay: the element nth_element puts at position nk / 2
-        double depth = ba.init_depth;
-        if (ba.median && nk > 0) {
+        double depth = init_depth;
+        if (median && nk > 0) {
             const int kth = nk / 2;
             for (int a = 0; a < nk; ++a) {
                 const double va = stats[2 * Ns + s_keep[a]];
@@ -320,7 +337,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     for (int t = tid; t < n2 * n2; t += BATCH_T) {
         const int r = t % n2, c = t / n2;
         const int gr = s_gidx[r], gc = s_gidx[c];
-        S0[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S1[gr + (size_t)gc * ld] : (r == c ? ba.init_var : 0.0);
+        S0[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S1[gr + (size_t)gc * ld] : (r == c ? init_var : 0.0);
     }
     if (tid < N2) {
         const int i = tid;
@@ -363,7 +380,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     double* gam = z + BATCH_MAXM;     // Gamma
     if (tid < M2) {
         const int i = s_mlm[tid], j = s_mj[tid];
-        const MeasOut o = measure_one(chart, in.cam, ld3(L0, L, i), ldq(L0 + BATCH_QQ * L, L, i), L0[BATCH_QA * L + i], in.y[2 * j], in.y[2 * j + 1], ba.star != 0,
+        const MeasOut o = measure_one(chart, in.cam, ld3(L0, L, i), ldq(L0 + BATCH_QQ * L, L, i), L0[BATCH_QA * L + i], in.y[2 * j], in.y[2 * j + 1], star != 0,
                                       ind ? ld_cc(L0, L, i, CC_R0) : M3{});
         for (int e = 0; e < 6; ++e)
             Cb[tid * 6 + e] = o.c[e];
@@ -396,7 +413,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         for (int c = 0; c < 3; ++c)
             for (int r = 0; r < 3; ++r)
                 sv[3 * c + r] = S0[(li + r) + (size_t)(lj + c) * ld];
-        bz_S_block(ci, cj, sv, ii == jj, ba.meas_var, o);
+        bz_S_block(ci, cj, sv, ii == jj, meas_var, o);
         Sp[bt_tri(2 * ii, 2 * jj)] = o[0][0];
         Sp[bt_tri(2 * ii + 1, 2 * jj)] = o[1][0];
         Sp[bt_tri(2 * ii + 1, 2 * jj + 1)] = o[1][1];
@@ -537,8 +554,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     double* est = ylm; // 4 planes of stride N2 (estimate, invalid flag)
     if (tid < N2) {
         const int i = tid;
-        const LiftIn li = lift_load(i, L, chart, ba.discrete, L0, L0 + BATCH_QQ * L, L0 + BATCH_QA * L);
-        lift_landmark(i, V3{gam[21 + 3 * i], gam[22 + 3 * i], gam[23 + 3 * i]}, li, N2, L, chart, ba.discrete, L0 + BATCH_QQ * L, L0 + BATCH_QA * L, est);
+        const LiftIn li = lift_load(i, L, chart, discrete, L0, L0 + BATCH_QQ * L, L0 + BATCH_QA * L);
+        lift_landmark(i, V3{gam[21 + 3 * i], gam[22 + 3 * i], gam[23 + 3 * i]}, li, N2, L, chart, discrete, L0 + BATCH_QQ * L, L0 + BATCH_QA * L, est);
     }
     if (tid < 21)
         out->gamma[tid] = gam[tid];
@@ -591,6 +608,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
 // every state landmark in state order; the landmark entries (pe = a R p, point_chart against q0) are computed here.
 struct NeesIn {
     int slot, cur, N;
+    int chart; // the slot's chart
     double eps[21];
     double p[3 * BATCH_L];
 };
@@ -599,7 +617,7 @@ struct NeesOut {
     int lu;       // 1: a pivot was <= 0 and the partial-pivot elimination gave the value
 };
 struct NeesArgs {
-    int chart, ld;
+    int ld;
     const double* sig;
     const double* lm;
     double* scr;
@@ -660,7 +678,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) {
     if (tid < N) {
         const int i = tid;
         const V3 pe = lm[BATCH_QA * L + i] * q_rot(ldq(lm + BATCH_QQ * L, L, i), V3{in.p[3 * i], in.p[3 * i + 1], in.p[3 * i + 2]}); // (Q_i^-1)^-1 p = a R p
-        const V3 e = point_chart(na.chart == EQVIO_COORD_INVDEPTH, pe, ld3(lm, L, i));
+        const V3 e = point_chart(in.chart == EQVIO_COORD_INVDEPTH, pe, ld3(lm, L, i));
         s_eps[21 + 3 * i] = e.x;
         s_eps[22 + 3 * i] = e.y;
         s_eps[23 + 3 * i] = e.z;
@@ -814,10 +832,10 @@ struct AugIn {
     int slot, cur, Nk, nnew; // landmarks kept, appended
     int keep[BATCH_L];       // state index of kept landmark i
     double p[3 * BATCH_L];   // provided point of the r-th appended landmark
+    double init_var;         // the slot's initialPointVariance
 };
 struct AugArgs {
     int ld;
-    double init_var;
     double* sig;
     double* lm;
     size_t sig_stride, lm_stride;
@@ -838,7 +856,7 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_augment(const AugArgs aa) {
     for (int t = tid; t < n2 * n2; t += BATCH_T) {
         const int r = t % n2, c = t / n2;
         const int gr = s_gidx[r], gc = s_gidx[c];
-        S1[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S0[gr + (size_t)gc * ld] : (r == c ? aa.init_var : 0.0);
+        S1[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S0[gr + (size_t)gc * ld] : (r == c ? in.init_var : 0.0);
     }
     if (tid < N2) {
         const int i = tid;

@@ -4032,10 +4032,10 @@ struct eqf_batch {
         int flags = 0;
         double depth = 0.0;
         long nees_lu = 0; // eqf_batch_nees entries answered by the partial-pivot fallback
+        eqvio_settings set{}; // the slot's own settings (eqf_batch_set_slot_settings; eqf_batch_create's until then)
+        BatchSlotSet ss{};    // what the kernels read of them: copied into the slot's packet entry of every step
     };
-    int device = 0, slots = 0, cap = 0, ld = 0, chart = 0;
-    eqvio_settings set{};
-    double Qd[12], Pd[8];
+    int device = 0, slots = 0, cap = 0, ld = 0;
     hipStream_t stream = nullptr;
     double *d_sig = nullptr, *d_lm = nullptr, *d_scr = nullptr;
     size_t sig_stride = 0, lm_stride = 0, scr_stride = 0;
@@ -4108,6 +4108,35 @@ int batch_fetch_landmarks(eqf_batch* b, int slot, std::vector<double>& out) {
     return 0;
 }
 bool batch_slot_ok(const eqf_batch* b, int slot) { return b && slot >= 0 && slot < b->slots; }
+// the settings checks eqf_batch_create and eqf_batch_set_slot_settings share: 0, EQF_E_BAD_ARG or EQF_E_UNSUPPORTED
+int batch_settings_check(const eqvio_settings* st) {
+    if (st->coordinateChoice != EQVIO_COORD_EUCLIDEAN && st->coordinateChoice != EQVIO_COORD_INVDEPTH && st->coordinateChoice != EQVIO_COORD_NORMAL)
+        return EQF_E_BAD_ARG;
+    if (!st->fastRiccati || st->coordinateChoice == EQVIO_COORD_NORMAL)
+        return EQF_E_UNSUPPORTED; // accurate / discrete Riccati and the Normal chart: the per-context path (eqf_hip.h)
+    return 0;
+}
+// the values the kernels read of a slot's settings
+BatchSlotSet batch_slot_values(const eqvio_settings* st) {
+    BatchSlotSet ss;
+    ss.chart = st->coordinateChoice;
+    ss.star = st->useEquivariantOutput;
+    ss.discrete = st->useDiscreteInnovationLift;
+    ss.median = st->useMedianDepth;
+    ss.thrAbs = st->outlierThresholdAbs;
+    ss.thrProb = st->outlierThresholdProb;
+    ss.meas_var = st->measurementNoise * st->measurementNoise;
+    ss.init_var = st->initialPointVariance;
+    ss.init_depth = st->initialSceneDepth;
+    const double qv[4] = {st->velGyrNoise * st->velGyrNoise, st->velAccNoise * st->velAccNoise, st->velGyrBiasWalk * st->velGyrBiasWalk,
+                          st->velAccBiasWalk * st->velAccBiasWalk}; // constructInputGainMatrix (VIOFilterSettings.h:192-201)
+    for (int i = 0; i < 12; ++i)
+        ss.Qd[i] = qv[i / 3];
+    const double pv[8] = {st->biasOmegaProcessVariance, st->biasAccelProcessVariance, st->attitudeProcessVariance, st->positionProcessVariance,
+                          st->velocityProcessVariance,  st->cameraAttitudeProcessVariance, st->cameraPositionProcessVariance, st->pointProcessVariance};
+    std::memcpy(ss.Pd, pv, sizeof(pv));
+    return ss;
+}
 // every entry point that allocates, copies or launches runs on the batch's device, and leaves the caller's current device as it was
 struct BatchDevice {
     int prev = -1;
@@ -4127,10 +4156,8 @@ struct BatchDevice {
 int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, const eqvio_settings* st) {
     if (!out || !st || slots < 1 || max_landmarks < 1 || max_landmarks > EQF_BATCH_MAX_LANDMARKS || device < 0)
         return EQF_E_BAD_ARG;
-    if (st->coordinateChoice != EQVIO_COORD_EUCLIDEAN && st->coordinateChoice != EQVIO_COORD_INVDEPTH && st->coordinateChoice != EQVIO_COORD_NORMAL)
-        return EQF_E_BAD_ARG;
-    if (!st->fastRiccati || st->coordinateChoice == EQVIO_COORD_NORMAL)
-        return EQF_E_UNSUPPORTED; // accurate / discrete Riccati and the Normal chart: the per-context path (eqf_hip.h)
+    if (int rc = batch_settings_check(st))
+        return rc;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device >= ndev)
@@ -4143,16 +4170,7 @@ int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, 
     b->device = device;
     b->slots = slots;
     b->cap = max_landmarks;
-    b->set = *st;
-    b->chart = st->coordinateChoice;
     b->ld = pick_ld(BATCH_NMAX);
-    const double qv[4] = {st->velGyrNoise * st->velGyrNoise, st->velAccNoise * st->velAccNoise, st->velGyrBiasWalk * st->velGyrBiasWalk,
-                          st->velAccBiasWalk * st->velAccBiasWalk}; // constructInputGainMatrix (VIOFilterSettings.h:192-201)
-    for (int i = 0; i < 12; ++i)
-        b->Qd[i] = qv[i / 3];
-    const double pv[8] = {st->biasOmegaProcessVariance, st->biasAccelProcessVariance, st->attitudeProcessVariance, st->positionProcessVariance,
-                          st->velocityProcessVariance,  st->cameraAttitudeProcessVariance, st->cameraPositionProcessVariance, st->pointProcessVariance};
-    std::memcpy(b->Pd, pv, sizeof(pv));
     b->sig_stride = (size_t)b->ld * BATCH_NMAX;
     b->lm_stride = (size_t)BATCH_PLANES * BATCH_L;
     b->scr_stride = batch_scr_doubles(b->ld);
@@ -4160,6 +4178,8 @@ int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, 
     for (auto& sl : b->s) {
         sl.xi0 = unpack_sensor(std::vector<double>{0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0}.data());
         sl.X = group_identity();
+        sl.set = *st;
+        sl.ss = batch_slot_values(st);
     }
     auto fail = [&](int rc) {
         eqf_batch_destroy(b);
@@ -4219,6 +4239,29 @@ int eqf_batch_synchronize(eqf_batch* b) {
         return EQF_E_BAD_ARG;
     BatchDevice dev(b);
     HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+// No device work: the values travel in the slot's packet entry of its next step / NEES / augment call.
+int eqf_batch_set_slot_settings(eqf_batch* b, int slot, const eqvio_settings* st) {
+    if (!b || !st)
+        return EQF_E_BAD_ARG;
+    if (int rc = batch_settings_check(st))
+        return rc;
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    eqf_batch::Slot& sl = b->s[slot];
+    if (st->coordinateChoice != sl.set.coordinateChoice && !sl.ids.empty())
+        return EQF_E_BAD_ARG; // the slot's Sigma is in the old chart's coordinates
+    sl.set = *st;
+    sl.ss = batch_slot_values(st);
+    return 0;
+}
+int eqf_batch_check_settings(const eqvio_settings* st) { return st ? batch_settings_check(st) : EQF_E_BAD_ARG; }
+int eqf_batch_get_slot_settings(const eqf_batch* b, int slot, eqvio_settings* out) {
+    if (!batch_slot_ok(b, slot) || !out)
+        return EQF_E_BAD_ARG;
+    *out = b->s[slot].set;
     return 0;
 }
 
@@ -4364,7 +4407,7 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         // removeOldLandmarks (VIOFilter.cpp:280-302) and the ids addNewLandmarks will append (:258-278)
         std::vector<int> surv;
         for (int i = 0; i < N0; ++i)
-            if (!b->set.removeLostLandmarks || std::binary_search(f.ids, f.ids + f.M, sl.ids[i]))
+            if (!sl.set.removeLostLandmarks || std::binary_search(f.ids, f.ids + f.M, sl.ids[i]))
                 surv.push_back(i);
         std::vector<int> midx(f.M);
         int nnew = 0;
@@ -4394,7 +4437,8 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         in.nnew = nnew;
         in.k = f.k;
         in.obs_off = nsteps;
-        in.max_outliers = (int)(size_t)((1.0 - b->set.featureRetention) * f.M); // removeOutliers (VIOFilter.cpp:305)
+        in.max_outliers = (int)(size_t)((1.0 - sl.set.featureRetention) * f.M); // removeOutliers (VIOFilter.cpp:305)
+        in.ss = sl.ss;
         Cam cam = make_cam(&f.cam);
         in.cam = cam;
         in.dt = f.dt_total;
@@ -4415,7 +4459,7 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         compute_common_at(sl.X, sl.xi0, f.imu13_mean, cm, in.ck); // integrateRiccatiStateFast at the current X
         GroupSensor X = sl.X;
         for (int s = 0; s < f.k; ++s)
-            observer_host_step(X, sl.xi0, f.imu13_k + 13 * s, f.dt_k[s], b->set.useDiscreteVelocityLift, b->h_steps[nsteps + s]);
+            observer_host_step(X, sl.xi0, f.imu13_k + 13 * s, f.dt_k[s], sl.set.useDiscreteVelocityLift, b->h_steps[nsteps + s]);
         nsteps += f.k;
         X_after[e] = X;
         for (int i : surv)
@@ -4426,18 +4470,7 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
     if (nin == 0)
         return 0;
     BatchArgs ba;
-    ba.chart = b->chart;
-    ba.star = b->set.useEquivariantOutput;
-    ba.discrete = b->set.useDiscreteInnovationLift;
-    ba.median = b->set.useMedianDepth;
     ba.ld = b->ld;
-    ba.thrAbs = b->set.outlierThresholdAbs;
-    ba.thrProb = b->set.outlierThresholdProb;
-    ba.meas_var = b->set.measurementNoise * b->set.measurementNoise;
-    ba.init_var = b->set.initialPointVariance;
-    ba.init_depth = b->set.initialSceneDepth;
-    std::memcpy(ba.Qd, b->Qd, sizeof(ba.Qd));
-    std::memcpy(ba.Pd, b->Pd, sizeof(ba.Pd));
     ba.sig = b->d_sig;
     ba.lm = b->d_lm;
     ba.scr = b->d_scr;
@@ -4469,7 +4502,7 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         int flags = (removed_old[e] ? EQF_BATCH_REMOVED_OLD : 0) | ((o.did & BATCH_DID_OUTLIERS) ? EQF_BATCH_REMOVED_OUTLIERS : 0) |
                     ((o.did & BATCH_DID_ADDED) ? EQF_BATCH_ADDED : 0) | ((o.did & BATCH_DID_EMPTY) ? EQF_BATCH_EMPTY : 0);
         if (o.status == 0 && (o.did & BATCH_DID_UPDATE)) {
-            sl.X = group_mul(sensor_lift_delta(o.gamma, sl.xi0, b->chart, b->set.useDiscreteInnovationLift), sl.X);
+            sl.X = group_mul(sensor_lift_delta(o.gamma, sl.xi0, sl.set.coordinateChoice, sl.set.useDiscreteInnovationLift), sl.X);
             flags |= EQF_BATCH_UPDATED;
             if (o.did & BATCH_DID_INVALID) {
                 std::vector<int> kept;
@@ -4552,7 +4585,8 @@ int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, doubl
         in.slot = t.slot;
         in.cur = sl.cur;
         in.N = N;
-        nees_sensor_error(sl.xi0, sl.X, b->chart, t.sensor, in.eps);
+        in.chart = sl.set.coordinateChoice;
+        nees_sensor_error(sl.xi0, sl.X, sl.set.coordinateChoice, t.sensor, in.eps);
         for (int i = 0; i < N; ++i)
             for (int c = 0; c < 3; ++c)
                 in.p[3 * i + c] = t.p[3 * jt[i] + c];
@@ -4561,7 +4595,6 @@ int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, doubl
     if (nin == 0)
         return 0;
     NeesArgs na;
-    na.chart = b->chart;
     na.ld = b->ld;
     na.sig = b->d_sig;
     na.lm = b->d_lm;
@@ -4650,6 +4683,7 @@ int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* en
         in.cur = sl.cur;
         in.Nk = nk;
         in.nnew = (int)from.size();
+        in.init_var = sl.set.initialPointVariance;
         for (int i = 0; i < nk; ++i)
             in.keep[i] = keep[i];
         for (size_t r = 0; r < from.size(); ++r)
@@ -4662,7 +4696,6 @@ int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* en
         return 0;
     AugArgs aa;
     aa.ld = b->ld;
-    aa.init_var = b->set.initialPointVariance;
     aa.sig = b->d_sig;
     aa.lm = b->d_lm;
     aa.sig_stride = b->sig_stride;

@@ -67,25 +67,57 @@ void check(int rc, const char* what) {
 }
 } // namespace
 
-VIOFilterBatch::VIOFilterBatch(const eqvio_settings& s, eqf_batch* b) : settings(s), batch(b) {
+VIOFilterBatch::VIOFilterBatch(eqf_batch* b) : batch(b) {
     const int slots = eqf_batch_slots(b);
     slotv.resize(slots);
-    // VIOFilter(const Settings&) (VIOFilter.cpp:31-41): xi0 with the camera offset, X = identity, Sigma = the initial sensor covariance
-    double xi0[23];
-    std::memcpy(xi0, kIdentityGroup, sizeof(xi0));
-    std::memcpy(xi0 + 16, s.cameraOffset, sizeof(double) * 7);
-    const std::vector<double> S = diagonal(initialCovariance(s, 0));
     for (int k = 0; k < slots; ++k) {
-        const int rc = eqf_batch_set_state(batch, k, xi0, kIdentityGroup, nullptr, nullptr, nullptr, 0);
-        const int rc2 = rc ? rc : eqf_batch_set_sigma(batch, k, S.data(), 21);
-        if (rc2) {
+        try {
+            resetSlot(k);
+        } catch (const BatchFailure&) {
             eqf_batch_destroy(batch);
             batch = nullptr;
-            check(rc2, "eqf_batch_set_state / eqf_batch_set_sigma");
+            throw;
         }
     }
 }
 VIOFilterBatch::~VIOFilterBatch() { eqf_batch_destroy(batch); }
+
+eqvio_settings VIOFilterBatch::slotSettings(int k) const {
+    eqvio_settings s;
+    check(eqf_batch_get_slot_settings(batch, k, &s), "eqf_batch_get_slot_settings");
+    return s;
+}
+// VIOFilter(const Settings&) (VIOFilter.cpp:31-41) with the slot's settings: xi0 with the camera offset, X = identity, Sigma = the initial sensor covariance
+void VIOFilterBatch::resetSlot(int k) {
+    const eqvio_settings s = slotSettings(k);
+    double xi0[23];
+    std::memcpy(xi0, kIdentityGroup, sizeof(xi0));
+    std::memcpy(xi0 + 16, s.cameraOffset, sizeof(double) * 7);
+    const std::vector<double> S = diagonal(initialCovariance(s, 0));
+    const int rc = eqf_batch_set_state(batch, k, xi0, kIdentityGroup, nullptr, nullptr, nullptr, 0);
+    check(rc ? rc : eqf_batch_set_sigma(batch, k, S.data(), 21), "eqf_batch_set_state / eqf_batch_set_sigma");
+}
+int VIOFilterBatch::setSlotSettings(int k, const eqvio_settings& s) {
+    if (const int rc = eqf_batch_check_settings(&s)) // the refusals in the order eqf_batch.h documents: the settings on their own first,
+        return rc;
+    eqvio_settings old;
+    if (const int rc = eqf_batch_get_slot_settings(batch, k, &old)) // ... then the slot index,
+        return rc;
+    if (const int rc = eqf_batch_set_slot_settings(batch, k, &s)) // ... then the chart against the slot's landmarks
+        return rc;
+    // what resetSlot reads of the settings: only a change of these asks for a new initial state
+    const bool initialValuesChanged = std::memcmp(old.cameraOffset, s.cameraOffset, sizeof(old.cameraOffset)) != 0 || initialCovariance(old, 0) != initialCovariance(s, 0);
+    if (!slotv.at(k).initialised && initialValuesChanged && eqf_batch_num_landmarks(batch, k) == 0) {
+        try {
+            resetSlot(k);
+        } catch (const BatchFailure&) {
+            if (const int rc = eqf_batch_set_slot_settings(batch, k, &old)) // N = 0: no chart refusal, so the slot has its former settings again
+                throw BatchFailure(std::string("the slot's reset failed, and so did putting its former settings back: ") + eqf_error_string(rc), rc);
+            throw;
+        }
+    }
+    return 0;
+}
 
 void VIOFilterBatch::startFromState(int k, const double* sensor, const int* ids, const double* p, int N, double time) { // VIOFilter.cpp:43-56
     Slot& sl = slotv.at(k);
@@ -95,7 +127,7 @@ void VIOFilterBatch::startFromState(int k, const double* sensor, const int* ids,
         std::memcpy(Q.data() + 5 * i, q, sizeof(q));
     }
     check(eqf_batch_set_state(batch, k, sensor, kIdentityGroup, ids, p, Q.data(), N), "eqf_batch_set_state");
-    const std::vector<double> S = diagonal(initialCovariance(settings, N));
+    const std::vector<double> S = diagonal(initialCovariance(slotSettings(k), N));
     check(eqf_batch_set_sigma(batch, k, S.data(), 21 + 3 * N), "eqf_batch_set_sigma");
     sl.velocityBuffer.clear();
     sl.currentTime = time;
@@ -249,7 +281,7 @@ int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* s, int device, i
         return rc;
     auto* b = new eqvio_batch;
     try {
-        b->f = new VIOFilterBatch(*s, core); // releases core itself if it throws
+        b->f = new VIOFilterBatch(core); // releases core itself if it throws
     } catch (const eqvio_amd::BatchFailure& e) {
         delete b;
         return e.code;
@@ -294,6 +326,16 @@ int eqvio_batch_get_sigma(eqvio_batch* b, int slot, double* out, int n) { return
 double eqvio_batch_get_time(const eqvio_batch* b, int slot) { return slot_ok(b, slot) ? b->f->slot(slot).currentTime : -1.0; }
 int eqvio_batch_is_initialised(const eqvio_batch* b, int slot) { return slot_ok(b, slot) ? (b->f->slot(slot).initialised ? 1 : 0) : EQF_E_BAD_ARG; }
 eqf_batch* eqvio_batch_core(eqvio_batch* b) { return b ? b->f->core() : nullptr; }
+int eqvio_batch_set_slot_settings(eqvio_batch* b, int slot, const eqvio_settings* s) {
+    if (!b || !s)
+        return EQF_E_BAD_ARG;
+    int code = 0;
+    const int rc = guarded(b, [&] { code = b->f->setSlotSettings(slot, *s); }); // the checks are eqf_batch_set_slot_settings's
+    return rc ? rc : code;
+}
+int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out) {
+    return b ? eqf_batch_get_slot_settings(b->f->core(), slot, out) : EQF_E_BAD_ARG;
+}
 int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count) {
     if (!b || !per_slot || first < 0 || count < 0)
         return EQF_E_BAD_ARG;

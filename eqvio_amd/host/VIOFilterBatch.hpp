@@ -24,11 +24,18 @@ class VIOFilterBatch {
         double currentTime = -1.0;
         bool initialised = false;
     };
-    // takes ownership of a batch made by eqf_batch_create with the same settings
-    VIOFilterBatch(const eqvio_settings& s, eqf_batch* batch);
+    // takes ownership of a batch made by eqf_batch_create; the slots' settings are the device layer's (eqf_batch_get_slot_settings), kept nowhere else
+    explicit VIOFilterBatch(eqf_batch* batch);
     ~VIOFilterBatch();
     VIOFilterBatch(const VIOFilterBatch&) = delete;
     VIOFilterBatch& operator=(const VIOFilterBatch&) = delete;
+    // The slot's own settings, from its next frame on (eqf_batch_set_slot_settings; returns its code, and nothing changes unless that is 0). The
+    // initial-value fields (cameraOffset, the initial sensor variances) only matter to a slot that has not initialised yet: when the call changes one of them
+    // on such a slot, while it holds no landmark, the slot is put back to what VIOFilter(const Settings&) makes of the new settings - which replaces a state or
+    // Sigma planted there through core(). Any other call, and any call on an initialised slot, keeps state and Sigma. If that reset fails on the device the
+    // call throws and the slot has its former settings again.
+    int setSlotSettings(int slot, const eqvio_settings& s);
+    eqvio_settings slotSettings(int slot) const;
     void startFromState(int slot, const double* sensor, const int* ids, const double* p, int N, double time);
     void processIMUData(int slot, const IMUVelocity& imu);
     // processVisionData for `count` slots in one device step; status per entry
@@ -48,7 +55,7 @@ class VIOFilterBatch {
     bool prepareFrame(int e, int k, double stamp, const eqvio_camera& cam, int M, const int* ids, const double* y, int* status);
     void stepPrepared(const int* slots, const double* stamps, int* status);
     void initialiseFromIMUData(int slot, const IMUVelocity& imu);
-    eqvio_settings settings;
+    void resetSlot(int slot);
     eqf_batch* batch = nullptr;
     std::vector<Slot> slotv;
 };

@@ -48,12 +48,29 @@ enum {
     EQF_BATCH_REMOVED_INVALID = 32
 };
 
-/* slots >= 1, 1 <= max_landmarks <= 64; settings: fastRiccati must be 1 and the chart Euclidean or InvDepth. The settings' gains, thresholds, depth and
- * lift choices hold for every slot. Every slot starts with no landmark, Sigma = 0 and xi0 = X = identity (set them with eqf_batch_set_state / _set_sigma). */
+/* slots >= 1, 1 <= max_landmarks <= 64; settings: fastRiccati must be 1 and the chart Euclidean or InvDepth. Every slot starts with these settings and
+ * keeps them until eqf_batch_set_slot_settings gives it its own: gains, thresholds, depth, lift choices and chart are per slot, so one step can run B
+ * different tunings. Every slot starts with no landmark, Sigma = 0 and xi0 = X = identity (set them with eqf_batch_set_state / _set_sigma). */
 int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, const eqvio_settings* s);
 void eqf_batch_destroy(eqf_batch* b);
 int eqf_batch_slots(const eqf_batch* b);
 int eqf_batch_max_landmarks(const eqf_batch* b);
+
+/* The slot's own settings, from its next eqf_batch_step / _nees / _augment on; the other slots keep theirs. What a slot reads of them: the eight process
+ * variances, the four IMU noises, measurementNoise, outlierThresholdAbs / Prob, featureRetention, initialPointVariance, initialSceneDepth, useMedianDepth,
+ * useEquivariantOutput, useDiscreteInnovationLift, useDiscreteVelocityLift, removeLostLandmarks and coordinateChoice. The call launches nothing and does not
+ * synchronise: the values travel in the slot's entry of the packet every step sends anyway. Refusals, checked in this order and before any device is
+ * looked at; the slot and its settings are then untouched, bit for bit:
+ *   EQF_E_BAD_ARG      null batch or settings, or a coordinateChoice outside the enum;
+ *   EQF_E_UNSUPPORTED  fastRiccati == 0 or the Normal chart (as eqf_batch_create);
+ *   EQF_E_BAD_ARG      bad slot index, or a chart other than the slot's while the slot holds landmarks: its Sigma is expressed in the old chart's
+ *                      coordinates. On a slot without landmarks the chart may change (the sensor chart is the same for Euclidean and InvDepth).
+ * get returns what the slot runs with: the last accepted set, or eqf_batch_create's settings. */
+int eqf_batch_set_slot_settings(eqf_batch* b, int slot, const eqvio_settings* s);
+int eqf_batch_get_slot_settings(const eqf_batch* b, int slot, eqvio_settings* out);
+/* What eqf_batch_create and eqf_batch_set_slot_settings make of these settings on their own: 0, EQF_E_BAD_ARG (null, or a coordinateChoice outside the enum)
+ * or EQF_E_UNSUPPORTED (fastRiccati == 0 or the Normal chart). Looks at no device and no batch: a caller can refuse a whole list of settings up front. */
+int eqf_batch_check_settings(const eqvio_settings* s);
 
 /* The slot's xi0 / X / landmarks (eqf_set_state's layout: ids, q0 3 and Q 5 doubles per landmark). N <= max_landmarks. Sigma is NOT changed by set_state:
  * set it afterwards with eqf_batch_set_sigma (n = 21 + 3 N). get_state returns N or < 0. */

@@ -18,9 +18,20 @@ extern "C" {
 
 typedef struct eqvio_batch eqvio_batch;
 
-/* every slot as VIOFilter(const Settings&) (src/VIOFilter.cpp:31-41): it initialises itself from its first IMU sample */
+/* every slot as VIOFilter(const Settings&) (src/VIOFilter.cpp:31-41): it initialises itself from its first IMU sample. The settings are every slot's until
+ * eqvio_batch_set_slot_settings gives a slot its own. */
 int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* settings, int device, int slots, int max_landmarks);
-/* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56) */
+/* The slot's own settings (eqf_batch_set_slot_settings, include/eqf_batch.h: same refusals, same codes, the slot untouched when refused), from the slot's next
+ * frame on; every other slot keeps its own. Whatever the host layer derives from settings uses the slot's copy. The initial-value fields (cameraOffset and the
+ * initial*Variance fields) only matter to a slot that has not initialised yet: a call that changes one of them on such a slot, while it holds no landmark, puts
+ * the slot back to what VIOFilter(const Settings&) makes of the new settings (this replaces a state or Sigma planted there through eqvio_batch_core), and
+ * eqvio_batch_create_slot_from_state takes its initial covariance from them; every other call, and every call on a slot that has initialised, keeps state and
+ * Sigma, and only the filter parameters change. Nothing changes unless the return value is 0: if that reset fails on the device (-1, eqvio_batch_last_error) the
+ * slot has its former settings again. eqvio_batch_run_prepared / _run_sim with the same sequence or simulator seed in
+ * every slot, after per-slot settings were set, is a settings sweep. get returns the slot's settings. */
+int eqvio_batch_set_slot_settings(eqvio_batch* b, int slot, const eqvio_settings* settings);
+int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out);
+/* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56), with the slot's settings */
 int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time);
 void eqvio_batch_destroy(eqvio_batch* b);
 const char* eqvio_batch_last_error(const eqvio_batch* b);
