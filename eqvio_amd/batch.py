@@ -60,6 +60,9 @@ def load_batch_protos():
         "eqf_batch_nees": (C.c_int, [vp, C.c_int, P(BatchTruth), c_double_p, c_int_p]),
         "eqf_batch_nees_lu_fallbacks": (C.c_int, [vp, C.c_int, P(C.c_long)]),
         "eqf_batch_augment": (C.c_int, [vp, C.c_int, P(BatchAugmentEntry), c_int_p]),
+        "eqf_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
+        "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
+        "eqf_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
     }
     fprotos = {
         "eqvio_batch_create": (C.c_int, [P(vp), P(Settings), C.c_int, C.c_int, C.c_int]),
@@ -83,6 +86,9 @@ def load_batch_protos():
         "eqvio_batch_compute_nees": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
         "eqvio_batch_augment_landmark_states": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_sim": (C.c_int, [vp, P(vp), C.c_int, c_double_p, c_int_p]),
+        "eqvio_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
+        "eqvio_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
+        "eqvio_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
     }
     for lib, protos in ((elib, eprotos), (flib, fprotos)):
         for name, (res, args) in protos.items():
@@ -246,6 +252,24 @@ class VIOFilterBatch:
         flags, depth = C.c_int(), C.c_double()
         self._chk(self.elib.eqf_batch_last_result(self.core_handle(), k, C.byref(flags), C.byref(depth)))
         return flags.value, depth.value
+
+    def last_innovation(self, k):
+        """(dof, nis, logdet) of slot k's last step (eqvio_batch_last_innovation): the rows m of the matched measurement, yTilde^T S^-1 yTilde and log det S
+        of its update; 0, 0, 0 after an empty measurement, m, NaN, NaN after a failed update. The innovation log-likelihood is
+        -0.5 * (nis + logdet + dof * log(2 pi))."""
+        dof, nis, logdet = C.c_int(), C.c_double(), C.c_double()
+        self._chk(self.lib.eqvio_batch_last_innovation(self.h, k, C.byref(dof), C.byref(nis), C.byref(logdet)))
+        return dof.value, nis.value, logdet.value
+
+    def innovation_totals(self, k):
+        """(updates, dof, nis, logdet): the sums over slot k's updated steps since the last reset, in step order (eqvio_batch_innovation_totals)."""
+        n, dof, nis, logdet = C.c_long(), C.c_long(), C.c_double(), C.c_double()
+        self._chk(self.lib.eqvio_batch_innovation_totals(self.h, k, C.byref(n), C.byref(dof), C.byref(nis), C.byref(logdet)))
+        return n.value, dof.value, nis.value, logdet.value
+
+    def reset_innovation_totals(self, k=None):
+        """Clears slot k's totals, or every slot's (k None)."""
+        self._chk(self.lib.eqvio_batch_reset_innovation_totals(self.h, -1 if k is None else k))
 
     def slot(self, k):
         if not 0 <= k < self.slots:

@@ -18,8 +18,8 @@
 //   3  addNewLandmarks: median of the squared depths (the nth_element element) or the fixed depth; the survivors, then the new landmarks (Q = identity,
 //      initialPointVariance I) go back to the first buffer pair.
 //   4  performVisionUpdate: C / yTilde (measure_one), T = Sigma C^T (bz_T_pair), S = C Sigma C^T + R (bz_S_block, packed lower triangle in LDS), Cholesky
-//      S = L L^T, W = L^-1 T^T and z = L^-1 yTilde by a blocked solve (MFMA products, VALU diagonal triangles), Gamma = W^T z, Sigma -= W^T W in MFMA
-//      tiles, landmark lift (lift_landmark); Gamma's 21 sensor
+//      S = L L^T, W = L^-1 T^T and z = L^-1 yTilde by a blocked solve (MFMA products, VALU diagonal triangles), the innovation statistics NIS = |z|^2 and
+//      log det S = 2 sum log L_kk (batch_wave_sum, from LDS), Gamma = W^T z, Sigma -= W^T W in MFMA tiles, landmark lift (lift_landmark); Gamma's 21 sensor
 //      rows go back to the host, which lifts the sensor part.
 //   5  removeInvalidLandmarks: flagged by the lift, compacted into the other buffer pair.
 // A pivot <= 0 (EQF_E_NOT_SPD) or a non-finite Gamma (EQF_E_NONFINITE) ends the frame before anything of the update is written: the slot then holds the frame's
@@ -70,6 +70,8 @@ struct BatchOut {
     unsigned long long invalid;  // bits: landmark index (after addNewLandmarks) removed by removeInvalidLandmarks
     double gamma[21];            // sensor rows of Gamma
     double depth;                // depth the new landmarks got
+    int dof;                     // rows m of the matched measurement (0: empty)
+    double nis, logdet;          // yTilde^T S^-1 yTilde and log det S of the update (NaN when the update failed)
 };
 struct BatchArgs {
     int ld;
@@ -91,6 +93,13 @@ constexpr int BATCH_SM_PROP = 441 + 252 + 66 + BATCH_L * 45 + BATCH_L * 9;
 constexpr int BATCH_SM_UPD = BATCH_SPACK + BATCH_L * 6 + BATCH_MAXM + BATCH_MAXM + BATCH_NMAX + 3;
 constexpr int BATCH_SM = BATCH_SM_PROP > BATCH_SM_UPD ? BATCH_SM_PROP : BATCH_SM_UPD;
 static_assert(BATCH_SM_PROP + 20 <= BATCH_SM, "the slot's Qd / Pd sit behind the propagation rows");
+
+// Sum of one wave's 64 values in a fixed order (the butterfly's pairing depends on the lane numbers alone); every lane gets it.
+__device__ __forceinline__ double batch_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1)
+        v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) {
     __shared__ double sm[BATCH_SM];
@@ -367,6 +376,9 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
             out->cur = cur;
             out->did |= BATCH_DID_EMPTY;
             out->invalid = 0;
+            out->dof = 0;
+            out->nis = 0.0;
+            out->logdet = 0.0;
         }
         return;
     }
@@ -378,6 +390,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     double* yt = Cb + BATCH_L * 6;    // yTilde
     double* z = yt + BATCH_MAXM;      // L^-1 yTilde
     double* gam = z + BATCH_MAXM;     // Gamma
+    double* inn = gam + BATCH_NMAX;   // NIS, log det S (the region's last three doubles are not Gamma's)
     if (tid < M2) {
         const int i = s_mlm[tid], j = s_mj[tid];
         const MeasOut o = measure_one(chart, in.cam, ld3(L0, L, i), ldq(L0 + BATCH_QQ * L, L, i), L0[BATCH_QA * L + i], in.y[2 * j], in.y[2 * j + 1], star != 0,
@@ -449,6 +462,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
             out->N = N2;
             out->cur = cur;
             out->invalid = 0;
+            out->dof = m;
+            out->nis = out->logdet = __builtin_nan("");
         }
         return;
     }
@@ -515,6 +530,22 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         if (!(g - g == 0.0))
             s_misc[2] = 2;
     }
+    // The innovation statistics, from what the solve left in LDS: NIS = |z|^2 (wave 0) and log det S = 2 sum log L_kk (wave 1), over the true m rows. Lane l
+    // adds its entries l, l + 64 in ascending order, then the wave's butterfly: the order depends on m alone, not on the workgroup or the step's slot count.
+    if (tid < 128) {
+        const int lane = tid & 63;
+        double v = 0.0;
+        if (tid < 64) {
+            for (int k = lane; k < m; k += 64)
+                v += z[k] * z[k];
+        } else {
+            for (int k = lane; k < m; k += 64)
+                v += log(Sp[bt_tri(k, k)]);
+        }
+        v = batch_wave_sum(v);
+        if (lane == 0)
+            inn[tid >> 6] = tid < 64 ? v : 2.0 * v;
+    }
     __syncthreads();
     if (s_misc[2]) {
         if (tid == 0) {
@@ -522,6 +553,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
             out->N = N2;
             out->cur = cur;
             out->invalid = 0;
+            out->dof = m;
+            out->nis = out->logdet = __builtin_nan("");
         }
         return;
     }
@@ -595,6 +628,9 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         out->cur = N3 < N2 ? nxt : cur;
         out->invalid = s_mask;
         out->did |= BATCH_DID_UPDATE | (N3 < N2 ? BATCH_DID_INVALID : 0);
+        out->dof = m;
+        out->nis = inn[0];
+        out->logdet = inn[1];
     }
 }
 

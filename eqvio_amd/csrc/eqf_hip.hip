@@ -4032,6 +4032,10 @@ struct eqf_batch {
         int flags = 0;
         double depth = 0.0;
         long nees_lu = 0; // eqf_batch_nees entries answered by the partial-pivot fallback
+        int inn_dof = 0;  // the last step's innovation statistics (eqf_batch_last_innovation)
+        double inn_nis = 0.0, inn_logdet = 0.0;
+        long tot_updates = 0, tot_dof = 0; // their sums over the steps that carried EQF_BATCH_UPDATED, in step order (eqf_batch_innovation_totals)
+        double tot_nis = 0.0, tot_logdet = 0.0;
         eqvio_settings set{}; // the slot's own settings (eqf_batch_set_slot_settings; eqf_batch_create's until then)
         BatchSlotSet ss{};    // what the kernels read of them: copied into the slot's packet entry of every step
     };
@@ -4519,8 +4523,54 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         sl.cur = o.cur;
         sl.flags = flags;
         sl.depth = o.depth;
+        sl.inn_dof = o.dof;
+        sl.inn_nis = o.nis;
+        sl.inn_logdet = o.logdet;
+        if (flags & EQF_BATCH_UPDATED) {
+            sl.tot_updates += 1;
+            sl.tot_dof += o.dof;
+            sl.tot_nis += o.nis;
+            sl.tot_logdet += o.logdet;
+        }
         if ((int)sl.ids.size() != o.N)
             status[e] = EQF_E_BAD_ARG; // bookkeeping disagreement: cannot happen
+    }
+    return 0;
+}
+
+int eqf_batch_last_innovation(const eqf_batch* b, int slot, int* dof, double* nis, double* logdet) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    const eqf_batch::Slot& sl = b->s[slot];
+    if (dof)
+        *dof = sl.inn_dof;
+    if (nis)
+        *nis = sl.inn_nis;
+    if (logdet)
+        *logdet = sl.inn_logdet;
+    return 0;
+}
+int eqf_batch_innovation_totals(const eqf_batch* b, int slot, long* updates, long* dof, double* nis, double* logdet) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    const eqf_batch::Slot& sl = b->s[slot];
+    if (updates)
+        *updates = sl.tot_updates;
+    if (dof)
+        *dof = sl.tot_dof;
+    if (nis)
+        *nis = sl.tot_nis;
+    if (logdet)
+        *logdet = sl.tot_logdet;
+    return 0;
+}
+int eqf_batch_reset_innovation_totals(eqf_batch* b, int slot) {
+    if (!b || slot >= b->slots)
+        return EQF_E_BAD_ARG;
+    for (int k = slot < 0 ? 0 : slot; k < (slot < 0 ? b->slots : slot + 1); ++k) {
+        eqf_batch::Slot& sl = b->s[k];
+        sl.tot_updates = sl.tot_dof = 0;
+        sl.tot_nis = sl.tot_logdet = 0.0;
     }
     return 0;
 }

@@ -87,6 +87,11 @@ eqvio_settings VIOFilterBatch::slotSettings(int k) const {
     check(eqf_batch_get_slot_settings(batch, k, &s), "eqf_batch_get_slot_settings");
     return s;
 }
+VIOFilterBatch::InnovationTotals VIOFilterBatch::innovationTotals(int k) const {
+    InnovationTotals t;
+    check(eqf_batch_innovation_totals(batch, k, &t.updates, &t.dof, &t.nis, &t.logdet), "eqf_batch_innovation_totals");
+    return t;
+}
 // VIOFilter(const Settings&) (VIOFilter.cpp:31-41) with the slot's settings: xi0 with the camera offset, X = identity, Sigma = the initial sensor covariance
 void VIOFilterBatch::resetSlot(int k) {
     const eqvio_settings s = slotSettings(k);
@@ -336,6 +341,13 @@ int eqvio_batch_set_slot_settings(eqvio_batch* b, int slot, const eqvio_settings
 int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out) {
     return b ? eqf_batch_get_slot_settings(b->f->core(), slot, out) : EQF_E_BAD_ARG;
 }
+int eqvio_batch_last_innovation(const eqvio_batch* b, int slot, int* dof, double* nis, double* logdet) {
+    return b ? eqf_batch_last_innovation(b->f->core(), slot, dof, nis, logdet) : EQF_E_BAD_ARG;
+}
+int eqvio_batch_innovation_totals(const eqvio_batch* b, int slot, long* updates, long* dof, double* nis, double* logdet) {
+    return b ? eqf_batch_innovation_totals(b->f->core(), slot, updates, dof, nis, logdet) : EQF_E_BAD_ARG;
+}
+int eqvio_batch_reset_innovation_totals(eqvio_batch* b, int slot) { return b ? eqf_batch_reset_innovation_totals(b->f->core(), slot) : EQF_E_BAD_ARG; }
 int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count) {
     if (!b || !per_slot || first < 0 || count < 0)
         return EQF_E_BAD_ARG;

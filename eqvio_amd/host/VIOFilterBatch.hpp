@@ -43,7 +43,16 @@ class VIOFilterBatch {
                            const double* y_all, int* status);
     // the same for measurements already built (a replay's VisionMeasurement objects): one device step for every listed slot
     void processVisionData(int count, const int* slots, const VisionMeasurement* const* meas, int* status);
+    // the innovation statistics of the slot's updated steps since the last reset (eqf_batch_innovation_totals: the numbers are the device batch's)
+    struct InnovationTotals {
+        long updates = 0, dof = 0;
+        double nis = 0, logdet = 0;
+        double meanNisPerDof() const { return nis / (double)dof; }
+        double logLikelihood() const { return -0.5 * (nis + logdet + (double)dof * 1.8378770664093453); } // ln 2 pi
+    };
+    InnovationTotals innovationTotals(int slot) const;
     eqf_batch* core() { return batch; }
+    const eqf_batch* core() const { return batch; }
     Slot& slot(int k) { return slotv.at(k); }
     const Slot& slot(int k) const { return slotv.at(k); }
     int slots() const { return (int)slotv.size(); }

@@ -2,9 +2,13 @@
 // a YAML file (VIOFilterSettings.h:126-174); yaml-cpp is not in this image, so every key is a --flag of the same name.
 #pragma once
 #include "VIOFilter.hpp"
+#include "eqf_batch.h"
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <string>
+#include <vector>
 
 namespace eqvio_amd {
 
@@ -62,6 +66,120 @@ inline bool parseFilterFlag(const std::string& a, const std::function<const char
         return true;
     }
     return false;
+}
+
+// ---- what the two mains share of --batch B --sweep NAME=v0,...: the settings as the C-ABI's struct, one of its fields by name, the refusals
+
+// --sweep NAME=v0,v1,...: one field of eqvio_settings by its name, one value per slot
+struct Sweep {
+    std::string name;
+    std::vector<std::string> values;
+};
+// the argument of --sweep: NAME=v0,v1,... (no '=': a name without values, which sweepRefusal refuses)
+inline Sweep parseSweep(const std::string& v) {
+    Sweep sweep;
+    const size_t eq = v.find('=');
+    sweep.name = v.substr(0, eq);
+    for (size_t p = eq == std::string::npos ? v.size() : eq + 1; p <= v.size() && eq != std::string::npos;) {
+        const size_t c = std::min(v.find(',', p), v.size());
+        sweep.values.push_back(v.substr(p, c - p));
+        p = c + 1;
+    }
+    return sweep;
+}
+inline bool setSettingsField(eqvio_settings& es, const std::string& name, const std::string& value, std::string& why) {
+    struct D { const char* name; double eqvio_settings::*p; };
+    static const D doubles[] = {
+        {"biasOmegaProcessVariance", &eqvio_settings::biasOmegaProcessVariance}, {"biasAccelProcessVariance", &eqvio_settings::biasAccelProcessVariance},
+        {"attitudeProcessVariance", &eqvio_settings::attitudeProcessVariance}, {"positionProcessVariance", &eqvio_settings::positionProcessVariance},
+        {"velocityProcessVariance", &eqvio_settings::velocityProcessVariance}, {"cameraAttitudeProcessVariance", &eqvio_settings::cameraAttitudeProcessVariance},
+        {"cameraPositionProcessVariance", &eqvio_settings::cameraPositionProcessVariance}, {"pointProcessVariance", &eqvio_settings::pointProcessVariance},
+        {"velGyrNoise", &eqvio_settings::velGyrNoise}, {"velAccNoise", &eqvio_settings::velAccNoise},
+        {"velGyrBiasWalk", &eqvio_settings::velGyrBiasWalk}, {"velAccBiasWalk", &eqvio_settings::velAccBiasWalk},
+        {"measurementNoise", &eqvio_settings::measurementNoise}, {"outlierThresholdAbs", &eqvio_settings::outlierThresholdAbs},
+        {"outlierThresholdProb", &eqvio_settings::outlierThresholdProb}, {"featureRetention", &eqvio_settings::featureRetention},
+        {"initialAttitudeVariance", &eqvio_settings::initialAttitudeVariance}, {"initialPositionVariance", &eqvio_settings::initialPositionVariance},
+        {"initialVelocityVariance", &eqvio_settings::initialVelocityVariance}, {"initialCameraAttitudeVariance", &eqvio_settings::initialCameraAttitudeVariance},
+        {"initialCameraPositionVariance", &eqvio_settings::initialCameraPositionVariance}, {"initialPointVariance", &eqvio_settings::initialPointVariance},
+        {"initialPointDepthVariance", &eqvio_settings::initialPointDepthVariance}, {"initialBiasOmegaVariance", &eqvio_settings::initialBiasOmegaVariance},
+        {"initialBiasAccelVariance", &eqvio_settings::initialBiasAccelVariance}, {"initialSceneDepth", &eqvio_settings::initialSceneDepth},
+    };
+    struct I { const char* name; int eqvio_settings::*p; };
+    static const I ints[] = {
+        {"useDiscreteInnovationLift", &eqvio_settings::useDiscreteInnovationLift}, {"useDiscreteVelocityLift", &eqvio_settings::useDiscreteVelocityLift},
+        {"useDiscreteStateMatrix", &eqvio_settings::useDiscreteStateMatrix}, {"fastRiccati", &eqvio_settings::fastRiccati},
+        {"useMedianDepth", &eqvio_settings::useMedianDepth}, {"useFeaturePredictions", &eqvio_settings::useFeaturePredictions},
+        {"useEquivariantOutput", &eqvio_settings::useEquivariantOutput}, {"removeLostLandmarks", &eqvio_settings::removeLostLandmarks},
+    };
+    char* end = nullptr;
+    for (const D& d : doubles)
+        if (name == d.name) {
+            es.*(d.p) = std::strtod(value.c_str(), &end);
+            if (value.empty() || *end)
+                why = "--sweep " + name + ": '" + value + "' is not a number";
+            return true;
+        }
+    for (const I& i : ints)
+        if (name == i.name) {
+            es.*(i.p) = (int)std::strtol(value.c_str(), &end, 10);
+            if (value.empty() || *end)
+                why = "--sweep " + name + ": '" + value + "' is not an integer";
+            return true;
+        }
+    if (name == "coordinateChoice") { // by name, or the enum's number; which charts the batch takes is eqf_batch_check_settings's to say
+        const char* charts[3] = {"Euclidean", "InvDepth", "Normal"};
+        const int enums[3] = {EQVIO_COORD_EUCLIDEAN, EQVIO_COORD_INVDEPTH, EQVIO_COORD_NORMAL};
+        const size_t c = std::find(charts, charts + 3, value) - charts;
+        es.coordinateChoice = c < 3 ? enums[c] : (int)std::strtol(value.c_str(), &end, 10);
+        if (c == 3 && (value.empty() || *end))
+            why = "--sweep coordinateChoice: '" + value + "' is neither Euclidean, InvDepth nor a number";
+        return true;
+    }
+    return false;
+}
+// what --sweep is refused for, before any device is opened (empty: nothing). es: the settings of the run without the swept field. Whether the batch takes
+// slot k's settings is asked of the batch (eqf_batch_check_settings), not restated here.
+inline std::string sweepRefusal(const Sweep& sw, int B, const eqvio_settings& es) {
+    if (sw.name.empty() || sw.values.empty())
+        return "--sweep needs NAME=v0,v1,...";
+    for (const std::string& v : sw.values) {
+        eqvio_settings ek = es;
+        std::string why;
+        if (!setSettingsField(ek, sw.name, v, why))
+            return "--sweep: '" + sw.name + "' is not a field of eqvio_settings";
+        if (!why.empty())
+            return why;
+        if (const int rc = eqf_batch_check_settings(&ek))
+            return "--sweep " + sw.name + "=" + v + ": the batch refuses these settings (" + eqf_error_string(rc) + ")";
+    }
+    if ((int)sw.values.size() != B)
+        return "--sweep has " + std::to_string(sw.values.size()) + " values for --batch " + std::to_string(B) + ": one value per slot";
+    return "";
+}
+
+// the filter settings as the C-ABI's eqvio_settings
+inline eqvio_settings batchSettings(const VIOFilter::Settings& fs) {
+    eqvio_settings es;
+    std::memset(&es, 0, sizeof(es));
+    es.biasOmegaProcessVariance = fs.biasOmegaProcessVariance, es.biasAccelProcessVariance = fs.biasAccelProcessVariance;
+    es.attitudeProcessVariance = fs.attitudeProcessVariance, es.positionProcessVariance = fs.positionProcessVariance;
+    es.velocityProcessVariance = fs.velocityProcessVariance, es.cameraAttitudeProcessVariance = fs.cameraAttitudeProcessVariance;
+    es.cameraPositionProcessVariance = fs.cameraPositionProcessVariance, es.pointProcessVariance = fs.pointProcessVariance;
+    es.velGyrNoise = fs.velGyrNoise, es.velAccNoise = fs.velAccNoise, es.velGyrBiasWalk = fs.velGyrBiasWalk, es.velAccBiasWalk = fs.velAccBiasWalk;
+    es.measurementNoise = fs.measurementNoise, es.outlierThresholdAbs = fs.outlierThresholdAbs, es.outlierThresholdProb = fs.outlierThresholdProb;
+    es.featureRetention = fs.featureRetention;
+    es.initialAttitudeVariance = fs.initialAttitudeVariance, es.initialPositionVariance = fs.initialPositionVariance;
+    es.initialVelocityVariance = fs.initialVelocityVariance, es.initialCameraAttitudeVariance = fs.initialCameraAttitudeVariance;
+    es.initialCameraPositionVariance = fs.initialCameraPositionVariance, es.initialPointVariance = fs.initialPointVariance;
+    es.initialPointDepthVariance = fs.initialPointDepthVariance, es.initialBiasOmegaVariance = fs.initialBiasOmegaVariance;
+    es.initialBiasAccelVariance = fs.initialBiasAccelVariance, es.initialSceneDepth = fs.initialSceneDepth;
+    es.useDiscreteInnovationLift = fs.useDiscreteInnovationLift, es.useDiscreteVelocityLift = fs.useDiscreteVelocityLift;
+    es.useDiscreteStateMatrix = fs.useDiscreteStateMatrix, es.fastRiccati = fs.fastRiccati, es.useMedianDepth = fs.useMedianDepth;
+    es.useFeaturePredictions = fs.useFeaturePredictions, es.useEquivariantOutput = fs.useEquivariantOutput, es.removeLostLandmarks = fs.removeLostLandmarks;
+    es.coordinateChoice = (int)fs.coordinateChoice;
+    const double offset[7] = {fs.cameraOffset.R.w, fs.cameraOffset.R.x, fs.cameraOffset.R.y, fs.cameraOffset.R.z, fs.cameraOffset.x.x, fs.cameraOffset.x.y, fs.cameraOffset.x.z};
+    std::memcpy(es.cameraOffset, offset, sizeof(offset));
+    return es;
 }
 
 } // namespace eqvio_amd

@@ -1,7 +1,10 @@
 // eqvio_opt: the reference's dataset main (src/main_opt.cpp:178-269) on the MI355X EqF path, fed by precomputed feature
 // tracks instead of images (no OpenCV / GIFT here): IMU -> processIMUData, tracks -> processVisionData, outputs through
 // VIOWriter. The filter starts uninitialised and sets its attitude from the first IMU sample (VIOFilter.cpp:65-78).
+// --batch B [--sweep NAME=v0,...] replays the dataset in the B slots of one filter batch (VIOFilterBatch.hpp), slot k with the k-th value, and scores every
+// slot by its innovation statistics (include/eqf_batch.h): a tuning sweep on a dataset without landmark truth.
 #include "DatasetReplay.hpp"
+#include "VIOFilterBatch.hpp"
 #include "VIOWriter.hpp"
 #include "cli.hpp"
 #include <chrono>
@@ -17,7 +20,76 @@ static void usage() {
               "                 [--cameraFile sensor.yaml | camchain.yaml]   (intrinsics, distortion and camera offset from the dataset's own file, main_opt.cpp:114-147)\n"
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)");
+              "                 [--batch B [--sweep NAME=v0,v1,...]]\n"
+              "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
+              "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
+              "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
+              "              (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood. Needs --fastRiccati 1 and at most 64\n"
+              "              features per frame; --output, --dumpStates and --sigmaFP32 are refused.\n"
+              "  --sweep NAME=v0,...,v(B-1)   with --batch B: slot k runs with the filter setting NAME (a field of eqvio_settings) at value vk. Needs exactly B values.");
+}
+
+// --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
+static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, double startTime, double stopTime) {
+    const bool swept = !sweep.name.empty();
+    const eqvio_settings es = batchSettings(fs);
+    eqf_batch* core = nullptr;
+    if (const int rc = eqf_batch_create(&core, fs.device, B, EQF_BATCH_MAX_LANDMARKS, &es)) {
+        std::fprintf(stderr, "eqvio_opt: eqf_batch_create: %s\n", eqf_error_string(rc));
+        return 1;
+    }
+    VIOFilterBatch filters(core); // every slot as VIOFilter(fs): it initialises itself from its first IMU sample
+    for (int k = 0; k < B && swept; ++k) {
+        eqvio_settings ek = es;
+        std::string why;
+        setSettingsField(ek, sweep.name, sweep.values[k], why);
+        if (const int rc = filters.setSlotSettings(k, ek))
+            throw std::runtime_error("--sweep " + sweep.name + "=" + sweep.values[k] + ": " + eqf_error_string(rc));
+    }
+    std::vector<int> slots(B), status(B), failed(B, 0);
+    for (int k = 0; k < B; ++k)
+        slots[k] = k;
+    int imuDataCounter = 0, visionDataCounter = 0;
+    const auto loopStartTime = std::chrono::steady_clock::now();
+    while (true) {
+        const MeasurementType measType = dataServer.nextMeasurementType();
+        if (measType == MeasurementType::None)
+            break;
+        if (measType == MeasurementType::Image) {
+            const VisionMeasurement measData = dataServer.getSimVision();
+            if (startTime > 0 && measData.stamp < startTime)
+                continue;
+            const std::vector<const VisionMeasurement*> meas(B, &measData);
+            filters.processVisionData(B, slots.data(), meas.data(), status.data()); // one device step for all slots
+            for (int k = 0; k < B; ++k) {
+                if (status[k] == EQF_E_NOT_SPD || status[k] == EQF_E_NONFINITE)
+                    ++failed[k]; // this tuning's update failed on this frame: the slot goes on without it, the others are not affected
+                else if (status[k] != 0)
+                    throw std::runtime_error("slot " + std::to_string(k) + ", stamp " + std::to_string(measData.stamp) + ": " + eqf_error_string(status[k]));
+            }
+            ++visionDataCounter;
+        } else {
+            const IMUVelocity imuData = dataServer.getIMU();
+            if (startTime > 0 && imuData.stamp < startTime)
+                continue;
+            for (int k = 0; k < B; ++k)
+                filters.processIMUData(k, imuData);
+            ++imuDataCounter;
+        }
+        if (stopTime > 0 && filters.slot(0).currentTime > stopTime)
+            break;
+    }
+    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopStartTime).count();
+    std::cout << "Processed " << imuDataCounter << " IMU and " << visionDataCounter << " vision measurements in " << B << " slots.\n"
+              << "Time taken: " << elapsed << " seconds." << std::endl;
+    for (int k = 0; k < B; ++k) {
+        const VIOFilterBatch::InnovationTotals t = filters.innovationTotals(k);
+        const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
+        std::printf("slot %d%s: frames updated %ld  failed %d  mean NIS/dof %.9g  log-likelihood %.9g\n", k, what.c_str(), t.updates, failed[k], t.meanNisPerDof(),
+                    t.logLikelihood());
+    }
+    std::printf("batch of %d slots: slots x vision updates/s %.1f\n", B, (double)B * visionDataCounter / elapsed);
+    return 0;
 }
 
 int main(int argc, char** argv) {
@@ -32,7 +104,9 @@ int main(int argc, char** argv) {
     cam->c.width = 752;
     cam->c.height = 480;
     double cameraLag = 0, startTime = -1, stopTime = -1;
-    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false;
+    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false;
+    int batch = 0;
+    Sweep sweep;
     try {
         for (int i = 1; i < argc; ++i) {
             const std::string a = argv[i];
@@ -83,9 +157,32 @@ int main(int argc, char** argv) {
             else if (a == "--sigmaFP32") sigmaFP32 = true;
             else if (a == "--dumpMeasurements") dump = true;
             else if (a == "--printCamera") printCamera = true;
+            else if (a == "--batch") batch = std::atoi(val());
+            else if (a == "--sweep") {
+                sweep = parseSweep(val());
+                haveSweep = true;
+            }
             else if (!parseFilterFlag(a, val, fs)) {
                 usage();
                 return a == "--help" ? 0 : 2;
+            }
+        }
+        if (haveSweep && batch == 0) {
+            std::fprintf(stderr, "eqvio_opt: --sweep needs --batch B (one value per slot)\n");
+            return 2;
+        }
+        if (batch != 0) { // what the filter batch refuses, before any file or device is opened
+            std::string why = batch < 1 ? "needs B >= 1"
+                              : !fs.fastRiccati ? "needs --fastRiccati 1 (the batch has fast Riccati only; the default is 0)"
+                              : !outputDir.empty() ? "does not support --output"
+                              : !statesName.empty() ? "does not support --dumpStates"
+                              : sigmaFP32 ? "does not support --sigmaFP32"
+                              : "";
+            if (why.empty() && haveSweep)
+                why = sweepRefusal(sweep, batch, batchSettings(fs));
+            if (!why.empty()) {
+                std::fprintf(stderr, "eqvio_opt: --batch %d: %s\n", batch, why.c_str());
+                return 2;
             }
         }
         if (imuName.empty() || featName.empty()) {
@@ -128,6 +225,8 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
+        if (batch != 0)
+            return runBatch(dataServer, fs, batch, sweep, startTime, stopTime);
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150
         if (sigmaFP32) // BASELINE config 5: Sigma stored as float in HBM (include/eqf_hip.h)

@@ -22,7 +22,7 @@ static void usage() {
     std::puts("usage: eqvio_sim [--duration S] [--trajectory wave|square|sine|line] [--numPoints N] [--numWalls W] [--wallDistance D]\n"
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
               "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
-              "                 [--sweep NAME=v0,v1,...]\n"
+              "                 [--sweep NAME=v0,v1,...] [--innovation]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
               "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
@@ -30,111 +30,14 @@ static void usage() {
               "              --output are refused.\n"
               "  --sweep NAME=v0,...,v(B-1)   with --batch B: runs the SAME seed (--seed) in every slot, slot k with the filter setting NAME (a field of\n"
               "              eqvio_settings: doubles, the 0 / 1 flags, coordinateChoice as Euclidean|InvDepth) at value vk, and prints each run's value and\n"
-              "              mean NEES. The simulated data are those of the unswept settings. Needs exactly B values.");
-}
-
-// --sweep NAME=v0,v1,...: one field of eqvio_settings by its name, one value per slot
-struct Sweep {
-    std::string name;
-    std::vector<std::string> values;
-};
-static bool setSettingsField(eqvio_settings& es, const std::string& name, const std::string& value, std::string& why) {
-    struct D { const char* name; double eqvio_settings::*p; };
-    static const D doubles[] = {
-        {"biasOmegaProcessVariance", &eqvio_settings::biasOmegaProcessVariance}, {"biasAccelProcessVariance", &eqvio_settings::biasAccelProcessVariance},
-        {"attitudeProcessVariance", &eqvio_settings::attitudeProcessVariance}, {"positionProcessVariance", &eqvio_settings::positionProcessVariance},
-        {"velocityProcessVariance", &eqvio_settings::velocityProcessVariance}, {"cameraAttitudeProcessVariance", &eqvio_settings::cameraAttitudeProcessVariance},
-        {"cameraPositionProcessVariance", &eqvio_settings::cameraPositionProcessVariance}, {"pointProcessVariance", &eqvio_settings::pointProcessVariance},
-        {"velGyrNoise", &eqvio_settings::velGyrNoise}, {"velAccNoise", &eqvio_settings::velAccNoise},
-        {"velGyrBiasWalk", &eqvio_settings::velGyrBiasWalk}, {"velAccBiasWalk", &eqvio_settings::velAccBiasWalk},
-        {"measurementNoise", &eqvio_settings::measurementNoise}, {"outlierThresholdAbs", &eqvio_settings::outlierThresholdAbs},
-        {"outlierThresholdProb", &eqvio_settings::outlierThresholdProb}, {"featureRetention", &eqvio_settings::featureRetention},
-        {"initialAttitudeVariance", &eqvio_settings::initialAttitudeVariance}, {"initialPositionVariance", &eqvio_settings::initialPositionVariance},
-        {"initialVelocityVariance", &eqvio_settings::initialVelocityVariance}, {"initialCameraAttitudeVariance", &eqvio_settings::initialCameraAttitudeVariance},
-        {"initialCameraPositionVariance", &eqvio_settings::initialCameraPositionVariance}, {"initialPointVariance", &eqvio_settings::initialPointVariance},
-        {"initialPointDepthVariance", &eqvio_settings::initialPointDepthVariance}, {"initialBiasOmegaVariance", &eqvio_settings::initialBiasOmegaVariance},
-        {"initialBiasAccelVariance", &eqvio_settings::initialBiasAccelVariance}, {"initialSceneDepth", &eqvio_settings::initialSceneDepth},
-    };
-    struct I { const char* name; int eqvio_settings::*p; };
-    static const I ints[] = {
-        {"useDiscreteInnovationLift", &eqvio_settings::useDiscreteInnovationLift}, {"useDiscreteVelocityLift", &eqvio_settings::useDiscreteVelocityLift},
-        {"useDiscreteStateMatrix", &eqvio_settings::useDiscreteStateMatrix}, {"fastRiccati", &eqvio_settings::fastRiccati},
-        {"useMedianDepth", &eqvio_settings::useMedianDepth}, {"useFeaturePredictions", &eqvio_settings::useFeaturePredictions},
-        {"useEquivariantOutput", &eqvio_settings::useEquivariantOutput}, {"removeLostLandmarks", &eqvio_settings::removeLostLandmarks},
-    };
-    char* end = nullptr;
-    for (const D& d : doubles)
-        if (name == d.name) {
-            es.*(d.p) = std::strtod(value.c_str(), &end);
-            if (value.empty() || *end)
-                why = "--sweep " + name + ": '" + value + "' is not a number";
-            return true;
-        }
-    for (const I& i : ints)
-        if (name == i.name) {
-            es.*(i.p) = (int)std::strtol(value.c_str(), &end, 10);
-            if (value.empty() || *end)
-                why = "--sweep " + name + ": '" + value + "' is not an integer";
-            return true;
-        }
-    if (name == "coordinateChoice") { // by name, or the enum's number; which charts the batch takes is eqf_batch_check_settings's to say
-        const char* charts[3] = {"Euclidean", "InvDepth", "Normal"};
-        const int enums[3] = {EQVIO_COORD_EUCLIDEAN, EQVIO_COORD_INVDEPTH, EQVIO_COORD_NORMAL};
-        const size_t c = std::find(charts, charts + 3, value) - charts;
-        es.coordinateChoice = c < 3 ? enums[c] : (int)std::strtol(value.c_str(), &end, 10);
-        if (c == 3 && (value.empty() || *end))
-            why = "--sweep coordinateChoice: '" + value + "' is neither Euclidean, InvDepth nor a number";
-        return true;
-    }
-    return false;
-}
-// what --sweep is refused for, before any device is opened (empty: nothing). es: the settings of the run without the swept field. Whether the batch takes
-// slot k's settings is asked of the batch (eqf_batch_check_settings), not restated here.
-static std::string sweepRefusal(const Sweep& sw, int B, const eqvio_settings& es) {
-    if (sw.name.empty() || sw.values.empty())
-        return "--sweep needs NAME=v0,v1,...";
-    for (const std::string& v : sw.values) {
-        eqvio_settings ek = es;
-        std::string why;
-        if (!setSettingsField(ek, sw.name, v, why))
-            return "--sweep: '" + sw.name + "' is not a field of eqvio_settings";
-        if (!why.empty())
-            return why;
-        if (const int rc = eqf_batch_check_settings(&ek))
-            return "--sweep " + sw.name + "=" + v + ": the batch refuses these settings (" + eqf_error_string(rc) + ")";
-    }
-    if ((int)sw.values.size() != B)
-        return "--sweep has " + std::to_string(sw.values.size()) + " values for --batch " + std::to_string(B) + ": one value per slot";
-    return "";
-}
-
-// the filter settings as the C-ABI's eqvio_settings
-static eqvio_settings batchSettings(const VIOFilter::Settings& fs) {
-    eqvio_settings es;
-    std::memset(&es, 0, sizeof(es));
-    es.biasOmegaProcessVariance = fs.biasOmegaProcessVariance, es.biasAccelProcessVariance = fs.biasAccelProcessVariance;
-    es.attitudeProcessVariance = fs.attitudeProcessVariance, es.positionProcessVariance = fs.positionProcessVariance;
-    es.velocityProcessVariance = fs.velocityProcessVariance, es.cameraAttitudeProcessVariance = fs.cameraAttitudeProcessVariance;
-    es.cameraPositionProcessVariance = fs.cameraPositionProcessVariance, es.pointProcessVariance = fs.pointProcessVariance;
-    es.velGyrNoise = fs.velGyrNoise, es.velAccNoise = fs.velAccNoise, es.velGyrBiasWalk = fs.velGyrBiasWalk, es.velAccBiasWalk = fs.velAccBiasWalk;
-    es.measurementNoise = fs.measurementNoise, es.outlierThresholdAbs = fs.outlierThresholdAbs, es.outlierThresholdProb = fs.outlierThresholdProb;
-    es.featureRetention = fs.featureRetention;
-    es.initialAttitudeVariance = fs.initialAttitudeVariance, es.initialPositionVariance = fs.initialPositionVariance;
-    es.initialVelocityVariance = fs.initialVelocityVariance, es.initialCameraAttitudeVariance = fs.initialCameraAttitudeVariance;
-    es.initialCameraPositionVariance = fs.initialCameraPositionVariance, es.initialPointVariance = fs.initialPointVariance;
-    es.initialPointDepthVariance = fs.initialPointDepthVariance, es.initialBiasOmegaVariance = fs.initialBiasOmegaVariance;
-    es.initialBiasAccelVariance = fs.initialBiasAccelVariance, es.initialSceneDepth = fs.initialSceneDepth;
-    es.useDiscreteInnovationLift = fs.useDiscreteInnovationLift, es.useDiscreteVelocityLift = fs.useDiscreteVelocityLift;
-    es.useDiscreteStateMatrix = fs.useDiscreteStateMatrix, es.fastRiccati = fs.fastRiccati, es.useMedianDepth = fs.useMedianDepth;
-    es.useFeaturePredictions = fs.useFeaturePredictions, es.useEquivariantOutput = fs.useEquivariantOutput, es.removeLostLandmarks = fs.removeLostLandmarks;
-    es.coordinateChoice = (int)fs.coordinateChoice;
-    const double offset[7] = {fs.cameraOffset.R.w, fs.cameraOffset.R.x, fs.cameraOffset.R.y, fs.cameraOffset.R.z, fs.cameraOffset.x.x, fs.cameraOffset.x.y, fs.cameraOffset.x.z};
-    std::memcpy(es.cameraOffset, offset, sizeof(offset));
-    return es;
+              "              mean NEES. The simulated data are those of the unswept settings. Needs exactly B values.\n"
+              "  --innovation   with --batch B: behind those lines, one line per run with the number of vision updates, the mean normalised innovation\n"
+              "              squared per degree of freedom (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood\n"
+              "              (eqvio_batch_innovation_totals). Needs no true state, unlike NEES.");
 }
 
 // --batch B: the default-mode loop of main() for B seeds in lockstep, through eqvio_batch_run_sim (augment, vision step and NEES: one launch each per frame)
-static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep) {
+static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep, bool innovation) {
     const bool swept = !sweep.name.empty();
     eqvio_sim_settings ss;
     eqvio_sim_default_settings(&ss);
@@ -212,6 +115,13 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
             std::printf("run %d seed %u: mean NEES %.9g over %d frames\n", k, sim.randomSeed + (unsigned)k, mean, n);
     }
     std::printf("batch of %d runs: mean of the runs' mean NEES %.9g  frames %d  runs x frames/s %.1f\n", B, sumOfMeans / B, frames, (double)B * frames / elapsed);
+    for (int k = 0; k < B && innovation; ++k) { // the slot's totals over the whole run: every slot starts with none
+        long updates = 0, dof = 0;
+        double nis = 0, logdet = 0;
+        eqvio_batch_innovation_totals(b, k, &updates, &dof, &nis, &logdet);
+        std::printf("innovation run %d: updates %ld  mean NIS/dof %.9g  log-likelihood %.9g\n", k, updates, nis / (double)dof,
+                    -0.5 * (nis + logdet + (double)dof * std::log(2.0 * M_PI)));
+    }
     eqvio_batch_destroy(b);
     release();
     return 0;
@@ -221,7 +131,7 @@ int main(int argc, char** argv) {
     SimSettings sim;
     sim.duration = 20.0;
     VIOFilter::Settings fs;
-    bool fullState = false, quiet = false, sigmaFP32 = false;
+    bool fullState = false, quiet = false, sigmaFP32 = false, innovation = false;
     double landmarkResetTime = -1.0;
     int batch = 0;
     Sweep sweep;
@@ -255,16 +165,10 @@ int main(int argc, char** argv) {
         else if (a == "--quiet") quiet = true;
         else if (a == "--sigmaFP32") sigmaFP32 = true;
         else if (a == "--batch") batch = std::atoi(val());
+        else if (a == "--innovation") innovation = true;
         else if (a == "--sweep") {
-            const std::string v = val();
+            sweep = parseSweep(val());
             haveSweep = true;
-            const size_t eq = v.find('=');
-            sweep.name = v.substr(0, eq);
-            for (size_t p = eq == std::string::npos ? v.size() : eq + 1; p <= v.size() && eq != std::string::npos;) {
-                const size_t c = std::min(v.find(',', p), v.size());
-                sweep.values.push_back(v.substr(p, c - p));
-                p = c + 1;
-            }
         }
         else if (parseFilterFlag(a, val, fs)) {
         } else {
@@ -274,6 +178,10 @@ int main(int argc, char** argv) {
     }
     if (haveSweep && batch == 0) {
         std::fprintf(stderr, "eqvio_sim: --sweep needs --batch B (one value per slot)\n");
+        return 2;
+    }
+    if (innovation && batch == 0) {
+        std::fprintf(stderr, "eqvio_sim: --innovation needs --batch B (the statistics are the filter batch's)\n");
         return 2;
     }
     if (batch != 0) { // what the filter batch refuses, before any device is opened
@@ -298,7 +206,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        return runBatch(sim, fs, batch, quiet, sweep);
+        return runBatch(sim, fs, batch, quiet, sweep, innovation);
     }
     double lastLandmarkReset = landmarkResetTime > 0 ? 0.0 : std::nan("");
 

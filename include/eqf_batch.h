@@ -96,6 +96,25 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
 /* flags (EQF_BATCH_*) of the slot's last step, and the depth its new landmarks got */
 int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth);
 
+/* Innovation statistics of the slot's last step, taken from the factorisation the update does anyway (no extra launch, copy or synchronisation):
+ *   dof     m, the rows of the matched measurement: two per feature left after removeOutliers, the features of new landmarks included;
+ *   nis     the normalised innovation squared yTilde^T S^-1 yTilde;
+ *   logdet  log det S,
+ * with S = C Sigma C^T + R the innovation covariance of performVisionUpdate, formed with the slot's own measurementNoise and useEquivariantOutput. The
+ * innovation log-likelihood is left to the caller: -1/2 (nis + logdet + dof ln 2 pi). What the last step leaves:
+ *   EQF_BATCH_UPDATED                    m, the values;
+ *   EQF_BATCH_EMPTY                      0, 0, 0;
+ *   EQF_E_NOT_SPD / EQF_E_NONFINITE      m, NaN, NaN (no update was applied);
+ *   refused before the launch (EQF_E_BAD_ARG, EQF_E_CAPACITY) or not listed: unchanged; a slot that never stepped has 0, 0, 0.
+ * A slot gives the same bits whichever step it is part of: the sums have a fixed order.
+ * The totals are the sums, formed on the host in step order, over the slot's steps that carried EQF_BATCH_UPDATED (failed and empty steps add nothing), and
+ * the number of those steps. Only eqf_batch_reset_innovation_totals (slot < 0: every slot) clears them: eqf_batch_set_state, _set_sigma and
+ * _set_slot_settings leave them, so a teacher-forced loop keeps its totals. Null output pointers are skipped. A null batch or a bad slot gives
+ * EQF_E_BAD_ARG; no device is looked at. */
+int eqf_batch_last_innovation(const eqf_batch* b, int slot, int* dof, double* nis, double* logdet);
+int eqf_batch_innovation_totals(const eqf_batch* b, int slot, long* updates, long* dof, double* nis, double* logdet);
+int eqf_batch_reset_innovation_totals(eqf_batch* b, int slot);
+
 /* One slot's true state for eqf_batch_nees: the 23 sensor doubles (eqvio_types.h layout) and n_true landmarks, ids in any order, camera-frame points. */
 typedef struct eqf_batch_truth {
     int slot;

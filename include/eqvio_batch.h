@@ -76,6 +76,12 @@ int eqvio_batch_sigma_dim(const eqvio_batch* b, int slot);
 int eqvio_batch_get_sigma(eqvio_batch* b, int slot, double* out_colmajor, int n);
 double eqvio_batch_get_time(const eqvio_batch* b, int slot);
 int eqvio_batch_is_initialised(const eqvio_batch* b, int slot);
+/* The innovation statistics of the slot's last step and their totals over the slot's updated steps (eqf_batch_last_innovation, _innovation_totals,
+ * _reset_innovation_totals, include/eqf_batch.h: same meaning, same codes; the numbers are the device batch's, kept nowhere else). A slot that sits a step
+ * out (stale stamp, ended sequence) adds nothing. For a score per slot of a replay: reset, eqvio_batch_run_prepared / _run_sim, read the totals. */
+int eqvio_batch_last_innovation(const eqvio_batch* b, int slot, int* dof, double* nis, double* logdet);
+int eqvio_batch_innovation_totals(const eqvio_batch* b, int slot, long* updates, long* dof, double* nis, double* logdet);
+int eqvio_batch_reset_innovation_totals(eqvio_batch* b, int slot); /* slot < 0: every slot */
 /* the device batch behind it */
 eqf_batch* eqvio_batch_core(eqvio_batch* b);
 
