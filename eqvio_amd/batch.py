@@ -63,6 +63,7 @@ def load_batch_protos():
         "eqf_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
         "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqf_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
+        "eqf_batch_copy_slots": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
     }
     fprotos = {
         "eqvio_batch_create": (C.c_int, [P(vp), P(Settings), C.c_int, C.c_int, C.c_int]),
@@ -89,6 +90,7 @@ def load_batch_protos():
         "eqvio_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
         "eqvio_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqvio_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
+        "eqvio_batch_copy_slots": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
     }
     for lib, protos in ((elib, eprotos), (flib, fprotos)):
         for name, (res, args) in protos.items():
@@ -271,6 +273,17 @@ class VIOFilterBatch:
         """Clears slot k's totals, or every slot's (k None)."""
         self._chk(self.lib.eqvio_batch_reset_innovation_totals(self.h, -1 if k is None else k))
 
+    def copy_slots(self, pairs):
+        """pairs: list of (src, dst). Slot dst becomes slot src as it was before the call - state, landmarks, Sigma, IMU buffer, time, initialised flag - in
+        ONE launch, without a transfer (eqvio_batch_copy_slots); any mapping goes in one call (fan-out, swap, cycle). dst keeps its own settings and innovation
+        totals. Returns the per-pair status codes (EQF_E_BAD_ARG: bad index, repeated destination, or a chart other than the source's while it holds
+        landmarks; that destination is untouched); raises BatchError when the call itself failed."""
+        n = len(pairs)
+        src, dst = _i32([p[0] for p in pairs]), _i32([p[1] for p in pairs])
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_copy_slots(self.h, n, _ip(src), _ip(dst), _ip(status)))
+        return [int(v) for v in status[:n]]
+
     def slot(self, k):
         if not 0 <= k < self.slots:
             raise IndexError(k)
@@ -289,6 +302,11 @@ class BatchSlot:
 
     def get_slot_settings(self):
         return self.b.get_slot_settings(self.k)
+
+    def copy_to(self, dsts):
+        """This slot into every slot of dsts (one slot or a list), one launch (VIOFilterBatch.copy_slots); returns the status codes."""
+        dsts = [dsts] if isinstance(dsts, (int, np.integer)) else list(dsts)
+        return self.b.copy_slots([(self.k, int(d)) for d in dsts])
 
     def process_imu(self, imu13):
         self.b.process_imu(self.k, imu13)

@@ -915,4 +915,58 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_augment(const AugArgs aa) {
     }
 }
 
+// eqf_batch_copy_slots (include/eqf_batch.h): entry e copies the live part of slot src's CURRENT buffer pair - the n x n of Sigma, n = 21 + 3 N, and the N live
+// entries of the 35 landmark planes - into slot dst's OTHER pair, which the host then names current. No launch of the batch reads a slot's other pair before it
+// has written it, so a copy never writes what this launch (or any entry of it) reads: a slot may be source and destination at once, and any mapping - fan-out,
+// swap, cycle - goes in one launch. Nothing outside the live part is copied, because nothing outside it is ever read: k_batch_frame gathers Sigma through
+// s_gidx and the planes through surv / s_keep (live indices only), k_batch_nees builds Z from r, c < n, k_batch_augment gathers through keep; the rows n .. ld and
+// the plane entries N .. 64 are whatever the buffer held.
+// Grid: x = entry, y = chunk of BATCH_COPY_COLS columns of Sigma (the last y also copies the planes); a block whose chunk starts at or behind column n has
+// nothing to do. 16-byte loads and stores: ld is even and every buffer 16-byte aligned, so a column starts on a 16-byte boundary and its rows go in pairs; an odd
+// n (or N) leaves one 8-byte element per column (plane). Blocks share nothing.
+struct CopyIn {
+    int src, scur; // source slot and its current pair
+    int dst, dnxt; // destination slot and its other pair
+    int N;         // the source's landmarks
+};
+struct CopyArgs {
+    int ld;
+    double* sig;
+    double* lm;
+    size_t sig_stride, lm_stride;
+    const CopyIn* in;
+};
+constexpr int BATCH_COPY_COLS = 16;
+constexpr int BATCH_COPY_CHUNKS = (BATCH_NMAX + BATCH_COPY_COLS - 1) / BATCH_COPY_COLS; // grid y
+// the 16-byte accesses: every plane and every buffer of planes starts at an even number of doubles (eqf_batch_copy_slots checks ld and the Sigma stride)
+static_assert(BATCH_L % 2 == 0 && (BATCH_PLANES * BATCH_L) % 2 == 0, "k_batch_copy moves pairs of doubles");
+__global__ void __launch_bounds__(BATCH_T) k_batch_copy(const CopyArgs ca) {
+    const CopyIn in = ca.in[blockIdx.x];
+    const int tid = threadIdx.x, L = BATCH_L, ld = ca.ld;
+    const int N = in.N, n = 21 + 3 * N;
+    const int c0 = blockIdx.y * BATCH_COPY_COLS, cols = min(BATCH_COPY_COLS, n - c0);
+    if (cols > 0) {
+        const double* S = ca.sig + (2 * (size_t)in.src + in.scur) * ca.sig_stride + (size_t)c0 * ld;
+        double* D = ca.sig + (2 * (size_t)in.dst + in.dnxt) * ca.sig_stride + (size_t)c0 * ld;
+        const int half = n >> 1; // >= 10
+        for (int t = tid; t < cols * half; t += BATCH_T) {
+            const size_t o = (size_t)(t / half) * ld + 2 * (t % half);
+            *reinterpret_cast<double2*>(D + o) = *reinterpret_cast<const double2*>(S + o);
+        }
+        if ((n & 1) && tid < cols)
+            D[(size_t)tid * ld + n - 1] = S[(size_t)tid * ld + n - 1];
+    }
+    if (blockIdx.y == gridDim.y - 1) {
+        const double* S = ca.lm + (2 * (size_t)in.src + in.scur) * ca.lm_stride;
+        double* D = ca.lm + (2 * (size_t)in.dst + in.dnxt) * ca.lm_stride;
+        const int half = N >> 1; // 0 for N <= 1: the loop does not run
+        for (int t = tid; t < BATCH_PLANES * half; t += BATCH_T) {
+            const int o = (t / half) * L + 2 * (t % half);
+            *reinterpret_cast<double2*>(D + o) = *reinterpret_cast<const double2*>(S + o);
+        }
+        if ((N & 1) && tid < BATCH_PLANES)
+            D[tid * L + N - 1] = S[tid * L + N - 1];
+    }
+}
+
 } // namespace eqf

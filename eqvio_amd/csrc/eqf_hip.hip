@@ -4050,7 +4050,8 @@ struct eqf_batch {
     NeesIn *h_nin = nullptr, *d_nin = nullptr; // eqf_batch_nees packets
     NeesOut *h_nout = nullptr, *d_nout = nullptr;
     AugIn *h_ain = nullptr, *d_ain = nullptr; // eqf_batch_augment packets
-    int nin_cap = 0, nout_cap = 0, aug_cap = 0;
+    CopyIn *h_cin = nullptr, *d_cin = nullptr; // eqf_batch_copy_slots packets
+    int nin_cap = 0, nout_cap = 0, aug_cap = 0, copy_cap = 0;
     std::vector<Slot> s;
 };
 
@@ -4230,6 +4231,9 @@ void eqf_batch_destroy(eqf_batch* b) {
         (void)hipHostFree(b->h_nout);
     if (b->h_ain)
         (void)hipHostFree(b->h_ain);
+    (void)hipFree(b->d_cin);
+    if (b->h_cin)
+        (void)hipHostFree(b->h_cin);
     if (b->stream)
         (void)hipStreamDestroy(b->stream);
     delete b;
@@ -4761,6 +4765,83 @@ int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* en
         eqf_batch::Slot& sl = b->s[entries[e].slot];
         sl.ids.swap(ids_after[e]);
         sl.cur ^= 1;
+    }
+    return 0;
+}
+
+// One launch for every accepted entry, one synchronisation. Everything that refuses an entry is decided on the host before the launch.
+int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst, int* status) {
+    if (!b || count < 0 || !src || !dst || !status)
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    std::vector<int> listed(b->slots, 0), in_of(count, -1);
+    int nin = 0;
+    for (int e = 0; e < count; ++e) {
+        status[e] = 0;
+        if (!batch_slot_ok(b, src[e]) || !batch_slot_ok(b, dst[e]) || listed[dst[e]]) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        const eqf_batch::Slot &from = b->s[src[e]], &to = b->s[dst[e]];
+        if (!from.ids.empty() && to.set.coordinateChoice != from.set.coordinateChoice) {
+            status[e] = EQF_E_BAD_ARG; // the source's Sigma is in its own chart's coordinates (eqf_batch_set_slot_settings's rule)
+            continue;
+        }
+        listed[dst[e]] = 1;
+        if (src[e] != dst[e])
+            in_of[e] = nin++;
+    }
+    if (nin == 0)
+        return 0;
+    if (b->ld % 2 || b->sig_stride % 2 || b->lm_stride % 2)
+        return EQF_E_BAD_ARG; // k_batch_copy moves pairs of doubles: a column, a plane and a buffer must start on 16 bytes (pick_ld gives an even ld today)
+    BatchDevice dev(b);
+    if (int rc = batch_grow_pair(b->h_cin, b->d_cin, b->copy_cap, nin))
+        return rc;
+    // the sources' host halves as they are BEFORE the call: a slot may be a destination of one entry and the source of another
+    struct HostHalf {
+        SensorState xi0;
+        GroupSensor X;
+        std::vector<int> ids;
+    };
+    std::vector<HostHalf> held(nin);
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        const eqf_batch::Slot &from = b->s[src[e]], &to = b->s[dst[e]];
+        CopyIn& in = b->h_cin[in_of[e]];
+        in.src = src[e];
+        in.scur = from.cur;
+        in.dst = dst[e];
+        in.dnxt = to.cur ^ 1;
+        in.N = (int)from.ids.size();
+        held[in_of[e]] = HostHalf{from.xi0, from.X, from.ids};
+    }
+    CopyArgs ca;
+    ca.ld = b->ld;
+    ca.sig = b->d_sig;
+    ca.lm = b->d_lm;
+    ca.sig_stride = b->sig_stride;
+    ca.lm_stride = b->lm_stride;
+    ca.in = b->d_cin;
+    HIPCHK(hipMemcpyAsync(b->d_cin, b->h_cin, sizeof(CopyIn) * nin, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_copy, dim3(nin, BATCH_COPY_CHUNKS), dim3(BATCH_T), 0, b->stream, ca);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        eqf_batch::Slot& to = b->s[dst[e]];
+        HostHalf& h = held[in_of[e]];
+        to.xi0 = h.xi0;
+        to.X = h.X;
+        to.ids.swap(h.ids);
+        to.cur ^= 1;
+        to.flags = 0; // the last step's outcome was another state's: as a slot that never stepped
+        to.depth = 0.0;
+        to.inn_dof = 0;
+        to.inn_nis = to.inn_logdet = 0.0;
     }
     return 0;
 }

@@ -124,6 +124,18 @@ int VIOFilterBatch::setSlotSettings(int k, const eqvio_settings& s) {
     return 0;
 }
 
+// eqf_batch_copy_slots, then the host half of every entry that was done, from the sources as they were before the call
+void VIOFilterBatch::copySlots(int count, const int* src, const int* dst, int* status) {
+    check(eqf_batch_copy_slots(batch, count, src, dst, status), "eqf_batch_copy_slots");
+    std::vector<Slot> held(count);
+    for (int e = 0; e < count; ++e)
+        if (status[e] == 0 && src[e] != dst[e])
+            held[e] = slotv.at(src[e]);
+    for (int e = 0; e < count; ++e)
+        if (status[e] == 0 && src[e] != dst[e])
+            slotv.at(dst[e]) = std::move(held[e]);
+}
+
 void VIOFilterBatch::startFromState(int k, const double* sensor, const int* ids, const double* p, int N, double time) { // VIOFilter.cpp:43-56
     Slot& sl = slotv.at(k);
     std::vector<double> Q(5 * (size_t)N);
@@ -348,6 +360,11 @@ int eqvio_batch_innovation_totals(const eqvio_batch* b, int slot, long* updates,
     return b ? eqf_batch_innovation_totals(b->f->core(), slot, updates, dof, nis, logdet) : EQF_E_BAD_ARG;
 }
 int eqvio_batch_reset_innovation_totals(eqvio_batch* b, int slot) { return b ? eqf_batch_reset_innovation_totals(b->f->core(), slot) : EQF_E_BAD_ARG; }
+int eqvio_batch_copy_slots(eqvio_batch* b, int count, const int* src, const int* dst, int* status) {
+    if (!b || count < 0 || !src || !dst || !status)
+        return EQF_E_BAD_ARG;
+    return guarded(b, [&] { b->f->copySlots(count, src, dst, status); });
+}
 int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count) {
     if (!b || !per_slot || first < 0 || count < 0)
         return EQF_E_BAD_ARG;

@@ -36,6 +36,9 @@ class VIOFilterBatch {
     // call throws and the slot has its former settings again.
     int setSlotSettings(int slot, const eqvio_settings& s);
     eqvio_settings slotSettings(int slot) const;
+    // Entry e: slot dst[e] becomes slot src[e] as it was before the call - the EqF state on the device (eqf_batch_copy_slots: one launch, same status codes)
+    // and the host half: IMU buffer, current time, initialised flag. The destination keeps its settings and innovation totals. A refused entry changes nothing.
+    void copySlots(int count, const int* src, const int* dst, int* status);
     void startFromState(int slot, const double* sensor, const int* ids, const double* p, int N, double time);
     void processIMUData(int slot, const IMUVelocity& imu);
     // processVisionData for `count` slots in one device step; status per entry

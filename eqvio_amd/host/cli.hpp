@@ -156,6 +156,19 @@ inline std::string sweepRefusal(const Sweep& sw, int B, const eqvio_settings& es
         return "--sweep has " + std::to_string(sw.values.size()) + " values for --batch " + std::to_string(B) + ": one value per slot";
     return "";
 }
+// what a sweep is refused for behind a warm-up (--warmup F, F > 0), where the value reaches a filter that already runs: the chart cannot change under a slot
+// that holds landmarks (eqf_batch_set_slot_settings), and the initial variances of the sensor state are read only when a filter starts, so every slot would
+// score the same. initialPointVariance, initialPointDepthVariance and initialSceneDepth are read for every new landmark and stay.
+inline std::string warmupSweepRefusal(const Sweep& sw) {
+    static const char* const atStart[] = {"initialAttitudeVariance", "initialPositionVariance", "initialVelocityVariance", "initialCameraAttitudeVariance",
+                                          "initialCameraPositionVariance", "initialBiasOmegaVariance", "initialBiasAccelVariance"};
+    if (sw.name == "coordinateChoice")
+        return "--warmup with --sweep coordinateChoice: the chart cannot change under a filter that holds landmarks";
+    for (const char* n : atStart)
+        if (sw.name == n)
+            return "--warmup with --sweep " + sw.name + ": it is read only when a filter starts, so it has no effect behind a warm-up";
+    return "";
+}
 
 // the filter settings as the C-ABI's eqvio_settings
 inline eqvio_settings batchSettings(const VIOFilter::Settings& fs) {

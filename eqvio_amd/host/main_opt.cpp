@@ -2,7 +2,9 @@
 // tracks instead of images (no OpenCV / GIFT here): IMU -> processIMUData, tracks -> processVisionData, outputs through
 // VIOWriter. The filter starts uninitialised and sets its attitude from the first IMU sample (VIOFilter.cpp:65-78).
 // --batch B [--sweep NAME=v0,...] replays the dataset in the B slots of one filter batch (VIOFilterBatch.hpp), slot k with the k-th value, and scores every
-// slot by its innovation statistics (include/eqf_batch.h): a tuning sweep on a dataset without landmark truth.
+// slot by its innovation statistics (include/eqf_batch.h): a tuning sweep on a dataset without landmark truth. With --warmup F the first F frames run once, in
+// slot 0 under the command line's settings, and slot 0 is then copied into the other slots on the device (eqf_batch_copy_slots): every tuning starts from the
+// same converged filter, and the scores count the frames after the warm-up only.
 #include "DatasetReplay.hpp"
 #include "VIOFilterBatch.hpp"
 #include "VIOWriter.hpp"
@@ -15,22 +17,31 @@
 
 using namespace eqvio_amd;
 
+static void check_rc(int rc, const char* what) {
+    if (rc != 0)
+        throw std::runtime_error(std::string(what) + ": " + eqf_error_string(rc));
+}
+
 static void usage() {
     std::puts("usage: eqvio_opt --imu FILE --features FILE [--format asl|uzhfpv] [--groundtruth FILE] [--dumpMeasurements] [--dumpStates FILE] [--printCamera]\n"
               "                 [--cameraFile sensor.yaml | camchain.yaml]   (intrinsics, distortion and camera offset from the dataset's own file, main_opt.cpp:114-147)\n"
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--batch B [--sweep NAME=v0,v1,...]]\n"
+              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F]]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
               "              (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood. Needs --fastRiccati 1 and at most 64\n"
               "              features per frame; --output, --dumpStates and --sigmaFP32 are refused.\n"
-              "  --sweep NAME=v0,...,v(B-1)   with --batch B: slot k runs with the filter setting NAME (a field of eqvio_settings) at value vk. Needs exactly B values.");
+              "  --sweep NAME=v0,...,v(B-1)   with --batch B: slot k runs with the filter setting NAME (a field of eqvio_settings) at value vk. Needs exactly B values.\n"
+              "  --warmup F   with --batch B --sweep: the first F vision frames run in slot 0 alone, with the command line's settings; slot 0 is then copied into\n"
+              "              slots 1 .. B-1 on the device, the sweep's values go to all B slots, and the scores count the frames after the warm-up only.\n"
+              "              With F > 0 a sweep of coordinateChoice (Sigma is in the chart's coordinates) or of an initial variance of the sensor state (used only\n"
+              "              when a filter starts) is refused.");
 }
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
-static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, double startTime, double stopTime) {
+static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -39,17 +50,40 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         return 1;
     }
     VIOFilterBatch filters(core); // every slot as VIOFilter(fs): it initialises itself from its first IMU sample
-    for (int k = 0; k < B && swept; ++k) {
-        eqvio_settings ek = es;
-        std::string why;
-        setSettingsField(ek, sweep.name, sweep.values[k], why);
-        if (const int rc = filters.setSlotSettings(k, ek))
-            throw std::runtime_error("--sweep " + sweep.name + "=" + sweep.values[k] + ": " + eqf_error_string(rc));
-    }
+    auto applySweep = [&] {
+        for (int k = 0; k < B && swept; ++k) {
+            eqvio_settings ek = es;
+            std::string why;
+            setSettingsField(ek, sweep.name, sweep.values[k], why);
+            if (const int rc = filters.setSlotSettings(k, ek))
+                throw std::runtime_error("--sweep " + sweep.name + "=" + sweep.values[k] + ": " + eqf_error_string(rc));
+        }
+    };
+    // --warmup F: slot 0 alone, under the command line's settings, until F frames have run; then it is copied into the others, the sweep's values go to all
+    // slots and the totals start again. Without a warm-up every slot runs from the start with its value.
+    // `branched` and not live < B says whether that has happened: with B = 1 nothing is copied, yet the value, the reset and the count start at frame F too.
+    int live = warmup > 0 ? 1 : B;
+    bool branched = warmup == 0;
+    auto branch = [&] {
+        std::vector<int> src(B - 1, 0), dst(B - 1), st(B - 1, 0);
+        for (int k = 1; k < B; ++k)
+            dst[k - 1] = k;
+        if (B > 1)
+            filters.copySlots(B - 1, src.data(), dst.data(), st.data());
+        for (int k = 1; k < B; ++k)
+            if (st[k - 1] != 0)
+                throw std::runtime_error("--warmup: copying slot 0 into slot " + std::to_string(k) + ": " + eqf_error_string(st[k - 1]));
+        applySweep();
+        check_rc(eqf_batch_reset_innovation_totals(filters.core(), -1), "eqf_batch_reset_innovation_totals");
+        live = B;
+        branched = true;
+    };
+    if (warmup == 0)
+        applySweep();
     std::vector<int> slots(B), status(B), failed(B, 0);
     for (int k = 0; k < B; ++k)
         slots[k] = k;
-    int imuDataCounter = 0, visionDataCounter = 0;
+    int imuDataCounter = 0, visionDataCounter = 0, scoredFrames = 0;
     const auto loopStartTime = std::chrono::steady_clock::now();
     while (true) {
         const MeasurementType measType = dataServer.nextMeasurementType();
@@ -59,20 +93,24 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
             const VisionMeasurement measData = dataServer.getSimVision();
             if (startTime > 0 && measData.stamp < startTime)
                 continue;
+            if (!branched && visionDataCounter == warmup)
+                branch(); // before the first frame after the warm-up, and behind every IMU sample that came before it
             const std::vector<const VisionMeasurement*> meas(B, &measData);
-            filters.processVisionData(B, slots.data(), meas.data(), status.data()); // one device step for all slots
-            for (int k = 0; k < B; ++k) {
-                if (status[k] == EQF_E_NOT_SPD || status[k] == EQF_E_NONFINITE)
-                    ++failed[k]; // this tuning's update failed on this frame: the slot goes on without it, the others are not affected
-                else if (status[k] != 0)
+            filters.processVisionData(live, slots.data(), meas.data(), status.data()); // one device step for all live slots
+            for (int k = 0; k < live; ++k) {
+                if (status[k] == EQF_E_NOT_SPD || status[k] == EQF_E_NONFINITE) {
+                    if (branched)
+                        ++failed[k]; // this tuning's update failed on this frame: the slot goes on without it, the others are not affected
+                } else if (status[k] != 0)
                     throw std::runtime_error("slot " + std::to_string(k) + ", stamp " + std::to_string(measData.stamp) + ": " + eqf_error_string(status[k]));
             }
             ++visionDataCounter;
+            scoredFrames += branched;
         } else {
             const IMUVelocity imuData = dataServer.getIMU();
             if (startTime > 0 && imuData.stamp < startTime)
                 continue;
-            for (int k = 0; k < B; ++k)
+            for (int k = 0; k < live; ++k)
                 filters.processIMUData(k, imuData);
             ++imuDataCounter;
         }
@@ -82,6 +120,11 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopStartTime).count();
     std::cout << "Processed " << imuDataCounter << " IMU and " << visionDataCounter << " vision measurements in " << B << " slots.\n"
               << "Time taken: " << elapsed << " seconds." << std::endl;
+    if (warmup > 0) {
+        if (!branched)
+            throw std::runtime_error("--warmup " + std::to_string(warmup) + ": the sequence has only " + std::to_string(visionDataCounter) + " vision frames");
+        std::printf("warm-up: %d frames in slot 0, then copied into %d slots; scores over the %d frames after the warm-up\n", warmup, B - 1, scoredFrames);
+    }
     for (int k = 0; k < B; ++k) {
         const VIOFilterBatch::InnovationTotals t = filters.innovationTotals(k);
         const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
@@ -104,8 +147,9 @@ int main(int argc, char** argv) {
     cam->c.width = 752;
     cam->c.height = 480;
     double cameraLag = 0, startTime = -1, stopTime = -1;
-    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false;
+    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false;
     int batch = 0;
+    std::string warmupText;
     Sweep sweep;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -161,6 +205,9 @@ int main(int argc, char** argv) {
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
                 haveSweep = true;
+            } else if (a == "--warmup") {
+                warmupText = val();
+                haveWarmup = true;
             }
             else if (!parseFilterFlag(a, val, fs)) {
                 usage();
@@ -171,6 +218,21 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "eqvio_opt: --sweep needs --batch B (one value per slot)\n");
             return 2;
         }
+        int warmup = 0;
+        if (haveWarmup) { // before any file or device is opened, as the refusals of --batch
+            char* end = nullptr;
+            const long f = std::strtol(warmupText.c_str(), &end, 10);
+            const std::string why = batch == 0 || !haveSweep ? "needs --batch B and --sweep NAME=v0,... (the warm-up is what the swept slots branch from)"
+                                    : warmupText.empty() || *end ? "'" + warmupText + "' is not a number of frames"
+                                    : f < 0 ? "needs F >= 0"
+                                    : f > 1000000000 ? "is more frames than any sequence has"
+                                    : "";
+            if (!why.empty()) {
+                std::fprintf(stderr, "eqvio_opt: --warmup %s: %s\n", warmupText.c_str(), why.c_str());
+                return 2;
+            }
+            warmup = (int)f;
+        }
         if (batch != 0) { // what the filter batch refuses, before any file or device is opened
             std::string why = batch < 1 ? "needs B >= 1"
                               : !fs.fastRiccati ? "needs --fastRiccati 1 (the batch has fast Riccati only; the default is 0)"
@@ -180,6 +242,8 @@ int main(int argc, char** argv) {
                               : "";
             if (why.empty() && haveSweep)
                 why = sweepRefusal(sweep, batch, batchSettings(fs));
+            if (why.empty() && warmup > 0)
+                why = warmupSweepRefusal(sweep);
             if (!why.empty()) {
                 std::fprintf(stderr, "eqvio_opt: --batch %d: %s\n", batch, why.c_str());
                 return 2;
@@ -226,7 +290,7 @@ int main(int argc, char** argv) {
             return 0;
         }
         if (batch != 0)
-            return runBatch(dataServer, fs, batch, sweep, startTime, stopTime);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime);
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150
         if (sigmaFP32) // BASELINE config 5: Sigma stored as float in HBM (include/eqf_hip.h)

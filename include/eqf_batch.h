@@ -154,6 +154,24 @@ typedef struct eqf_batch_augment_entry {
  *   EQF_E_CAPACITY     the result would hold more than max_landmarks: the slot is untouched.
  * Returns 0, EQF_E_BAD_ARG for null arguments or count < 0, or a HIP error. */
 int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* entries, int* status);
+
+/* Copies whole filters between slots on the device: entry e makes slot dst[e] hold the EqF state slot src[e] held BEFORE the call - xi0, X, the landmark
+ * ids, the landmarks (q0 and its chart constants, Q) and Sigma (n x n, n = 21 + 3 N), bit for bit. One launch for the whole call and one synchronisation;
+ * nothing crosses to the host. Every copy reads its source's current buffers and writes its destination's other ones, so the entries of one call may form
+ * any mapping: a slot may be the source of many entries, and the destination of one entry while the source of another (a swap, a cycle). To fork a run, to
+ * warm up once and branch into B tunings, to resample by likelihood, to keep a checkpoint slot.
+ * The destination keeps its own settings (eqf_batch_set_slot_settings), its innovation totals and its eqf_batch_nees_lu_fallbacks count. Its last step's
+ * outcome was another state's: eqf_batch_last_result gives flags 0 and depth 0, eqf_batch_last_innovation 0, 0, 0, as on a slot that never stepped.
+ * src[e] == dst[e] is accepted and does nothing, but it names its slot as a destination like any entry: a later entry into that slot is refused as a
+ * repeated destination, and so is the entry onto itself when an earlier entry copied into the slot. status[e] (count entries):
+ *   0                  done;
+ *   EQF_E_BAD_ARG      bad slot index; a destination that an earlier entry of the call names already; or a source that holds landmarks while the
+ *                      destination's coordinateChoice is not the source's: Sigma is expressed in the chart's coordinates (the rule of
+ *                      eqf_batch_set_slot_settings; a source without landmarks copies into either chart).
+ * Refusals are decided before any device work and leave the refused destination untouched, bit for bit; the other entries are still done.
+ * Returns 0 when the launch ran (whatever the per-entry codes), EQF_E_BAD_ARG for a null batch, src, dst or status or count < 0 (no device is looked at),
+ * or a HIP error. */
+int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst, int* status);
 /* the hipStream_t the batch launches on, as void* */
 void* eqf_batch_stream(eqf_batch* b);
 int eqf_batch_synchronize(eqf_batch* b);

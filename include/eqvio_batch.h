@@ -76,6 +76,13 @@ int eqvio_batch_sigma_dim(const eqvio_batch* b, int slot);
 int eqvio_batch_get_sigma(eqvio_batch* b, int slot, double* out_colmajor, int n);
 double eqvio_batch_get_time(const eqvio_batch* b, int slot);
 int eqvio_batch_is_initialised(const eqvio_batch* b, int slot);
+/* Copies whole filters between slots without leaving the device (eqf_batch_copy_slots, include/eqf_batch.h: one launch, any mapping of sources to
+ * destinations, same status codes and refusals): entry e makes slot dst[e] what slot src[e] was BEFORE the call - the EqF state (xi0, X, landmarks, Sigma) and
+ * what the reference's VIOFilter keeps on the host: the IMU buffer, the current time and the initialised flag. The destination keeps its own settings and
+ * its innovation totals; its last step's innovation reads 0, 0, 0. A refused entry changes nothing of its destination, host half included. For a sweep that
+ * warms up once: run the first frames in one slot, copy it into the others, give them their settings. Returns 0, EQF_E_BAD_ARG (null arguments, count < 0)
+ * or -1 (eqvio_batch_last_error). */
+int eqvio_batch_copy_slots(eqvio_batch* b, int count, const int* src, const int* dst, int* status);
 /* The innovation statistics of the slot's last step and their totals over the slot's updated steps (eqf_batch_last_innovation, _innovation_totals,
  * _reset_innovation_totals, include/eqf_batch.h: same meaning, same codes; the numbers are the device batch's, kept nowhere else). A slot that sits a step
  * out (stale stamp, ended sequence) adds nothing. For a score per slot of a replay: reset, eqvio_batch_run_prepared / _run_sim, read the totals. */
