@@ -5,6 +5,7 @@ step, one workgroup per slot. .slot(k) is a view with the method names of capi.V
 The prototypes are declared in lists of their own (_batch_declared), apart from the loaders' _declared lists of eqf_hip.h / eqvio_filter.h.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -33,6 +34,24 @@ class BatchAugmentEntry(C.Structure):
     _fields_ = [("slot", C.c_int), ("n_new", C.c_int), ("new_ids", c_int_p), ("n_prov", C.c_int), ("prov_ids", c_int_p), ("prov_p", c_double_p)]
 
 
+EQF_BATCH_NBLOCKS = 7
+BLOCK_NAMES = ("bias", "attitude", "position", "pose", "velocity", "camera", "sensor")  # EQF_BLOCK_* order
+
+
+class BatchConsistencyRecord(C.Structure):
+    """eqf_batch_consistency_record (include/eqf_batch.h)."""
+
+    _fields_ = [("N", C.c_int), ("lu", C.c_int), ("nees", C.c_double), ("block", C.c_double * EQF_BATCH_NBLOCKS),
+                ("eps", C.c_double * (21 + 3 * EQF_BATCH_MAX_LANDMARKS)), ("sigma_diag", C.c_double * (21 + 3 * EQF_BATCH_MAX_LANDMARKS)),
+                ("ids", C.c_int * EQF_BATCH_MAX_LANDMARKS), ("lm_quad", C.c_double * EQF_BATCH_MAX_LANDMARKS), ("lm_err", C.c_double * EQF_BATCH_MAX_LANDMARKS)]
+
+    def trimmed(self):
+        """The record as a dict of numpy arrays trimmed to n = 21 + 3 N and N."""
+        N, n = self.N, 21 + 3 * self.N
+        return {"N": N, "lu": self.lu, "nees": self.nees, "block": np.array(self.block), "eps": np.array(self.eps)[:n], "sigma_diag": np.array(self.sigma_diag)[:n],
+                "ids": np.array(self.ids, dtype=np.int32)[:N], "lm_quad": np.array(self.lm_quad)[:N], "lm_err": np.array(self.lm_err)[:N]}
+
+
 def load_batch_protos():
     """Declare the prototypes of include/eqf_batch.h on libeqf_hip.so and of include/eqvio_batch.h on libeqvio_filter.so."""
     elib, flib = load_eqf_lib(), load_filter_lib()
@@ -59,6 +78,7 @@ def load_batch_protos():
         "eqf_batch_synchronize": (C.c_int, [vp]),
         "eqf_batch_nees": (C.c_int, [vp, C.c_int, P(BatchTruth), c_double_p, c_int_p]),
         "eqf_batch_nees_lu_fallbacks": (C.c_int, [vp, C.c_int, P(C.c_long)]),
+        "eqf_batch_consistency": (C.c_int, [vp, C.c_int, P(BatchTruth), P(BatchConsistencyRecord), c_int_p]),
         "eqf_batch_augment": (C.c_int, [vp, C.c_int, P(BatchAugmentEntry), c_int_p]),
         "eqf_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
         "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
@@ -87,6 +107,8 @@ def load_batch_protos():
         "eqvio_batch_compute_nees": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
         "eqvio_batch_augment_landmark_states": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_sim": (C.c_int, [vp, P(vp), C.c_int, c_double_p, c_int_p]),
+        "eqvio_batch_consistency": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, P(BatchConsistencyRecord), c_int_p]),
+        "eqvio_batch_run_sim_recorded": (C.c_int, [vp, P(vp), C.c_int, c_double_p, c_int_p, C.c_char_p]),
         "eqvio_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
         "eqvio_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqvio_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
@@ -213,6 +235,27 @@ class VIOFilterBatch:
         self._chk(self.lib.eqvio_batch_compute_nees(self.h, n, _ip(slots), _dp(sensors), _ip(counts), _ip(ids), _dp(p), _dp(nees), _ip(status)))
         return nees[:n].copy(), status[:n].copy()
 
+    def consistency_records(self, entries, rec=None):
+        """eqvio_batch_consistency on entries as compute_nees's: the untrimmed BatchConsistencyRecord array (rec, or a new zeroed one; a refused entry's
+        record is left as it was) and the per-entry status codes."""
+        n = len(entries)
+        slots = _i32([e[0] for e in entries])
+        sensors = _f64(np.concatenate([np.asarray(e[1], np.float64).ravel() for e in entries]) if n else np.zeros(0))
+        counts = _i32([len(e[2]) for e in entries])
+        ids = _i32(np.concatenate([np.asarray(e[2], np.int32) for e in entries]) if n else np.zeros(0, np.int32))
+        p = _f64(np.concatenate([np.asarray(e[3], np.float64).ravel() for e in entries]) if n else np.zeros(0))
+        rec = (BatchConsistencyRecord * max(n, 1))() if rec is None else rec
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_consistency(self.h, n, _ip(slots), _dp(sensors), _ip(counts), _ip(ids), _dp(p), rec, _ip(status)))
+        return rec, status[:n].copy()
+
+    def consistency(self, entries):
+        """entries as compute_nees's. The consistency record of every listed slot in ONE launch (eqvio_batch_consistency): returns a list of dicts of numpy
+        arrays trimmed to n = 21 + 3 N and N (nees, lu, block[7] in BLOCK_NAMES order, eps, sigma_diag, ids, lm_quad, lm_err; None where the status is not 0)
+        and the per-entry status codes. Only the records cross to the host."""
+        rec, status = self.consistency_records(entries)
+        return [rec[e].trimmed() if status[e] == 0 else None for e in range(len(entries))], status
+
     def augment_landmark_states(self, entries):
         """entries: list of (slot, new_ids, provided_ids, provided_p[n, 3]). augmentLandmarkStates of every listed slot in ONE launch; returns the per-entry
         status codes (eqf_batch_augment)."""
@@ -228,15 +271,20 @@ class VIOFilterBatch:
                                                                _ip(status)))
         return status[:n].copy()
 
-    def run_sim(self, sims, max_frames):
+    def run_sim(self, sims, max_frames, record_dir=None):
         """The reference's main_sim loop over the slots in lockstep (eqvio_batch_run_sim): sims[k] is slot k's capi.SimulationDataServer (or None). Returns the
-        NEES of every frame and slot, shape (frames run, slots), NaN where a slot had no frame."""
+        NEES of every frame and slot, shape (frames run, slots), NaN where a slot had no frame. With record_dir every run's consistency files (nees.csv,
+        poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv, landmarkError.csv) go to record_dir/run_<k>/ (eqvio_batch_run_sim_recorded); the
+        returned array is the same, bit for bit."""
         if len(sims) > self.slots:
             raise ValueError("more simulations than slots")
         arr = (C.c_void_p * self.slots)(*([s.h if s is not None else None for s in sims] + [None] * (self.slots - len(sims))))
         nees = np.zeros(max(max_frames, 1) * self.slots)
         done = C.c_int()
-        self._chk(self.lib.eqvio_batch_run_sim(self.h, arr, max_frames, _dp(nees), C.byref(done)))
+        if record_dir is None:
+            self._chk(self.lib.eqvio_batch_run_sim(self.h, arr, max_frames, _dp(nees), C.byref(done)))
+        else:
+            self._chk(self.lib.eqvio_batch_run_sim_recorded(self.h, arr, max_frames, _dp(nees), C.byref(done), os.fsencode(record_dir)))
         return nees[: done.value * self.slots].reshape(done.value, self.slots).copy()
 
     def nees_lu_fallbacks(self, k):
@@ -321,6 +369,13 @@ class BatchSlot:
         if st[0] != 0:
             raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
         return float(nees[0])
+
+    def consistency(self, sensor, ids, p):
+        """This slot's consistency record (VIOFilterBatch.consistency), a dict of numpy arrays trimmed to n and N."""
+        rec, st = self.b.consistency([(self.k, sensor, ids, p)])
+        if st[0] != 0:
+            raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
+        return rec[0]
 
     def augment_landmark_states(self, new_ids, sensor, ids, p):
         """capi.VIOFilter's signature; the provided state's sensor part is not used (nor is it by the reference)."""

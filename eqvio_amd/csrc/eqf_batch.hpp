@@ -25,6 +25,7 @@
 // A pivot <= 0 (EQF_E_NOT_SPD) or a non-finite Gamma (EQF_E_NONFINITE) ends the frame before anything of the update is written: the slot then holds the frame's
 // propagation and landmark bookkeeping (phases 0 - 3) without the update.
 #pragma once
+#include "eqf_batch.h"
 #include "eqf_kernels.hpp"
 
 namespace eqf {
@@ -690,12 +691,124 @@ __device__ __forceinline__ void nees_build_z(int n, int np, int ld, const double
     }
 }
 
+// ---- the consistency record (eqf_batch_consistency, include/eqf_batch.h): what k_batch_consistency adds to the NEES of an entry
+// Rows of eps / Sigma of block k (EQF_BLOCK_*): first row and size
+__device__ __forceinline__ int cons_block_row(int k) { return k == 0 ? 0 : k == 1 ? 6 : k == 2 ? 9 : k == 3 ? 6 : k == 4 ? 12 : k == 5 ? 15 : 0; }
+__device__ __forceinline__ int cons_block_dim(int k) { return k == 0 || k == 3 || k == 5 ? 6 : k == 6 ? 21 : 3; }
+// LDS layout of the block forms, in the panel region P before the factorisation uses it (doubles): the sensor block of Sigma (21 x 21, M[i][j] at 21 i + j), the
+// wave's working copy [M | x] of the 21-row block (row stride 22) with its solution behind it, one workspace per small block and one per landmark
+constexpr int CONS_S21 = 0, CONS_W21 = 448, CONS_Y21 = CONS_W21 + 21 * 22, CONS_SMALL = 944, CONS_SMALL_W = 6 * 7 + 12, CONS_LM = CONS_SMALL + 6 * CONS_SMALL_W,
+              CONS_LM_W = 3 * 4 + 6, CONS_END = CONS_LM + BATCH_L * CONS_LM_W;
+static_assert(CONS_Y21 + 21 <= CONS_SMALL && 441 <= CONS_W21, "the block forms' LDS regions are disjoint");
+
+// Measurement switch, 0 in every build that ships: -DEQF_CONS_MEASURE_SKIP=1 builds k_batch_consistency without the block forms (block[] and lm_quad stay
+// unwritten), =2 without the stores of eps and of the diagonal of Sigma. For attributing the kernel's time only (profiles/r13_batch_consistency_breakdown.txt).
+#ifndef EQF_CONS_MEASURE_SKIP
+#define EQF_CONS_MEASURE_SKIP 0
+#endif
+
+// the lanes of one wave see each other's LDS stores behind this
+__device__ __forceinline__ void batch_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// x^T M^-1 x by the elimination rule of VIOWriter.cpp's quadInv (the reference's .inverse() route): Gaussian elimination with partial pivoting on [M | x], the
+// pivot the first row of largest magnitude, back substitution, then x^T y. One lane; w: K rows of [M | x] (row stride K + 1, destroyed), then K doubles that
+// hold x and K that receive y. A zero pivot gives a non-finite value, which is returned as it is.
+__device__ __forceinline__ double cons_quad_inv_lane(double* w, int K) {
+    const int st = K + 1;
+    double* x0 = w + K * st;
+    double* y = x0 + K;
+    for (int i = 0; i < K; ++i)
+        x0[i] = w[i * st + K];
+    for (int c = 0; c < K; ++c) {
+        int p = c;
+        for (int r = c + 1; r < K; ++r)
+            if (fabs(w[r * st + c]) > fabs(w[p * st + c]))
+                p = r;
+        if (p != c)
+            for (int j = 0; j <= K; ++j) {
+                const double t = w[p * st + j];
+                w[p * st + j] = w[c * st + j];
+                w[c * st + j] = t;
+            }
+        for (int r = c + 1; r < K; ++r) {
+            const double f = w[r * st + c] / w[c * st + c];
+            for (int j = c; j <= K; ++j)
+                w[r * st + j] -= f * w[c * st + j];
+        }
+    }
+    for (int i = K - 1; i >= 0; --i) {
+        double s = w[i * st + K];
+        for (int j = i + 1; j < K; ++j)
+            s -= w[i * st + j] * y[j];
+        y[i] = s / w[i * st + i];
+    }
+    double q = 0.0;
+    for (int i = 0; i < K; ++i)
+        q += x0[i] * y[i];
+    return q;
+}
+
+// The same rule for the 21-row sensor block by one wave: lane r owns row r of [M | x] (w, row stride 22, destroyed; x: the 21 sensor entries of eps; y: 21
+// doubles). Per column: the pivot search across the wave (largest |a[r][c]|, the first such row), the row swap by lanes 0 .. 21, the elimination one lane per
+// row; lane 0 then does the back substitution and x^T y in quadInv's order. Every lane returns the value.
+__device__ __forceinline__ double cons_quad_inv_wave21(double* w, const double* x, double* y, int lane) {
+    constexpr int K = 21, st = K + 1;
+    for (int c = 0; c < K; ++c) {
+        double v = (lane >= c && lane < K) ? fabs(w[lane * st + c]) : -1.0;
+        int p = lane;
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(v, o, 64);
+            const int op = __shfl_xor(p, o, 64);
+            if (ov > v || (ov == v && op < p)) {
+                v = ov;
+                p = op;
+            }
+        }
+        p = __shfl(p, 0, 64);
+        p = (p >= c && p < K) ? p : c; // a column of NaN leaves no order: any row of the range, the same in every lane
+        if (p != c && lane <= K) {
+            const double t = w[p * st + lane];
+            w[p * st + lane] = w[c * st + lane];
+            w[c * st + lane] = t;
+        }
+        batch_wave_sync();
+        if (lane > c && lane < K) {
+            const double f = w[lane * st + c] / w[c * st + c];
+            for (int j = c; j <= K; ++j)
+                w[lane * st + j] -= f * w[c * st + j];
+        }
+        batch_wave_sync();
+    }
+    double q = 0.0;
+    if (lane == 0) {
+        for (int i = K - 1; i >= 0; --i) {
+            double s = w[i * st + K];
+            for (int j = i + 1; j < K; ++j)
+                s -= w[i * st + j] * y[j];
+            y[i] = s / w[i * st + i];
+        }
+        for (int i = 0; i < K; ++i)
+            q += x[i] * y[i];
+    }
+    return __shfl(q, 0, 64);
+}
+
 // Blocked right-looking Cholesky of Z = [Sigma ; eps^T] with the eps row carried along as an extra row: after the factorisation that row holds z = L^-1 eps,
 // and |z|^2 = eps^T Sigma^-1 eps. Per 16-column panel: rows k0 .. np of the panel into LDS, the panel factored on the VALU (one lane per row), the eps row's
 // entries summed, and the trailing lower triangle (the eps row included) updated by Z -= L21 L21^T in 16 x 16 tiles on the matrix cores (mfma16_nt, one wave
 // per tile, operands from LDS). A pivot <= 0 (or not finite) sends the slot to partial-pivot Gaussian elimination on [Sigma | eps], in the same workgroup: what
 // k_ge_step / k_ge_back do over np launches in the context path, so a number comes back whenever the reference's Sigma.inverse() gives one.
-__global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) {
+//
+// REC (k_batch_consistency): the same front half and the same factorisation, and between them the rest of the entry's consistency record - the seven block
+// forms and the landmarks' 3 x 3 forms by quadInv's rule, the landmarks' point errors, eps and the diagonal of Sigma - written to rec with plain stores. The
+// block forms work in the panel region before the first panel is loaded, so the LDS footprint is k_batch_nees's. eps^T Sigma^-1 eps and the fallback flag then go
+// to rec->nees / rec->lu instead of na.out. Nothing of the arithmetic that leads to them depends on REC.
+template <bool REC> __device__ __forceinline__ void batch_nees_body(const NeesArgs& na, eqf_batch_consistency_record* rec) {
+    static_assert(CONS_END <= NEES_PLD * NEES_PW, "the block forms fit into the panel region");
     __shared__ double P[NEES_PLD * NEES_PW]; // the panel; x of the back substitution in the fallback
     __shared__ double s_eps[NEES_NP + 1];
     __shared__ double s_red[BATCH_T];
@@ -718,8 +831,61 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) {
         s_eps[21 + 3 * i] = e.x;
         s_eps[22 + 3 * i] = e.y;
         s_eps[23 + 3 * i] = e.z;
+        if constexpr (REC) { // |p_hat - p_true|, p_hat = Q^-1 q0 (eqf_batch_state_estimate's expression)
+            const V3 ph = (1.0 / lm[BATCH_QA * L + i]) * q_rot(q_inv(ldq(lm + BATCH_QQ * L, L, i)), ld3(lm, L, i));
+            rec->lm_err[i] = norm(ph - V3{in.p[3 * i], in.p[3 * i + 1], in.p[3 * i + 2]});
+        }
     }
     __syncthreads();
+    if constexpr (REC) {
+        for (int t = tid; t < 441; t += BATCH_T)
+            P[CONS_S21 + t] = S[t / 21 + (size_t)(t % 21) * ld];
+        __syncthreads();
+        const int wave = tid >> 6, lane = tid & 63;
+        if constexpr (EQF_CONS_MEASURE_SKIP & 1) {
+        } else if (wave == 0) { // the 21-row block
+            double* w = P + CONS_W21;
+            for (int t = lane; t < 21 * 22; t += 64)
+                w[t] = t % 22 < 21 ? P[CONS_S21 + 21 * (t / 22) + t % 22] : s_eps[t / 22];
+            batch_wave_sync();
+            const double q = cons_quad_inv_wave21(w, s_eps, P + CONS_Y21, lane);
+            if (lane == 0)
+                rec->block[EQF_BLOCK_SENSOR] = q;
+        } else if (wave == 1) { // the six small blocks, one lane each
+            if (lane < EQF_BLOCK_SENSOR) {
+                const int r0 = cons_block_row(lane), K = cons_block_dim(lane);
+                double* w = P + CONS_SMALL + lane * CONS_SMALL_W;
+                for (int i = 0; i < K; ++i) {
+                    for (int j = 0; j < K; ++j)
+                        w[i * (K + 1) + j] = P[CONS_S21 + 21 * (r0 + i) + r0 + j];
+                    w[i * (K + 1) + K] = s_eps[r0 + i];
+                }
+                rec->block[lane] = cons_quad_inv_lane(w, K);
+            }
+        } else if (wave == 2) { // the landmarks' 3 x 3 marginals, straight from Sigma
+            if (lane < N) {
+                const int r0 = 21 + 3 * lane;
+                double* w = P + CONS_LM + lane * CONS_LM_W;
+                for (int i = 0; i < 3; ++i) {
+                    for (int j = 0; j < 3; ++j)
+                        w[i * 4 + j] = S[(r0 + i) + (size_t)(r0 + j) * ld];
+                    w[i * 4 + 3] = s_eps[r0 + i];
+                }
+                rec->lm_quad[lane] = cons_quad_inv_lane(w, 3);
+            }
+        }
+        if constexpr (!(EQF_CONS_MEASURE_SKIP & 2))
+            for (int r = tid; r < BATCH_NMAX; r += BATCH_T) {
+                rec->eps[r] = r < n ? s_eps[r] : 0.0;
+                rec->sigma_diag[r] = r < n ? S[r + (size_t)r * ld] : 0.0;
+            }
+        for (int i = N + tid; i < BATCH_L; i += BATCH_T) {
+            rec->lm_quad[i] = 0.0;
+            rec->lm_err[i] = 0.0;
+        }
+        if (tid == 0)
+            rec->N = N;
+    }
     nees_build_z(n, np, ld, S, s_eps, Z, true);
     __syncthreads();
 
@@ -785,8 +951,13 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) {
     }
     if (!fail) {
         if (tid == 0) {
-            na.out[blockIdx.x].sumsq = acc;
-            na.out[blockIdx.x].lu = 0;
+            if constexpr (REC) {
+                rec->nees = acc;
+                rec->lu = 0;
+            } else {
+                na.out[blockIdx.x].sumsq = acc;
+                na.out[blockIdx.x].lu = 0;
+            }
         }
         return;
     }
@@ -856,9 +1027,19 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) {
         s += s_eps[j] * x[j];
     s = nees_block_sum(s, s_red);
     if (tid == 0) {
-        na.out[blockIdx.x].sumsq = s;
-        na.out[blockIdx.x].lu = 1;
+        if constexpr (REC) {
+            rec->nees = s;
+            rec->lu = 1;
+        } else {
+            na.out[blockIdx.x].sumsq = s;
+            na.out[blockIdx.x].lu = 1;
+        }
     }
+}
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_nees(const NeesArgs na) { batch_nees_body<false>(na, nullptr); }
+// eqf_batch_consistency: entry e's record at rec[e]; the host fills in the ids and divides the NEES by n
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_consistency(const NeesArgs na, eqf_batch_consistency_record* rec) {
+    batch_nees_body<true>(na, rec + blockIdx.x);
 }
 
 // augmentLandmarkStates (VIOFilter.cpp:112-132): removeOldLandmarks' compaction and addNewLandmarks (VIO_eqf.cpp:225-245), the two halves of k_batch_frame's

@@ -4049,9 +4049,10 @@ struct eqf_batch {
     int in_cap = 0, steps_cap = 0;
     NeesIn *h_nin = nullptr, *d_nin = nullptr; // eqf_batch_nees packets
     NeesOut *h_nout = nullptr, *d_nout = nullptr;
+    eqf_batch_consistency_record *h_rec = nullptr, *d_rec = nullptr; // eqf_batch_consistency records
     AugIn *h_ain = nullptr, *d_ain = nullptr; // eqf_batch_augment packets
     CopyIn *h_cin = nullptr, *d_cin = nullptr; // eqf_batch_copy_slots packets
-    int nin_cap = 0, nout_cap = 0, aug_cap = 0, copy_cap = 0;
+    int nin_cap = 0, nout_cap = 0, rec_cap = 0, aug_cap = 0, copy_cap = 0;
     std::vector<Slot> s;
 };
 
@@ -4234,6 +4235,9 @@ void eqf_batch_destroy(eqf_batch* b) {
     (void)hipFree(b->d_cin);
     if (b->h_cin)
         (void)hipHostFree(b->h_cin);
+    (void)hipFree(b->d_rec);
+    if (b->h_rec)
+        (void)hipHostFree(b->h_rec);
     if (b->stream)
         (void)hipStreamDestroy(b->stream);
     delete b;
@@ -4596,24 +4600,17 @@ template <typename T> int batch_grow_pair(T*& h, T*& d, int& cap, int n) {
 }
 } // namespace
 
-int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, double* nees, int* status) {
-    if (!b || count < 0 || (count > 0 && (!truths || !nees || !status)))
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    BatchDevice dev(b);
-    if (int rc = batch_grow_pair(b->h_nin, b->d_nin, b->nin_cap, count))
-        return rc;
-    if (int rc = batch_grow_pair(b->h_nout, b->d_nout, b->nout_cap, count))
-        return rc;
-    // host half: the sensor entries of eps (eqf_compute_nees's code), the true points in state order
-    std::vector<int> listed(b->slots, 0), in_of(count, -1), jt;
+namespace {
+// The host half eqf_batch_nees and eqf_batch_consistency share: the per-entry refusals, and for every accepted entry its packet in b->h_nin (the sensor
+// entries of eps - eqf_compute_nees's code -, the true points in state order). in_of[e]: entry e's packet, or -1; returns the packets.
+int batch_nees_pack(eqf_batch* b, int count, const eqf_batch_truth* truths, int* status, std::vector<int>& in_of) {
+    std::vector<int> listed(b->slots, 0), jt;
     std::vector<std::pair<int, int>> order;
+    in_of.assign(count, -1);
     int nin = 0;
     for (int e = 0; e < count; ++e) {
         const eqf_batch_truth& t = truths[e];
         status[e] = 0;
-        nees[e] = std::nan("");
         if (!batch_slot_ok(b, t.slot) || listed[t.slot] || !t.sensor || t.n_true < 0 || (t.n_true > 0 && (!t.ids || !t.p))) {
             status[e] = EQF_E_BAD_ARG;
             continue;
@@ -4646,8 +4643,9 @@ int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, doubl
                 in.p[3 * i + c] = t.p[3 * jt[i] + c];
         in_of[e] = nin++;
     }
-    if (nin == 0)
-        return 0;
+    return nin;
+}
+NeesArgs batch_nees_args(eqf_batch* b) {
     NeesArgs na;
     na.ld = b->ld;
     na.sig = b->d_sig;
@@ -4658,6 +4656,27 @@ int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, doubl
     na.scr_stride = b->scr_stride;
     na.in = b->d_nin;
     na.out = b->d_nout;
+    return na;
+}
+} // namespace
+
+int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, double* nees, int* status) {
+    if (!b || count < 0 || (count > 0 && (!truths || !nees || !status)))
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = batch_grow_pair(b->h_nin, b->d_nin, b->nin_cap, count))
+        return rc;
+    if (int rc = batch_grow_pair(b->h_nout, b->d_nout, b->nout_cap, count))
+        return rc;
+    for (int e = 0; e < count; ++e)
+        nees[e] = std::nan("");
+    std::vector<int> in_of;
+    const int nin = batch_nees_pack(b, count, truths, status, in_of);
+    if (nin == 0)
+        return 0;
+    const NeesArgs na = batch_nees_args(b);
     HIPCHK(hipMemcpyAsync(b->d_nin, b->h_nin, sizeof(NeesIn) * nin, hipMemcpyHostToDevice, b->stream));
     hipLaunchKernelGGL(k_batch_nees, dim3(nin), dim3(BATCH_T), 0, b->stream, na);
     HIPCHK(hipGetLastError());
@@ -4670,6 +4689,40 @@ int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, doubl
         eqf_batch::Slot& sl = b->s[truths[e].slot];
         nees[e] = o.sumsq / (double)(21 + 3 * (int)sl.ids.size());
         sl.nees_lu += o.lu;
+    }
+    return 0;
+}
+int eqf_batch_consistency(eqf_batch* b, int count, const eqf_batch_truth* truths, eqf_batch_consistency_record* out, int* status) {
+    if (!b || count < 0 || (count > 0 && (!truths || !out || !status)))
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = batch_grow_pair(b->h_nin, b->d_nin, b->nin_cap, count))
+        return rc;
+    if (int rc = batch_grow_pair(b->h_rec, b->d_rec, b->rec_cap, count))
+        return rc;
+    std::vector<int> in_of;
+    const int nin = batch_nees_pack(b, count, truths, status, in_of);
+    if (nin == 0)
+        return 0;
+    const NeesArgs na = batch_nees_args(b); // na.out is not used: the kernel writes the records
+    HIPCHK(hipMemcpyAsync(b->d_nin, b->h_nin, sizeof(NeesIn) * nin, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_consistency, dim3(nin), dim3(BATCH_T), 0, b->stream, na, b->d_rec);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_rec, b->d_rec, sizeof(eqf_batch_consistency_record) * nin, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        eqf_batch::Slot& sl = b->s[truths[e].slot];
+        eqf_batch_consistency_record& r = out[e];
+        r = b->h_rec[in_of[e]];
+        const int N = (int)sl.ids.size();
+        r.nees = r.nees / (double)(21 + 3 * N); // the kernel left eps^T Sigma^-1 eps there
+        for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
+            r.ids[i] = i < N ? sl.ids[i] : 0;
+        sl.nees_lu += r.lu;
     }
     return 0;
 }

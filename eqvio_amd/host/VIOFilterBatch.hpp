@@ -2,6 +2,7 @@
 // time, initialised flag; the EqF state lives in the device batch of include/eqf_batch.h), whose frames go to the device in one step.
 #pragma once
 #include "VIOFilter.hpp"
+#include "VIOWriter.hpp"
 #include "eqf_batch.h"
 #include <vector>
 
@@ -16,6 +17,11 @@ struct ImuSelection {
 };
 ImuSelection selectImu(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime);
 void trimImuBuffer(std::vector<IMUVelocity>& buffer, double currentTime);
+
+// One frame's rows of nees.csv, poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv and landmarkError.csv from a slot's consistency record
+// (eqf_batch_consistency), through VIOWriter's own row formatting: what writeConsistency and writeLandmarkError write for a single filter. landmarkError.csv
+// has one column per TRUE landmark (true_ids, the true state's order), NaN where the slot does not hold it.
+void writeConsistencyRecord(VIOWriter& writer, double stamp, const eqf_batch_consistency_record& record, int n_true, const int* true_ids);
 
 class VIOFilterBatch {
   public:

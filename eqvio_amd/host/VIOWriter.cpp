@@ -13,10 +13,13 @@ namespace {
 // One CSV line: elements formatted one by one with a default-precision stream, joined by ", " (CSVLine.h:84-89, 153-161)
 class Line {
     std::vector<std::string> data;
+    // One default-precision stream for all elements of the line (a landmarkError row has one per world point). Only plain values may be streamed into a Line:
+    // a manipulator or a failed insertion would carry its formatting state or fail bit over to the elements behind it.
+    std::ostringstream ss;
 
   public:
     template <typename T> Line& operator<<(const T& d) {
-        std::stringstream ss;
+        ss.str(std::string());
         ss << d;
         data.emplace_back(ss.str());
         return *this;
@@ -146,22 +149,56 @@ void VIOWriter::writeTiming(const LoopTimer::LoopTimingData& timingData) { // :9
     timingFile << line << '\n';
 }
 
-void VIOWriter::writeLandmarkError(const double& stamp, const VIOState& trueState, const VIOState& estState) { // :117-138
+void VIOWriter::writeLandmarkErrorRow(const double& stamp, const std::vector<double>& errors) { // :117-138, the row
     if (!landmarkErrorFile.is_open()) {
         landmarkErrorFile.open(outputDir + "landmarkError.csv");
         landmarkErrorFile << "time, lm_err_1, lm_err_2, ...\n";
     }
     stampPrefix(landmarkErrorFile, stamp);
+    Line line;
+    for (double e : errors)
+        line << e;
+    landmarkErrorFile << line << '\n';
+}
+
+void VIOWriter::writeLandmarkError(const double& stamp, const VIOState& trueState, const VIOState& estState) { // :117-138
     // one column per TRUE landmark, NaN where the filter does not hold it
     std::map<int, V3> est;
     for (const Landmark& lm : estState.cameraLandmarks)
         est.emplace(lm.id, lm.p);
-    Line line;
+    std::vector<double> errors;
     for (const Landmark& lm : trueState.cameraLandmarks) {
         const auto it = est.find(lm.id);
-        line << (it == est.end() ? std::nan("") : norm(it->second - lm.p));
+        errors.push_back(it == est.end() ? std::nan("") : norm(it->second - lm.p));
     }
-    landmarkErrorFile << line << '\n';
+    writeLandmarkErrorRow(stamp, errors);
+}
+
+void VIOWriter::writeNEESRow(const double& stamp, double fullNEES, int dof, double poseNEES, double attitudeNEES) { // :196-212, the row
+    if (!neesFile.is_open()) {
+        neesFile.open(outputDir + "nees.csv");
+        neesFile << "time, NEES, DoF, PoseNEES, AttitudeNEES\n";
+    }
+    stampPrefix(neesFile, stamp);
+    neesFile << (Line() << fullNEES << dof << poseNEES << attitudeNEES) << '\n';
+}
+
+void VIOWriter::writeConsistencyRow(ConsistencyFile which, const double& stamp, const double (&eps)[6], const double (&sigma2)[6]) { // :214-227, the row
+    static const char* const poseHeader = "time, eps_rx, eps_ry, eps_rz, eps_px, eps_py, eps_pz,Sigma2_rx, Sigma2_ry, Sigma2_rz, Sigma2_px, Sigma2_py, Sigma2_pz\n";
+    static const char* const biasHeader = "time, eps_gyr_x, eps_gyr_y, eps_gyr_z, eps_acc_x, eps_acc_y, eps_acc_z,Sigma2_gyr_x, Sigma2_gyr_y, Sigma2_gyr_z, Sigma2_acc_x, Sigma2_acc_y, "
+                                          "Sigma2_acc_z\n";
+    std::ofstream& f = which == PoseConsistency ? poseConsistencyFile : which == CameraConsistency ? cameraConsistencyFile : biasConsistencyFile;
+    if (!f.is_open()) {
+        f.open(outputDir + (which == PoseConsistency ? "poseConsistency.csv" : which == CameraConsistency ? "cameraConsistency.csv" : "biasConsistency.csv"));
+        f << (which == BiasConsistency ? biasHeader : poseHeader);
+    }
+    stampPrefix(f, stamp);
+    Line line;
+    for (double e : eps)
+        line << e;
+    for (double v : sigma2)
+        line << v;
+    f << line << '\n';
 }
 
 void VIOWriter::writeConsistency(const double& stamp, const VIOState& trueState, const VIO_eqf& filter) { // :140-228
@@ -200,11 +237,6 @@ void VIOWriter::writeConsistency(const double& stamp, const VIOState& trueState,
     V3 epsR, epsX;
     se3_log(pose_mul(pose_inv(xi0.sensor.pose), errorPose), epsR, epsX);
 
-    if (!neesFile.is_open()) {
-        neesFile.open(outputDir + "nees.csv");
-        neesFile << "time, NEES, DoF, PoseNEES, AttitudeNEES\n";
-    }
-    stampPrefix(neesFile, stamp);
     {
         double fullNEES = std::nan("");
         try {
@@ -223,43 +255,31 @@ void VIOWriter::writeConsistency(const double& stamp, const VIOState& trueState,
             for (int j = 0; j < 3; ++j)
                 P3[i][j] = S[6 + i][6 + j];
         const double attitudeNEES = quadInv<3>(P3, e3);
-        neesFile << (Line() << fullNEES << xi0.Dim() << poseNEES << attitudeNEES) << '\n';
+        writeNEESRow(stamp, fullNEES, xi0.Dim(), poseNEES, attitudeNEES);
     }
 
-    auto consistency = [&](std::ofstream& f, const char* name, const char* header, const double (&eps)[6], int s0) {
-        if (!f.is_open()) {
-            f.open(outputDir + name);
-            f << header;
-        }
-        stampPrefix(f, stamp);
-        Line line;
-        for (double e : eps)
-            line << e;
+    auto consistency = [&](ConsistencyFile which, const double (&eps)[6], int s0) {
+        double sigma2[6];
         for (int k = 0; k < 6; ++k)
-            line << S[s0 + k][s0 + k];
-        f << line << '\n';
+            sigma2[k] = S[s0 + k][s0 + k];
+        writeConsistencyRow(which, stamp, eps, sigma2);
     };
     {
         const double eps[6] = {epsR.x, epsR.y, epsR.z, epsX.x, epsX.y, epsX.z};
-        consistency(poseConsistencyFile, "poseConsistency.csv",
-                    "time, eps_rx, eps_ry, eps_rz, eps_px, eps_py, eps_pz,Sigma2_rx, Sigma2_ry, Sigma2_rz, Sigma2_px, Sigma2_py, Sigma2_pz\n", eps, 6);
+        consistency(PoseConsistency, eps, 6);
     }
     {
         const Pose errorCamera = pose_mul(pose_mul(X.A, trueState.sensor.cameraOffset), pose_inv(X.B));
         V3 r, x;
         se3_log(pose_mul(pose_inv(xi0.sensor.cameraOffset), errorCamera), r, x);
         const double eps[6] = {r.x, r.y, r.z, x.x, x.y, x.z};
-        consistency(cameraConsistencyFile, "cameraConsistency.csv",
-                    "time, eps_rx, eps_ry, eps_rz, eps_px, eps_py, eps_pz,Sigma2_rx, Sigma2_ry, Sigma2_rz, Sigma2_px, Sigma2_py, Sigma2_pz\n", eps, 15);
+        consistency(CameraConsistency, eps, 15);
     }
     {
         double eps[6];
         for (int k = 0; k < 6; ++k)
             eps[k] = trueState.sensor.inputBias[k] - X.beta[k] - xi0.sensor.inputBias[k];
-        consistency(biasConsistencyFile, "biasConsistency.csv",
-                    "time, eps_gyr_x, eps_gyr_y, eps_gyr_z, eps_acc_x, eps_acc_y, eps_acc_z,Sigma2_gyr_x, Sigma2_gyr_y, Sigma2_gyr_z, Sigma2_acc_x, Sigma2_acc_y, "
-                    "Sigma2_acc_z\n",
-                    eps, 0);
+        consistency(BiasConsistency, eps, 0);
     }
 }
 

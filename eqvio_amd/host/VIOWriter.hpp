@@ -25,6 +25,13 @@ class VIOWriter {
     void writeTiming(const LoopTimer::LoopTimingData& timingData);
     void writeLandmarkError(const double& stamp, const VIOState& trueState, const VIOState& estState);
     void writeConsistency(const double& stamp, const VIOState& trueState, const VIO_eqf& filter);
+
+    // The rows of the consistency files from numbers already in hand: writeLandmarkError and writeConsistency format their rows through these, and so does
+    // the filter batch's recorded run (eqvio_batch_run_sim_recorded), whose numbers come from the device's consistency records.
+    enum ConsistencyFile { PoseConsistency, CameraConsistency, BiasConsistency };
+    void writeLandmarkErrorRow(const double& stamp, const std::vector<double>& errors); // one per TRUE landmark, NaN where the filter does not hold it
+    void writeNEESRow(const double& stamp, double fullNEES, int dof, double poseNEES, double attitudeNEES);
+    void writeConsistencyRow(ConsistencyFile which, const double& stamp, const double (&eps)[6], const double (&sigma2)[6]);
 };
 
 } // namespace eqvio_amd

@@ -22,7 +22,7 @@ static void usage() {
     std::puts("usage: eqvio_sim [--duration S] [--trajectory wave|square|sine|line] [--numPoints N] [--numWalls W] [--wallDistance D]\n"
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
               "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
-              "                 [--sweep NAME=v0,v1,...] [--innovation]\n"
+              "                 [--sweep NAME=v0,v1,...] [--innovation] [--record DIR]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
               "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
@@ -33,11 +33,14 @@ static void usage() {
               "              mean NEES. The simulated data are those of the unswept settings. Needs exactly B values.\n"
               "  --innovation   with --batch B: behind those lines, one line per run with the number of vision updates, the mean normalised innovation\n"
               "              squared per degree of freedom (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood\n"
-              "              (eqvio_batch_innovation_totals). Needs no true state, unlike NEES.");
+              "              (eqvio_batch_innovation_totals). Needs no true state, unlike NEES.\n"
+              "  --record DIR   with --batch B: writes every run's consistency record to DIR/run_<k>/ - nees.csv (NEES, PoseNEES, AttitudeNEES),\n"
+              "              poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv and landmarkError.csv, in the formats of --output - from one\n"
+              "              launch per frame for all runs (eqvio_batch_run_sim_recorded).");
 }
 
 // --batch B: the default-mode loop of main() for B seeds in lockstep, through eqvio_batch_run_sim (augment, vision step and NEES: one launch each per frame)
-static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep, bool innovation) {
+static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep, bool innovation, const std::string& recordDir) {
     const bool swept = !sweep.name.empty();
     eqvio_sim_settings ss;
     eqvio_sim_default_settings(&ss);
@@ -90,10 +93,11 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
     std::vector<double> nees((size_t)maxFrames * B);
     int frames = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    rc = eqvio_batch_run_sim(b, sims.data(), maxFrames, nees.data(), &frames);
+    rc = recordDir.empty() ? eqvio_batch_run_sim(b, sims.data(), maxFrames, nees.data(), &frames)
+                           : eqvio_batch_run_sim_recorded(b, sims.data(), maxFrames, nees.data(), &frames, recordDir.c_str());
     const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc) {
-        std::fprintf(stderr, "eqvio_sim: eqvio_batch_run_sim: %s\n", rc == -1 ? eqvio_batch_last_error(b) : eqf_error_string(rc));
+        std::fprintf(stderr, "eqvio_sim: %s: %s\n", recordDir.empty() ? "eqvio_batch_run_sim" : "eqvio_batch_run_sim_recorded", rc == -1 ? eqvio_batch_last_error(b) : eqf_error_string(rc));
         eqvio_batch_destroy(b);
         release();
         return 1;
@@ -136,7 +140,7 @@ int main(int argc, char** argv) {
     int batch = 0;
     Sweep sweep;
     bool haveSweep = false;
-    std::string outputDir, datasetDir;
+    std::string outputDir, datasetDir, recordDir;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         std::function<const char*()> val = [&]() -> const char* {
@@ -166,6 +170,7 @@ int main(int argc, char** argv) {
         else if (a == "--sigmaFP32") sigmaFP32 = true;
         else if (a == "--batch") batch = std::atoi(val());
         else if (a == "--innovation") innovation = true;
+        else if (a == "--record") recordDir = val();
         else if (a == "--sweep") {
             sweep = parseSweep(val());
             haveSweep = true;
@@ -182,6 +187,10 @@ int main(int argc, char** argv) {
     }
     if (innovation && batch == 0) {
         std::fprintf(stderr, "eqvio_sim: --innovation needs --batch B (the statistics are the filter batch's)\n");
+        return 2;
+    }
+    if (!recordDir.empty() && batch == 0) {
+        std::fprintf(stderr, "eqvio_sim: --record needs --batch B (the records are the filter batch's; a single run writes them with --output)\n");
         return 2;
     }
     if (batch != 0) { // what the filter batch refuses, before any device is opened
@@ -206,7 +215,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        return runBatch(sim, fs, batch, quiet, sweep, innovation);
+        return runBatch(sim, fs, batch, quiet, sweep, innovation, recordDir);
     }
     double lastLandmarkReset = landmarkResetTime > 0 ? 0.0 : std::nan("");
 

@@ -135,6 +135,33 @@ int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, doubl
 /* how many eqf_batch_nees entries of the slot took the partial-pivot fallback */
 int eqf_batch_nees_lu_fallbacks(const eqf_batch* b, int slot, long* count);
 
+/* The blocks of the sensor state a consistency record reports, and their rows of eps / Sigma (nees_sensor_error's order: gyroscope and accelerometer bias,
+ * attitude, position, velocity, camera attitude and position): 0..5, 6..8, 9..11, 6..11, 12..14, 15..20, 0..20. */
+enum { EQF_BLOCK_BIAS, EQF_BLOCK_ATTITUDE, EQF_BLOCK_POSITION, EQF_BLOCK_POSE, EQF_BLOCK_VELOCITY, EQF_BLOCK_CAMERA, EQF_BLOCK_SENSOR, EQF_BATCH_NBLOCKS };
+
+/* One slot's consistency record: what the reference's Monte-Carlo study writes per frame (VIOWriter::writeConsistency, writeLandmarkError) beside the full NEES.
+ * n = 21 + 3 N. Entries of the fixed-size arrays beyond n or N read 0. */
+typedef struct eqf_batch_consistency_record {
+    int N, lu;                       /* landmarks of the slot; 1: the full NEES took the partial-pivot fallback */
+    double nees;                     /* as eqf_batch_nees: eps^T Sigma^-1 eps / n */
+    double block[EQF_BATCH_NBLOCKS]; /* x^T M^-1 x of the block, NOT divided by its dof (nees.csv's PoseNEES / AttitudeNEES) */
+    double eps[21 + 3 * EQF_BATCH_MAX_LANDMARKS];        /* the eps computeNEES forms */
+    double sigma_diag[21 + 3 * EQF_BATCH_MAX_LANDMARKS]; /* the diagonal of Sigma */
+    int ids[EQF_BATCH_MAX_LANDMARKS];                    /* state order */
+    double lm_quad[EQF_BATCH_MAX_LANDMARKS];             /* eps_i^T Sigma_ii^-1 eps_i, 3 x 3 marginal of landmark i */
+    double lm_err[EQF_BATCH_MAX_LANDMARKS];              /* |p_hat_i - p_true_i|, camera frame (landmarkError.csv) */
+} eqf_batch_consistency_record;
+
+/* The consistency record of the `count` listed slots (distinct): one packet to the device, one launch (one workgroup per accepted entry), one copy back, one
+ * synchronisation; nothing but the records crosses to the host. Arguments, refusals and codes are eqf_batch_nees's (status[e] 0 or EQF_E_BAD_ARG; the call
+ * returns EQF_E_BAD_ARG for null arguments or count < 0), checked before any device is looked at; a refused entry's record is left untouched. out[e].nees and
+ * out[e].lu are, bit for bit, what eqf_batch_nees gives for the same entry (the same factorisation, the same fallback), and the fallback counts in
+ * eqf_batch_nees_lu_fallbacks in the same way. The block forms and the landmarks' 3 x 3 forms are x^T M^-1 x by Gaussian elimination with partial pivoting on
+ * [M | x] (the reference's .inverse() route); a zero pivot gives a non-finite value, reported as it is. The landmark's point estimate is
+ * eqf_batch_state_estimate's. The call is read-only like eqf_batch_nees: no slot's state, Sigma, landmark planes, settings, innovation totals or last result
+ * change. */
+int eqf_batch_consistency(eqf_batch* b, int count, const eqf_batch_truth* truths, eqf_batch_consistency_record* out, int* status);
+
 /* One slot's augmentLandmarkStates for eqf_batch_augment: the ids the slot keeps and adds (n_new), and the provided state's landmarks (n_prov ids and
  * camera-frame points) the new ones are taken from. */
 typedef struct eqf_batch_augment_entry {

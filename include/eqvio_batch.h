@@ -55,6 +55,11 @@ int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot
  * Returns 0, EQF_E_BAD_ARG or a HIP error. */
 int eqvio_batch_compute_nees(eqvio_batch* b, int count, const int* slots, const double* true_sensor_all, const int* true_counts, const int* true_ids_all,
                              const double* true_p_all, double* nees, int* status);
+/* The consistency record of `count` distinct slots in ONE launch (eqf_batch_consistency, include/eqf_batch.h): the argument list of eqvio_batch_compute_nees
+ * with the records in place of nees. out[e].nees is eqvio_batch_compute_nees's value bit for bit; a refused entry's record is left untouched. Returns 0,
+ * EQF_E_BAD_ARG or a HIP error. */
+int eqvio_batch_consistency(eqvio_batch* b, int count, const int* slots, const double* true_sensor_all, const int* true_counts, const int* true_ids_all,
+                            const double* true_p_all, eqf_batch_consistency_record* out, int* status);
 /* augmentLandmarkStates(newIds, providedState) (VIOFilter.cpp:112-132) of `count` distinct slots in ONE launch (eqf_batch_augment). Entry e: slot slots[e],
  * new_counts[e] ids from new_ids_all, prov_counts[e] provided landmarks from prov_ids_all / prov_p_all. status[e] as eqf_batch_augment. Returns 0,
  * EQF_E_BAD_ARG or a HIP error. */
@@ -66,6 +71,13 @@ int eqvio_batch_augment_landmark_states(eqvio_batch* b, int count, const int* sl
  * call (getTrueState(time)) for every slot that has a frame. nees: max_frames x slots, row-major [frame][slot], NaN where a slot has no frame. Runs until
  * every sim has ended or max_frames frames have run; *frames_run = frames run. Returns 0, EQF_E_BAD_ARG, or -1 (a call failed: eqvio_batch_last_error). */
 int eqvio_batch_run_sim(eqvio_batch* b, eqvio_sim* const* sims, int max_frames, double* nees, int* frames_run);
+/* eqvio_batch_run_sim with the frame's NEES launch replaced by the consistency launch (eqf_batch_consistency): the same loop, the same nees array bit for
+ * bit, and for every slot k with a sim the directory output_dir/run_<k>/ with the reference's consistency files of that run - nees.csv (NEES, DoF, PoseNEES,
+ * AttitudeNEES), poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv (the error components and the matching diagonal entries of Sigma) and
+ * landmarkError.csv (one column per TRUE landmark, NaN where the slot does not hold it) - with the headers, column order and number formatting of the single
+ * filter's `eqvio_sim --output` (VIOWriter). One row per frame the slot ran; a slot without a frame writes no row, and a file appears with its first row.
+ * Only the records cross to the host. An output_dir that cannot be created gives -1 (eqvio_batch_last_error) before any frame runs; a null one EQF_E_BAD_ARG. */
+int eqvio_batch_run_sim_recorded(eqvio_batch* b, eqvio_sim* const* sims, int max_frames, double* nees, int* frames_run, const char* output_dir);
 
 /* per slot: stateEstimate, viewEqFState (xi0, X, Sigma), getTime, isInitialised, and the forcing of a whole EqF state (teacher forcing) */
 int eqvio_batch_state_estimate(eqvio_batch* b, int slot, double* sensor, int* ids, double* p, int cap); /* returns N or < 0 */
