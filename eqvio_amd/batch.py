@@ -52,6 +52,19 @@ class BatchConsistencyRecord(C.Structure):
                 "ids": np.array(self.ids, dtype=np.int32)[:N], "lm_quad": np.array(self.lm_quad)[:N], "lm_err": np.array(self.lm_err)[:N]}
 
 
+class BatchEstimateRecord(C.Structure):
+    """eqf_batch_estimate_record (include/eqf_batch.h)."""
+
+    _fields_ = [("N", C.c_int), ("reserved", C.c_int), ("sensor", C.c_double * 23), ("sigma_sensor", C.c_double * (21 * 21)),
+                ("ids", C.c_int * EQF_BATCH_MAX_LANDMARKS), ("p", C.c_double * (3 * EQF_BATCH_MAX_LANDMARKS)), ("p_world", C.c_double * (3 * EQF_BATCH_MAX_LANDMARKS))]
+
+    def trimmed(self):
+        """The record as a dict of numpy arrays trimmed to N: sensor[23], sigma_sensor (21, 21), ids[N], p (N, 3), p_world (N, 3)."""
+        N = self.N
+        return {"N": N, "sensor": np.array(self.sensor), "sigma_sensor": np.array(self.sigma_sensor).reshape(21, 21).T.copy(),
+                "ids": np.array(self.ids, dtype=np.int32)[:N], "p": np.array(self.p)[: 3 * N].reshape(N, 3), "p_world": np.array(self.p_world)[: 3 * N].reshape(N, 3)}
+
+
 def load_batch_protos():
     """Declare the prototypes of include/eqf_batch.h on libeqf_hip.so and of include/eqvio_batch.h on libeqvio_filter.so."""
     elib, flib = load_eqf_lib(), load_filter_lib()
@@ -79,6 +92,7 @@ def load_batch_protos():
         "eqf_batch_nees": (C.c_int, [vp, C.c_int, P(BatchTruth), c_double_p, c_int_p]),
         "eqf_batch_nees_lu_fallbacks": (C.c_int, [vp, C.c_int, P(C.c_long)]),
         "eqf_batch_consistency": (C.c_int, [vp, C.c_int, P(BatchTruth), P(BatchConsistencyRecord), c_int_p]),
+        "eqf_batch_estimates": (C.c_int, [vp, C.c_int, c_int_p, P(BatchEstimateRecord), c_int_p]),
         "eqf_batch_augment": (C.c_int, [vp, C.c_int, P(BatchAugmentEntry), c_int_p]),
         "eqf_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
         "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
@@ -96,6 +110,8 @@ def load_batch_protos():
         "eqvio_batch_process_imu": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqvio_batch_process_vision": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, P(Camera), c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
+        "eqvio_batch_run_prepared_recorded": (C.c_int, [vp, P(vp), C.c_int, C.c_int, C.c_char_p]),
+        "eqvio_batch_estimates": (C.c_int, [vp, C.c_int, c_int_p, P(BatchEstimateRecord), c_double_p, c_int_p]),
         "eqvio_batch_state_estimate": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int]),
         "eqvio_batch_get_eqf": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
         "eqvio_batch_force_eqf": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int, c_double_p]),
@@ -209,18 +225,33 @@ class VIOFilterBatch:
         self._chk(self.lib.eqvio_batch_process_vision(self.h, n, _ip(slots), _dp(stamps), cams, _ip(counts), _ip(ids), _dp(y), _ip(status)))
         return status[:n].copy()
 
-    def run_prepared(self, sequences, first=0, count=None):
+    def run_prepared(self, sequences, first=0, count=None, record_dir=None):
         """Lockstep replay (eqvio_batch_run_prepared): sequences[k] is slot k's capi.PreparedFrames (or None); frame j of every slot goes in one device step, a
-        slot whose sequence has ended sits out. Returns the number of steps run."""
+        slot whose sequence has ended sits out. Returns the number of steps run. With record_dir every slot's IMUState.csv, camera.csv, bias.csv and points.csv
+        go to record_dir/run_<k>/, one row per frame the slot ran (eqvio_batch_run_prepared_recorded); the slots end in the same state, bit for bit."""
         if len(sequences) > self.slots:
             raise ValueError("more sequences than slots")
         arr = (C.c_void_p * self.slots)(*([q.h if q is not None else None for q in sequences] + [None] * (self.slots - len(sequences))))
         n = max(len(q) for q in sequences if q is not None)
         count = n - first if count is None else count
-        rc = self.lib.eqvio_batch_run_prepared(self.h, arr, first, count)
+        if record_dir is None:
+            rc = self.lib.eqvio_batch_run_prepared(self.h, arr, first, count)
+        else:
+            rc = self.lib.eqvio_batch_run_prepared_recorded(self.h, arr, first, count, os.fsencode(record_dir))
         if rc < 0:
             self._chk(rc)
         return rc
+
+    def state_estimates(self, slots, rec=None):
+        """The estimate records of the listed slots in ONE launch (eqvio_batch_estimates): returns (records, times, status) - the untrimmed BatchEstimateRecord
+        array (rec, or a new zeroed one; a refused entry's record is left as it was; .trimmed() gives numpy arrays), each slot's get_time() and the per-entry
+        status codes. Only the records cross to the host."""
+        n = len(slots)
+        sl = _i32(list(slots) if n else np.zeros(1, np.int32))
+        rec = (BatchEstimateRecord * max(n, 1))() if rec is None else rec
+        times, status = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_estimates(self.h, n, _ip(sl), rec, _dp(times), _ip(status)))
+        return rec, times[:n].copy(), status[:n].copy()
 
     def compute_nees(self, entries):
         """entries: list of (slot, true_sensor[23], true_ids, true_p[n, 3]). viewEqFState().computeNEES of every listed slot in ONE launch; returns the NEES

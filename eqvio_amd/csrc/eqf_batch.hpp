@@ -1150,4 +1150,40 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_copy(const CopyArgs ca) {
     }
 }
 
+// eqf_batch_estimates (include/eqf_batch.h): entry e's workgroup reads its slot's CURRENT landmark planes and Sigma buffer and writes, into rec[e], the
+// landmarks' camera-frame points p = Q^-1 q0 (eqf_batch_state_estimate's expression, the one k_batch_consistency uses for lm_err), their world-frame points
+// pc * p with pc = pose * cameraOffset given by the host, and the 21 x 21 sensor block of Sigma, column-major - plain copies, so that block is Sigma's bit
+// for bit. Entries of p / p_world beyond N are written as 0. N, the ids and the sensor estimate are the host's and are filled in there. The kernel writes
+// nothing but the record: no LDS, no scratch area, no reduction - a record's bytes do not depend on the launch it is part of.
+struct EstIn {
+    int slot, cur, N, pad;
+    Pose pc; // pose * cameraOffset of the slot's sensor estimate
+};
+struct EstArgs {
+    int ld;
+    const double* sig;
+    const double* lm;
+    size_t sig_stride, lm_stride;
+    const EstIn* in;
+    eqf_batch_estimate_record* rec;
+};
+__global__ void __launch_bounds__(BATCH_T) k_batch_estimate(const EstArgs ea) {
+    const EstIn& in = ea.in[blockIdx.x];
+    eqf_batch_estimate_record* rec = ea.rec + blockIdx.x;
+    const int tid = threadIdx.x, L = BATCH_L, ld = ea.ld, N = in.N;
+    const double* S = ea.sig + (2 * (size_t)in.slot + in.cur) * ea.sig_stride;
+    const double* lm = ea.lm + (2 * (size_t)in.slot + in.cur) * ea.lm_stride;
+    for (int i = tid; i < BATCH_L; i += BATCH_T) {
+        V3 ph{0.0, 0.0, 0.0}, pw{0.0, 0.0, 0.0};
+        if (i < N) {
+            ph = (1.0 / lm[BATCH_QA * L + i]) * q_rot(q_inv(ldq(lm + BATCH_QQ * L, L, i)), ld3(lm, L, i));
+            pw = pose_act(in.pc, ph);
+        }
+        rec->p[3 * i] = ph.x, rec->p[3 * i + 1] = ph.y, rec->p[3 * i + 2] = ph.z;
+        rec->p_world[3 * i] = pw.x, rec->p_world[3 * i + 1] = pw.y, rec->p_world[3 * i + 2] = pw.z;
+    }
+    for (int t = tid; t < 441; t += BATCH_T)
+        rec->sigma_sensor[t] = S[t % 21 + (size_t)(t / 21) * ld];
+}
+
 } // namespace eqf

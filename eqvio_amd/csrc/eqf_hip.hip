@@ -4052,7 +4052,9 @@ struct eqf_batch {
     eqf_batch_consistency_record *h_rec = nullptr, *d_rec = nullptr; // eqf_batch_consistency records
     AugIn *h_ain = nullptr, *d_ain = nullptr; // eqf_batch_augment packets
     CopyIn *h_cin = nullptr, *d_cin = nullptr; // eqf_batch_copy_slots packets
-    int nin_cap = 0, nout_cap = 0, rec_cap = 0, aug_cap = 0, copy_cap = 0;
+    EstIn *h_ein = nullptr, *d_ein = nullptr;  // eqf_batch_estimates packets
+    eqf_batch_estimate_record *h_erec = nullptr, *d_erec = nullptr; // eqf_batch_estimates records
+    int nin_cap = 0, nout_cap = 0, rec_cap = 0, aug_cap = 0, copy_cap = 0, ein_cap = 0, erec_cap = 0;
     std::vector<Slot> s;
 };
 
@@ -4238,6 +4240,12 @@ void eqf_batch_destroy(eqf_batch* b) {
     (void)hipFree(b->d_rec);
     if (b->h_rec)
         (void)hipHostFree(b->h_rec);
+    (void)hipFree(b->d_ein);
+    if (b->h_ein)
+        (void)hipHostFree(b->h_ein);
+    (void)hipFree(b->d_erec);
+    if (b->h_erec)
+        (void)hipHostFree(b->h_erec);
     if (b->stream)
         (void)hipStreamDestroy(b->stream);
     delete b;
@@ -4723,6 +4731,72 @@ int eqf_batch_consistency(eqf_batch* b, int count, const eqf_batch_truth* truths
         for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
             r.ids[i] = i < N ? sl.ids[i] : 0;
         sl.nees_lu += r.lu;
+    }
+    return 0;
+}
+// One packet, one launch of k_batch_estimate over the accepted entries, one copy back, one synchronisation. The host's part of a record (N, ids, the sensor
+// estimate by eqf_batch_state_estimate's expression) is written into out[e] after the copy; a refused entry's out[e] is never touched.
+int eqf_batch_estimates(eqf_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, int* status) {
+    if (!b || count < 0 || !slots || !out || !status)
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    std::vector<int> listed(b->slots, 0), in_of(count, -1);
+    int nin = 0;
+    for (int e = 0; e < count; ++e) { // the refusals, before any device is looked at
+        status[e] = 0;
+        if (!batch_slot_ok(b, slots[e]) || listed[slots[e]]) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        listed[slots[e]] = 1;
+        in_of[e] = nin++;
+    }
+    if (nin == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = batch_grow_pair(b->h_ein, b->d_ein, b->ein_cap, nin))
+        return rc;
+    if (int rc = batch_grow_pair(b->h_erec, b->d_erec, b->erec_cap, nin))
+        return rc;
+    std::vector<SensorState> est(nin);
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        const eqf_batch::Slot& sl = b->s[slots[e]];
+        EstIn& in = b->h_ein[in_of[e]];
+        in.slot = slots[e];
+        in.cur = sl.cur;
+        in.N = (int)sl.ids.size();
+        in.pad = 0;
+        est[in_of[e]] = sensor_action(sl.X, sl.xi0);
+        in.pc = pose_mul(est[in_of[e]].pose, est[in_of[e]].cam);
+    }
+    EstArgs ea;
+    ea.ld = b->ld;
+    ea.sig = b->d_sig;
+    ea.lm = b->d_lm;
+    ea.sig_stride = b->sig_stride;
+    ea.lm_stride = b->lm_stride;
+    ea.in = b->d_ein;
+    ea.rec = b->d_erec;
+    HIPCHK(hipMemcpyAsync(b->d_ein, b->h_ein, sizeof(EstIn) * nin, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_estimate, dim3(nin), dim3(BATCH_T), 0, b->stream, ea);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_erec, b->d_erec, sizeof(eqf_batch_estimate_record) * nin, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int e = 0; e < count; ++e) {
+        if (in_of[e] < 0)
+            continue;
+        const eqf_batch::Slot& sl = b->s[slots[e]];
+        eqf_batch_estimate_record& r = out[e];
+        r = b->h_erec[in_of[e]]; // p, p_world, sigma_sensor
+        const int N = (int)sl.ids.size();
+        r.N = N;
+        r.reserved = 0;
+        pack_sensor(est[in_of[e]], r.sensor);
+        for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
+            r.ids[i] = i < N ? sl.ids[i] : 0;
     }
     return 0;
 }

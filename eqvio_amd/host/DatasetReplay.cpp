@@ -1,5 +1,6 @@
 // See DatasetReplay.hpp.
 #include "DatasetReplay.hpp"
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <sstream>
@@ -132,6 +133,43 @@ std::vector<StampedPose> TrackReplayServer::groundtruth(const std::string& fileN
         }
     }
     return poses;
+}
+
+TrajectoryScore trajectoryPositionRMSE(const std::vector<StampedPose>& est, const std::vector<StampedPose>& gt) {
+    TrajectoryScore score{std::nan(""), 0};
+    if (gt.empty())
+        return score;
+    const bool ascending = std::is_sorted(gt.begin(), gt.end(), [](const StampedPose& a, const StampedPose& b) { return a.t < b.t; });
+    // the first ground-truth pose of the smallest |t - stamp|: a scan in file order, or, on ascending stamps, the two neighbours of the stamp
+    const auto nearest = [&](double t) {
+        size_t k = 0;
+        if (ascending) {
+            const size_t hi = std::lower_bound(gt.begin(), gt.end(), t, [](const StampedPose& g, double v) { return g.t < v; }) - gt.begin();
+            k = hi == gt.size() ? hi - 1 : hi;
+            while (k > 0 && std::fabs(gt[k - 1].t - t) <= std::fabs(gt[k].t - t))
+                --k; // the earlier one on a tie (equal stamps included)
+        } else {
+            for (size_t j = 0; j < gt.size(); ++j)
+                if (std::fabs(gt[j].t - t) < std::fabs(gt[k].t - t))
+                    k = j;
+        }
+        return k;
+    };
+    Pose A = eqf::pose_identity();
+    double sum = 0.0;
+    for (const StampedPose& e : est) {
+        if (e.t < 0)
+            continue;
+        const Pose& g = gt[nearest(e.t)].pose;
+        if (score.frames == 0)
+            A = eqf::pose_mul(g, eqf::pose_inv(e.pose));
+        const V3 d = eqf::pose_act(A, e.pose.x) - g.x;
+        sum += d.x * d.x + d.y * d.y + d.z * d.z;
+        ++score.frames;
+    }
+    if (score.frames > 0)
+        score.rmse = std::sqrt(sum / score.frames);
+    return score;
 }
 
 namespace {

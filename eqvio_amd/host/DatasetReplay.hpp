@@ -42,6 +42,16 @@ class TrackReplayServer {
     static std::vector<StampedPose> groundtruth(const std::string& fileName, DatasetFormat format);
 };
 
+// The position error of an estimated trajectory against ground truth, after aligning the first poses (what a tuning of a dataset replay is finally judged
+// by; `eqvio_opt --batch B --groundtruth FILE` prints it per slot). Frames with stamp < 0 (a filter that has not initialised) are skipped. g_j is the
+// ground-truth pose nearest in time to frame j, the earlier one on a tie (the rule main() uses for its last pose); A = g_0 e_0^-1 from the first kept frame;
+// rmse = sqrt(mean_j |pos(A e_j) - pos(g_j)|^2) over the kept frames. No kept frame or no ground truth: NaN and 0 frames.
+struct TrajectoryScore {
+    double rmse;
+    int frames;
+};
+TrajectoryScore trajectoryPositionRMSE(const std::vector<StampedPose>& est, const std::vector<StampedPose>& gt);
+
 // The camera file of a dataset (main_opt.cpp:114-147: intrinsics for the measurement's camera, extrinsics into settings.cameraOffset), the subset of YAML the two
 // readers consume - yaml-cpp is not in this image, so the few keys are picked out of the text directly:
 //   ASL / EuRoC  mav0/cam0/sensor.yaml (ASLDatasetReader.cpp:76-101): resolution [w, h], intrinsics [fu, fv, cu, cv], distortion_coefficients [k1, k2, p1, p2 (, k3)]

@@ -4,6 +4,7 @@
 #include "PreparedFrames.hpp"
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <array>
 #include <map>
@@ -58,6 +59,21 @@ void writeConsistencyRecord(VIOWriter& writer, double stamp, const eqf_batch_con
         errors[j] = it == held.end() ? std::nan("") : it->second;
     }
     writer.writeLandmarkErrorRow(stamp, errors);
+}
+
+void writeEstimateRecord(VIOWriter& writer, double stamp, const eqf_batch_estimate_record& r) {
+    writer.writeSensorRows(stamp, r.sensor);
+    writer.writePointsRow(stamp, r.N, r.ids, r.p_world);
+}
+std::unique_ptr<VIOWriter> makeRunWriter(const std::string& output_dir, int k) {
+    const std::string dir = output_dir + "/run_" + std::to_string(k);
+    auto writer = std::make_unique<VIOWriter>(dir);
+    struct stat st;
+    if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode))
+        throw std::runtime_error("cannot create the output directory " + dir);
+    for (const char* name : {"IMUState.csv", "camera.csv", "bias.csv", "points.csv"})
+        std::remove((dir + "/" + name).c_str());
+    return writer;
 }
 
 namespace {
@@ -390,12 +406,27 @@ int eqvio_batch_copy_slots(eqvio_batch* b, int count, const int* src, const int*
         return EQF_E_BAD_ARG;
     return guarded(b, [&] { b->f->copySlots(count, src, dst, status); });
 }
-int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count) {
-    if (!b || !per_slot || first < 0 || count < 0)
+int eqvio_batch_estimates(eqvio_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, double* times, int* status) {
+    if (!b || count < 0 || !slots || !out || !status)
         return EQF_E_BAD_ARG;
+    const int rc = eqf_batch_estimates(b->f->core(), count, slots, out, status);
+    for (int e = 0; e < count && rc == 0 && times; ++e)
+        times[e] = eqvio_batch_get_time(b, slots[e]); // -1 for a slot that has not initialised (and for a refused index)
+    return rc;
+}
+
+namespace {
+// eqvio_batch_run_prepared (output_dir null) and eqvio_batch_run_prepared_recorded: one loop; the recorded one reads the estimates of the slots that had a
+// frame after every step (eqf_batch_estimates is read-only, so the slots end in the same state bit for bit) and writes their rows
+int run_prepared_loop(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count, const char* output_dir) {
     const int B = b->f->slots();
     int steps = 0;
     const int rc = guarded(b, [&] {
+        std::vector<std::unique_ptr<eqvio_amd::VIOWriter>> writers(B); // output_dir/run_<k>/ of every slot with a sequence, before any frame runs
+        for (int k = 0; k < B && output_dir; ++k)
+            if (per_slot[k])
+                writers[k] = eqvio_amd::makeRunWriter(output_dir, k);
+        std::vector<eqf_batch_estimate_record> rec;
         std::vector<int> slots, status;
         std::vector<const eqvio_amd::VisionMeasurement*> meas;
         slots.reserve(B), status.reserve(B), meas.reserve(B);
@@ -417,10 +448,30 @@ int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot
             for (size_t e = 0; e < slots.size(); ++e)
                 if (status[e] != 0)
                     throw std::runtime_error("frame " + std::to_string(j) + ", slot " + std::to_string(slots[e]) + ": " + eqf_error_string(status[e]));
+            if (output_dir) {
+                rec.resize(slots.size());
+                eqvio_amd::check(eqf_batch_estimates(b->f->core(), (int)slots.size(), slots.data(), rec.data(), status.data()), "eqf_batch_estimates");
+                for (size_t e = 0; e < slots.size(); ++e) {
+                    if (status[e] != 0)
+                        throw std::runtime_error("estimates, frame " + std::to_string(j) + ", slot " + std::to_string(slots[e]) + ": " + eqf_error_string(status[e]));
+                    eqvio_amd::writeEstimateRecord(*writers[slots[e]], b->f->slot(slots[e]).currentTime, rec[e]);
+                }
+            }
             ++steps;
         }
     });
     return rc ? rc : steps;
+}
+} // namespace
+int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count) {
+    if (!b || !per_slot || first < 0 || count < 0)
+        return EQF_E_BAD_ARG;
+    return run_prepared_loop(b, per_slot, first, count, nullptr);
+}
+int eqvio_batch_run_prepared_recorded(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count, const char* output_dir) {
+    if (!b || !per_slot || first < 0 || count < 0 || !output_dir)
+        return EQF_E_BAD_ARG;
+    return run_prepared_loop(b, per_slot, first, count, output_dir);
 }
 
 namespace {

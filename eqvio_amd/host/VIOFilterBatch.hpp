@@ -4,6 +4,8 @@
 #include "VIOFilter.hpp"
 #include "VIOWriter.hpp"
 #include "eqf_batch.h"
+#include <memory>
+#include <string>
 #include <vector>
 
 namespace eqvio_amd {
@@ -22,6 +24,12 @@ void trimImuBuffer(std::vector<IMUVelocity>& buffer, double currentTime);
 // (eqf_batch_consistency), through VIOWriter's own row formatting: what writeConsistency and writeLandmarkError write for a single filter. landmarkError.csv
 // has one column per TRUE landmark (true_ids, the true state's order), NaN where the slot does not hold it.
 void writeConsistencyRecord(VIOWriter& writer, double stamp, const eqf_batch_consistency_record& record, int n_true, const int* true_ids);
+// One frame's rows of IMUState.csv, camera.csv, bias.csv and points.csv from a slot's estimate record (eqf_batch_estimates), through VIOWriter's own row
+// formatting: what writeStates writes for a single filter. points.csv takes the record's p_world.
+void writeEstimateRecord(VIOWriter& writer, double stamp, const eqf_batch_estimate_record& record);
+// output_dir/run_<k>/ as a VIOWriter whose four state files start anew: the directory is made, files of an earlier run are removed (a file appears with its
+// first row). Throws when the directory cannot be created.
+std::unique_ptr<VIOWriter> makeRunWriter(const std::string& output_dir, int k);
 
 class VIOFilterBatch {
   public:

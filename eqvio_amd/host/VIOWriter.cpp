@@ -72,6 +72,23 @@ template <int K> double quadInv(const double (&M)[K][K], const double (&x)[K]) {
         q += x[i] * y[i];
     return q;
 }
+// the sensor state in eqvio_types.h's flat layout (bias, pose quaternion and position, velocity, camera offset) and back: plain copies
+void sensorToFlat(const VIOSensorState& se, double (&s)[23]) {
+    const double v[23] = {se.inputBias[0], se.inputBias[1], se.inputBias[2], se.inputBias[3], se.inputBias[4], se.inputBias[5], se.pose.R.w, se.pose.R.x, se.pose.R.y,
+                          se.pose.R.z, se.pose.x.x, se.pose.x.y, se.pose.x.z, se.velocity.x, se.velocity.y, se.velocity.z, se.cameraOffset.R.w, se.cameraOffset.R.x,
+                          se.cameraOffset.R.y, se.cameraOffset.R.z, se.cameraOffset.x.x, se.cameraOffset.x.y, se.cameraOffset.x.z};
+    for (int i = 0; i < 23; ++i)
+        s[i] = v[i];
+}
+VIOSensorState sensorFromFlat(const double (&s)[23]) {
+    VIOSensorState se;
+    for (int i = 0; i < 6; ++i)
+        se.inputBias[i] = s[i];
+    se.pose = Pose{Qt{s[6], s[7], s[8], s[9]}, V3{s[10], s[11], s[12]}};
+    se.velocity = V3{s[13], s[14], s[15]};
+    se.cameraOffset = Pose{Qt{s[16], s[17], s[18], s[19]}, V3{s[20], s[21], s[22]}};
+    return se;
+}
 } // namespace
 
 VIOWriter::VIOWriter(const std::string& providedOutputDir) : outputDir(providedOutputDir) { // :22-31
@@ -80,20 +97,21 @@ VIOWriter::VIOWriter(const std::string& providedOutputDir) : outputDir(providedO
     makeDirs(outputDir);
 }
 
-void VIOWriter::writeStates(const double& stamp, const VIOState& xi) { // :33-80
+void VIOWriter::writeSensorRows(const double& stamp, const double (&sensor)[23]) { // :33-60, the rows of IMUState.csv, camera.csv and bias.csv
+    const VIOSensorState se = sensorFromFlat(sensor);
     if (!IMUStateFile.is_open()) {
         IMUStateFile.open(outputDir + "IMUState.csv");
         IMUStateFile << "time, px, py, pz, qw, qx, qy, qz, vx, vy, vz\n";
     }
     stampPrefix(IMUStateFile, stamp);
-    IMUStateFile << (Line() << xi.sensor.pose << xi.sensor.velocity) << '\n';
+    IMUStateFile << (Line() << se.pose << se.velocity) << '\n';
 
     if (!cameraFile.is_open()) {
         cameraFile.open(outputDir + "camera.csv");
         cameraFile << "time, px, py, pz, qw, qx, qy, qz\n";
     }
     stampPrefix(cameraFile, stamp);
-    cameraFile << (Line() << xi.sensor.cameraOffset) << '\n';
+    cameraFile << (Line() << se.cameraOffset) << '\n';
 
     if (!biasFile.is_open()) {
         biasFile.open(outputDir + "bias.csv");
@@ -102,23 +120,37 @@ void VIOWriter::writeStates(const double& stamp, const VIOState& xi) { // :33-80
     stampPrefix(biasFile, stamp);
     {
         Line line;
-        for (double b : xi.sensor.inputBias)
+        for (double b : se.inputBias)
             line << b;
         biasFile << line << '\n';
     }
+}
 
+void VIOWriter::writePointsRow(const double& stamp, int N, const int* ids, const double* worldPoints) { // :62-79, the row of points.csv
     if (!pointsFile.is_open()) {
         pointsFile.open(outputDir + "points.csv");
         pointsFile << "time, p1id, p1x, p1y, p1z, ...\n";
     }
     stampPrefix(pointsFile, stamp);
-    {
-        Line line;
-        const Pose PC = pose_mul(xi.sensor.pose, xi.sensor.cameraOffset); // world-frame points
-        for (const Landmark& q : xi.cameraLandmarks)
-            line << q.id << pose_act(PC, q.p);
-        pointsFile << line << '\n';
+    Line line;
+    for (int i = 0; i < N; ++i)
+        line << ids[i] << worldPoints[3 * i] << worldPoints[3 * i + 1] << worldPoints[3 * i + 2];
+    pointsFile << line << '\n';
+}
+
+void VIOWriter::writeStates(const double& stamp, const VIOState& xi) { // :33-80
+    double sensor[23];
+    sensorToFlat(xi.sensor, sensor);
+    writeSensorRows(stamp, sensor);
+    const Pose PC = pose_mul(xi.sensor.pose, xi.sensor.cameraOffset); // world-frame points
+    std::vector<int> ids;
+    std::vector<double> world;
+    for (const Landmark& q : xi.cameraLandmarks) {
+        const V3 w = pose_act(PC, q.p);
+        ids.push_back(q.id);
+        world.insert(world.end(), {w.x, w.y, w.z});
     }
+    writePointsRow(stamp, (int)ids.size(), ids.data(), world.data());
 }
 
 void VIOWriter::writeFeatures(const VisionMeasurement& y) { // :82-94

@@ -32,6 +32,10 @@ class VIOWriter {
     void writeLandmarkErrorRow(const double& stamp, const std::vector<double>& errors); // one per TRUE landmark, NaN where the filter does not hold it
     void writeNEESRow(const double& stamp, double fullNEES, int dof, double poseNEES, double attitudeNEES);
     void writeConsistencyRow(ConsistencyFile which, const double& stamp, const double (&eps)[6], const double (&sigma2)[6]);
+    // The rows of the state files from numbers already in hand: writeStates formats its rows through these, and so do the filter batch's recorded replay
+    // (eqvio_batch_run_prepared_recorded) and `eqvio_opt --batch B --record DIR`, whose numbers come from the device's estimate records (eqf_batch_estimates).
+    void writeSensorRows(const double& stamp, const double (&sensor)[23]); // IMUState.csv, camera.csv, bias.csv; the sensor state in eqvio_types.h's flat layout
+    void writePointsRow(const double& stamp, int N, const int* ids, const double* worldPoints); // points.csv: pose * cameraOffset * p, 3 per landmark
 };
 
 } // namespace eqvio_amd

@@ -5,6 +5,8 @@
 // slot by its innovation statistics (include/eqf_batch.h): a tuning sweep on a dataset without landmark truth. With --warmup F the first F frames run once, in
 // slot 0 under the command line's settings, and slot 0 is then copied into the other slots on the device (eqf_batch_copy_slots): every tuning starts from the
 // same converged filter, and the scores count the frames after the warm-up only.
+// --batch B --record DIR writes every slot's trajectory (the four state files of --output) to DIR/run_<k>/, and --batch B --groundtruth FILE scores every slot's
+// trajectory against ground truth: both from ONE estimates call per vision measurement over the live slots (eqf_batch_estimates).
 #include "DatasetReplay.hpp"
 #include "VIOFilterBatch.hpp"
 #include "VIOWriter.hpp"
@@ -27,12 +29,16 @@ static void usage() {
               "                 [--cameraFile sensor.yaml | camchain.yaml]   (intrinsics, distortion and camera offset from the dataset's own file, main_opt.cpp:114-147)\n"
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F]]]\n"
+              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F]] [--record DIR]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
               "              (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood. Needs --fastRiccati 1 and at most 64\n"
-              "              features per frame; --output, --dumpStates and --sigmaFP32 are refused.\n"
+              "              features per frame; --output, --dumpStates and --sigmaFP32 are refused. With --groundtruth FILE one more line per slot: the position\n"
+              "              RMSE of the slot's trajectory against the ground-truth poses nearest in time, after aligning the first poses.\n"
+              "  --record DIR   with --batch B: slot k's IMUState.csv, camera.csv, bias.csv and points.csv (the formats of --output) go to DIR/run_<k>/, one row per\n"
+              "              vision measurement per live slot, from one estimates call over the live slots per measurement. With --warmup F slots 1 .. B-1 start\n"
+              "              their files at the branch.\n"
               "  --sweep NAME=v0,...,v(B-1)   with --batch B: slot k runs with the filter setting NAME (a field of eqvio_settings) at value vk. Needs exactly B values.\n"
               "  --warmup F   with --batch B --sweep: the first F vision frames run in slot 0 alone, with the command line's settings; slot 0 is then copied into\n"
               "              slots 1 .. B-1 on the device, the sweep's values go to all B slots, and the scores count the frames after the warm-up only.\n"
@@ -41,7 +47,8 @@ static void usage() {
 }
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
-static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime) {
+static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime,
+                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -50,6 +57,13 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         return 1;
     }
     VIOFilterBatch filters(core); // every slot as VIOFilter(fs): it initialises itself from its first IMU sample
+    // --record / --groundtruth: the live slots' estimates after every vision measurement, one call for all of them
+    const bool wantEstimates = !recordDir.empty() || groundtruth;
+    std::vector<std::unique_ptr<VIOWriter>> writers(B);
+    for (int k = 0; k < B && !recordDir.empty(); ++k)
+        writers[k] = makeRunWriter(recordDir, k); // before any frame runs
+    std::vector<eqf_batch_estimate_record> records(B);
+    std::vector<std::vector<StampedPose>> trajectories(B);
     auto applySweep = [&] {
         for (int k = 0; k < B && swept; ++k) {
             eqvio_settings ek = es;
@@ -106,6 +120,18 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
             }
             ++visionDataCounter;
             scoredFrames += branched;
+            if (wantEstimates) {
+                check_rc(eqf_batch_estimates(filters.core(), live, slots.data(), records.data(), status.data()), "eqf_batch_estimates");
+                for (int k = 0; k < live; ++k) {
+                    check_rc(status[k], "eqf_batch_estimates");
+                    const eqf_batch_estimate_record& r = records[k];
+                    const double stamp = filters.slot(k).currentTime; // -1 before the slot has initialised, as main() writes it
+                    if (writers[k])
+                        writeEstimateRecord(*writers[k], stamp, r);
+                    if (groundtruth)
+                        trajectories[k].push_back(StampedPose{stamp, Pose{Qt{r.sensor[6], r.sensor[7], r.sensor[8], r.sensor[9]}, V3{r.sensor[10], r.sensor[11], r.sensor[12]}}});
+                }
+            }
         } else {
             const IMUVelocity imuData = dataServer.getIMU();
             if (startTime > 0 && imuData.stamp < startTime)
@@ -131,13 +157,18 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         std::printf("slot %d%s: frames updated %ld  failed %d  mean NIS/dof %.9g  log-likelihood %.9g\n", k, what.c_str(), t.updates, failed[k], t.meanNisPerDof(),
                     t.logLikelihood());
     }
+    for (int k = 0; k < B && groundtruth; ++k) {
+        const TrajectoryScore t = trajectoryPositionRMSE(trajectories[k], *groundtruth);
+        const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
+        std::printf("slot %d%s: position RMSE %.9g over %d frames\n", k, what.c_str(), t.rmse, t.frames);
+    }
     std::printf("batch of %d slots: slots x vision updates/s %.1f\n", B, (double)B * visionDataCounter / elapsed);
     return 0;
 }
 
 int main(int argc, char** argv) {
     VIOFilter::Settings fs;
-    std::string imuName, featName, gtName, outputDir, cameraFileName, statesName;
+    std::string imuName, featName, gtName, outputDir, cameraFileName, statesName, recordDir;
     DatasetFormat format = DatasetFormat::ASL;
     auto cam = std::make_shared<Camera>();
     cam->c.fx = 458.654; // intrinsics.yaml:7 (EuRoC cam0)
@@ -202,6 +233,7 @@ int main(int argc, char** argv) {
             else if (a == "--dumpMeasurements") dump = true;
             else if (a == "--printCamera") printCamera = true;
             else if (a == "--batch") batch = std::atoi(val());
+            else if (a == "--record") recordDir = val();
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
                 haveSweep = true;
@@ -216,6 +248,10 @@ int main(int argc, char** argv) {
         }
         if (haveSweep && batch == 0) {
             std::fprintf(stderr, "eqvio_opt: --sweep needs --batch B (one value per slot)\n");
+            return 2;
+        }
+        if (!recordDir.empty() && batch == 0) { // before any file or device is opened
+            std::fprintf(stderr, "eqvio_opt: --record needs --batch\n");
             return 2;
         }
         int warmup = 0;
@@ -289,8 +325,12 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
-        if (batch != 0)
-            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime);
+        if (batch != 0) {
+            std::vector<StampedPose> gt;
+            if (!gtName.empty())
+                gt = TrackReplayServer::groundtruth(gtName, format);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt);
+        }
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150
         if (sigmaFP32) // BASELINE config 5: Sigma stored as float in HBM (include/eqf_hip.h)

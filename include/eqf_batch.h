@@ -162,6 +162,30 @@ typedef struct eqf_batch_consistency_record {
  * change. */
 int eqf_batch_consistency(eqf_batch* b, int count, const eqf_batch_truth* truths, eqf_batch_consistency_record* out, int* status);
 
+/* One slot's state estimate: what stateEstimate() and viewEqFState() hand back of a filter for its output files, in one fixed-size record. Entries of the
+ * fixed-size arrays beyond N read 0. The sensor layout is eqvio_types.h's (bias, pose quaternion and position, velocity, camera offset). */
+typedef struct eqf_batch_estimate_record {
+    int N, reserved;                                /* landmarks of the slot; 0 */
+    double sensor[23];                              /* stateGroupAction(X, xi0), sensor part: eqf_batch_state_estimate's 23 doubles */
+    double sigma_sensor[21 * 21];                   /* Sigma[0:21, 0:21], column-major */
+    int ids[EQF_BATCH_MAX_LANDMARKS];               /* state order */
+    double p[3 * EQF_BATCH_MAX_LANDMARKS];          /* camera-frame points, Q^-1 q0 (eqf_batch_state_estimate's p) */
+    double p_world[3 * EQF_BATCH_MAX_LANDMARKS];    /* pose * cameraOffset * p: the points of points.csv */
+} eqf_batch_estimate_record;
+
+/* The state estimates of the `count` listed slots (distinct): one packet to the device, one launch (k_batch_estimate, one workgroup per accepted entry), one
+ * copy back, one synchronisation, whatever count is; nothing but the records crosses to the host. The host supplies what it holds of a slot (its current
+ * buffers, N, the ids, the sensor estimate - by the function eqf_batch_state_estimate uses, so N, ids and sensor are that call's bit for bit - and the product
+ * pose * cameraOffset); the slot's workgroup reads its landmark planes and Sigma and writes p, p_world and sigma_sensor. sigma_sensor is the raw block of
+ * Sigma, as eqf_batch_get_sigma returns it, bit for bit; p and p_world are formed on the device and agree with eqf_batch_state_estimate's p to rounding.
+ * The call is read-only: no slot's state, Sigma, landmark planes, settings, innovation totals, last result or LU-fallback count change. A slot's record has
+ * the same bytes whichever call it is part of: alone, among others in any order, in a batch of any size (nothing is summed). status[e]:
+ *   0                  done;
+ *   EQF_E_BAD_ARG      bad slot index or repeated slot: out[e] is left untouched, byte for byte; the other entries are still done.
+ * Returns 0 when the launch ran (whatever the per-entry codes) or count == 0, EQF_E_BAD_ARG for a null batch, slots, out or status or count < 0 (checked
+ * before any device is looked at), or a HIP error. */
+int eqf_batch_estimates(eqf_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, int* status);
+
 /* One slot's augmentLandmarkStates for eqf_batch_augment: the ids the slot keeps and adds (n_new), and the provided state's landmarks (n_prov ids and
  * camera-frame points) the new ones are taken from. */
 typedef struct eqf_batch_augment_entry {

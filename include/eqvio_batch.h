@@ -49,6 +49,13 @@ int eqvio_batch_process_vision(eqvio_batch* b, int count, const int* slots, cons
  * frame j of every slot that has one - its IMU samples, then its measurement - goes in one device step; a slot whose sequence has ended sits out. Returns the
  * number of steps run, or -1 (a slot's frame was refused or failed: message via eqvio_batch_last_error). */
 int eqvio_batch_run_prepared(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count);
+/* eqvio_batch_run_prepared with the estimates recorded: the same loop with the same steps, leaving every slot in the same state bit for bit, and after every
+ * step ONE eqf_batch_estimates call for the slots that had a frame. For every slot k with a sequence the directory output_dir/run_<k>/ gets IMUState.csv,
+ * camera.csv, bias.csv and points.csv with the headers, column order and number formatting of a single filter's --output (VIOWriter::writeStates): one row per
+ * frame the slot ran, stamp = the slot's getTime(); points.csv takes the records' p_world. Each call starts its files anew (files of an earlier call are
+ * removed), and a file appears with its first row. Only the records cross to the host. An output_dir that cannot be created gives -1
+ * (eqvio_batch_last_error) before any frame runs; a null one EQF_E_BAD_ARG. */
+int eqvio_batch_run_prepared_recorded(eqvio_batch* b, const eqvio_frames* const* per_slot, int first, int count, const char* output_dir);
 
 /* viewEqFState().computeNEES(trueState) of `count` distinct slots in ONE launch (eqf_batch_nees). Entry e: slot slots[e], the 23 sensor doubles at
  * true_sensor_all + 23 e, true_counts[e] landmarks taken in order from true_ids_all / true_p_all (3 doubles each). nees[e], status[e] as eqf_batch_nees.
@@ -79,6 +86,11 @@ int eqvio_batch_run_sim(eqvio_batch* b, eqvio_sim* const* sims, int max_frames, 
  * Only the records cross to the host. An output_dir that cannot be created gives -1 (eqvio_batch_last_error) before any frame runs; a null one EQF_E_BAD_ARG. */
 int eqvio_batch_run_sim_recorded(eqvio_batch* b, eqvio_sim* const* sims, int max_frames, double* nees, int* frames_run, const char* output_dir);
 
+/* The estimate records of `count` distinct slots in ONE launch (eqf_batch_estimates, include/eqf_batch.h: same records, same refusals, same codes; a refused
+ * entry's record is left untouched) and, when times is not null, each listed slot's getTime(). A slot that has not initialised gives the state it was
+ * created with (identity pose, the settings' camera offset, no landmark) and -1, as a single filter does. Returns 0, EQF_E_BAD_ARG (a null batch, slots, out
+ * or status, count < 0) or a HIP error. */
+int eqvio_batch_estimates(eqvio_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, double* times, int* status);
 /* per slot: stateEstimate, viewEqFState (xi0, X, Sigma), getTime, isInitialised, and the forcing of a whole EqF state (teacher forcing) */
 int eqvio_batch_state_estimate(eqvio_batch* b, int slot, double* sensor, int* ids, double* p, int cap); /* returns N or < 0 */
 int eqvio_batch_get_eqf(eqvio_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap);
