@@ -1,5 +1,6 @@
 // Filter batch (include/eqf_batch.h): B independent filters of at most 64 landmarks, one workgroup per slot, ONE launch per frame of all of them.
-// Included by eqf_hip.hip after eqf_kernels.hpp; every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
+// The device side: the packet structs and the six kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
+// eqf_hip.hip includes both. Every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
 //
 // Per slot s, in HBM (fp64): two Sigma buffers (n x n column-major, leading dimension ld, n <= 21 + 3 * 64), two landmark buffers (35 SoA planes of stride
 // BATCH_L: q0 and its chart constants - the layout ld_cc expects -, Qq, Qa) and one scratch area (F Sigma, then [T ; yTilde^T] -> [W^T ; z^T] and L dense,
@@ -74,12 +75,18 @@ struct BatchOut {
     int dof;                     // rows m of the matched measurement (0: empty)
     double nis, logdet;          // yTilde^T S^-1 yTilde and log det S of the update (NaN when the update failed)
 };
+// The slots' buffers, the same for every kernel: slot s has two Sigma buffers and two landmark buffers (which = 0 / 1; the host names the current one) and one
+// scratch area.
+struct BatchBufs {
+    int ld; // leading dimension of a Sigma buffer
+    double *sig, *lm, *scr;
+    size_t sig_stride, lm_stride, scr_stride; // doubles per buffer
+    __host__ __device__ double* sig_of(int slot, int which) const { return sig + (2 * (size_t)slot + which) * sig_stride; }
+    __host__ __device__ double* lm_of(int slot, int which) const { return lm + (2 * (size_t)slot + which) * lm_stride; }
+    __host__ __device__ double* scr_of(int slot) const { return scr + (size_t)slot * scr_stride; }
+};
 struct BatchArgs {
-    int ld;
-    double* sig;
-    double* lm;
-    double* scr;
-    size_t sig_stride, lm_stride, scr_stride;
+    BatchBufs buf;
     const BatchIn* in;
     const ObsStep* steps;
     BatchOut* out;
@@ -101,6 +108,56 @@ __device__ __forceinline__ double batch_wave_sum(double v) {
         v += __shfl_xor(v, o, 64);
     return v;
 }
+// the lanes of one wave see each other's LDS stores behind this
+__device__ __forceinline__ void batch_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// tile t of a lower triangle of tiles counted row by row: its row bi and column bj <= bi
+__device__ __forceinline__ void batch_tri_tile(int t, int& bi, int& bj) {
+    bi = 0;
+    while ((bi + 1) * (bi + 2) / 2 <= t)
+        ++bi;
+    bj = t - bi * (bi + 1) / 2;
+}
+// addNewLandmarks' entry i of a landmark buffer: origin point p with its chart constants, Q = identity, a = 1
+__device__ __forceinline__ void batch_new_landmark(double* planes, int i, double px, double py, double pz) {
+    const int L = BATCH_L;
+    planes[i] = px;
+    planes[L + i] = py;
+    planes[2 * L + i] = pz;
+    store_chart_constants(planes + (size_t)CC_OFF * L, L, i, px, py, pz, nullptr);
+    planes[BATCH_QQ * L + i] = 1.0;
+    planes[(BATCH_QQ + 1) * L + i] = 0.0;
+    planes[(BATCH_QQ + 2) * L + i] = 0.0;
+    planes[(BATCH_QQ + 3) * L + i] = 0.0;
+    planes[BATCH_QA * L + i] = 1.0;
+}
+// dst (n x n) = src gathered through gidx (LDS); a row or column with gidx < 0 is a new landmark's: zero cross terms, init_var on the diagonal
+// (init_var by reference: k_batch_augment's stays in its packet entry until an element needs it, as before the two loops became this one)
+__device__ __forceinline__ void batch_gather_sigma(double* dst, const double* src, const int* gidx, int n, int ld, const double& init_var) {
+    for (int t = threadIdx.x; t < n * n; t += BATCH_T) {
+        const int r = t % n, c = t / n;
+        const int gr = gidx[r], gc = gidx[c];
+        dst[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? src[gr + (size_t)gc * ld] : (r == c ? init_var : 0.0);
+    }
+}
+// what a frame reports however it ends (one thread); did, outliers, depth and gamma are written where they are decided
+__device__ __forceinline__ void batch_finish(BatchOut* out, int status, int N, int cur, unsigned long long invalid, int dof, double nis, double logdet) {
+    out->status = status;
+    out->N = N;
+    out->cur = cur;
+    out->invalid = invalid;
+    out->dof = dof;
+    out->nis = nis;
+    out->logdet = logdet;
+}
+// landmark i's camera-frame point estimate p = Q^-1 q0 from a landmark buffer (eqf_batch_state_estimate's expression)
+__device__ __forceinline__ V3 batch_point_estimate(const double* lm, int i) {
+    const int L = BATCH_L;
+    return (1.0 / lm[BATCH_QA * L + i]) * q_rot(q_inv(ldq(lm + BATCH_QQ * L, L, i)), ld3(lm, L, i));
+}
 
 __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) {
     __shared__ double sm[BATCH_SM];
@@ -112,17 +169,17 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     const BatchIn& in = ba.in[blockIdx.x];
     BatchOut* out = ba.out + blockIdx.x;
     const int tid = threadIdx.x;
-    const int L = BATCH_L, ld = ba.ld;
+    const int L = BATCH_L, ld = ba.buf.ld;
     // the slot's settings: read once, before the first store of the launch
     const int chart = in.ss.chart, star = in.ss.star, discrete = in.ss.discrete, median = in.ss.median;
     const double thrAbs = in.ss.thrAbs, thrProb = in.ss.thrProb, meas_var = in.ss.meas_var, init_var = in.ss.init_var, init_depth = in.ss.init_depth;
     const bool ind = chart == EQVIO_COORD_INVDEPTH;
     const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
-    double* S0 = ba.sig + (2 * (size_t)slot + cur) * ba.sig_stride;
-    double* S1 = ba.sig + (2 * (size_t)slot + nxt) * ba.sig_stride;
-    double* L0 = ba.lm + (2 * (size_t)slot + cur) * ba.lm_stride;
-    double* L1 = ba.lm + (2 * (size_t)slot + nxt) * ba.lm_stride;
-    double* scr = ba.scr + (size_t)slot * ba.scr_stride;
+    double* S0 = ba.buf.sig_of(slot, cur);
+    double* S1 = ba.buf.sig_of(slot, nxt);
+    double* L0 = ba.buf.lm_of(slot, cur);
+    double* L1 = ba.buf.lm_of(slot, nxt);
+    double* scr = ba.buf.scr_of(slot);
     const int Ns = in.Ns, n1 = 21 + 3 * Ns, M = in.M;
     const double dt = in.dt;
 
@@ -344,11 +401,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     for (int r = tid; r < n2; r += BATCH_T)
         s_gidx[r] = r < 21 ? r : ((r - 21) / 3 < nk ? 21 + 3 * s_keep[(r - 21) / 3] + (r - 21) % 3 : -1);
     __syncthreads();
-    for (int t = tid; t < n2 * n2; t += BATCH_T) {
-        const int r = t % n2, c = t / n2;
-        const int gr = s_gidx[r], gc = s_gidx[c];
-        S0[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S1[gr + (size_t)gc * ld] : (r == c ? init_var : 0.0);
-    }
+    batch_gather_sigma(S0, S1, s_gidx, n2, ld, init_var);
     if (tid < N2) {
         const int i = tid;
         if (i < nk) {
@@ -357,29 +410,14 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         } else {
             const int r = i - nk;
             const double d = s_depth;
-            const double px = in.bear[3 * r] * d, py = in.bear[3 * r + 1] * d, pz = in.bear[3 * r + 2] * d;
-            L0[i] = px;
-            L0[L + i] = py;
-            L0[2 * L + i] = pz;
-            store_chart_constants(L0 + (size_t)CC_OFF * L, L, i, px, py, pz, nullptr);
-            L0[BATCH_QQ * L + i] = 1.0;
-            L0[(BATCH_QQ + 1) * L + i] = 0.0;
-            L0[(BATCH_QQ + 2) * L + i] = 0.0;
-            L0[(BATCH_QQ + 3) * L + i] = 0.0;
-            L0[BATCH_QA * L + i] = 1.0;
+            batch_new_landmark(L0, i, in.bear[3 * r] * d, in.bear[3 * r + 1] * d, in.bear[3 * r + 2] * d);
         }
     }
     __syncthreads();
     if (M2 == 0) { // performVisionUpdate returns at once on an empty measurement, and processVisionData before removeInvalidLandmarks
         if (tid == 0) {
-            out->status = 0;
-            out->N = N2;
-            out->cur = cur;
             out->did |= BATCH_DID_EMPTY;
-            out->invalid = 0;
-            out->dof = 0;
-            out->nis = 0.0;
-            out->logdet = 0.0;
+            batch_finish(out, 0, N2, cur, 0, 0, 0.0, 0.0);
         }
         return;
     }
@@ -458,14 +496,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         __syncthreads();
     }
     if (s_misc[2]) {
-        if (tid == 0) {
-            out->status = EQF_E_NOT_SPD;
-            out->N = N2;
-            out->cur = cur;
-            out->invalid = 0;
-            out->dof = m;
-            out->nis = out->logdet = __builtin_nan("");
-        }
+        if (tid == 0)
+            batch_finish(out, EQF_E_NOT_SPD, N2, cur, 0, m, __builtin_nan(""), __builtin_nan(""));
         return;
     }
     // W^T = T L^-T and z^T = yTilde^T L^-T, blocked by 16 columns on the matrix cores: row tiles of 16 rows of [T ; yTilde^T] (one wave each); per column block
@@ -499,9 +531,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
                     double* e = Tr + lr + (size_t)(kb * 16 + lk + 4 * q) * ld;
                     *e -= acc[q];
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                batch_wave_sync();
                 if (lane < 16) { // the diagonal block: row lr of the tile against L[kb block][kb block]
                     double x[16];
                     for (int c = 0; c < 16; ++c) {
@@ -513,9 +543,7 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
                         Tr[lane + (size_t)(kb * 16 + c) * ld] = x[c];
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                batch_wave_sync();
             }
         }
     }
@@ -549,14 +577,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
     }
     __syncthreads();
     if (s_misc[2]) {
-        if (tid == 0) {
-            out->status = EQF_E_NONFINITE;
-            out->N = N2;
-            out->cur = cur;
-            out->invalid = 0;
-            out->dof = m;
-            out->nis = out->logdet = __builtin_nan("");
-        }
+        if (tid == 0)
+            batch_finish(out, EQF_E_NONFINITE, N2, cur, 0, m, __builtin_nan(""), __builtin_nan(""));
         return;
     }
     // Sigma -= W^T W on the matrix cores: lower 16 x 16 tiles (one wave each), K = m16 (the padded columns of W are zero), mirrored into the upper half
@@ -564,10 +586,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
         const int wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
         const int nt = (n2 + 15) / 16;
         for (int t = wave; t < nt * (nt + 1) / 2; t += BATCH_T / 64) {
-            int bi = 0;
-            while ((bi + 1) * (bi + 2) / 2 <= t)
-                ++bi;
-            const int bj = t - bi * (bi + 1) / 2;
+            int bi, bj;
+            batch_tri_tile(t, bi, bj);
             d4 acc = {0, 0, 0, 0};
             for (int pb = 0; pb < m16 / 16; ++pb) {
                 const d4 a = mfma16_nt(T + bi * 16 + (size_t)pb * 16 * ld, ld, T + bj * 16 + (size_t)pb * 16 * ld, ld);
@@ -624,14 +644,8 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) 
                 L1[pl * L + tid] = L0[pl * L + s_keep[tid]];
     }
     if (tid == 0) {
-        out->status = 0;
-        out->N = N3;
-        out->cur = N3 < N2 ? nxt : cur;
-        out->invalid = s_mask;
         out->did |= BATCH_DID_UPDATE | (N3 < N2 ? BATCH_DID_INVALID : 0);
-        out->dof = m;
-        out->nis = inn[0];
-        out->logdet = inn[1];
+        batch_finish(out, 0, N3, N3 < N2 ? nxt : cur, s_mask, m, inn[0], inn[1]);
     }
 }
 
@@ -654,11 +668,7 @@ struct NeesOut {
     int lu;       // 1: a pivot was <= 0 and the partial-pivot elimination gave the value
 };
 struct NeesArgs {
-    int ld;
-    const double* sig;
-    const double* lm;
-    double* scr;
-    size_t sig_stride, lm_stride, scr_stride;
+    BatchBufs buf;
     const NeesIn* in;
     NeesOut* out;
 };
@@ -706,13 +716,6 @@ static_assert(CONS_Y21 + 21 <= CONS_SMALL && 441 <= CONS_W21, "the block forms' 
 #ifndef EQF_CONS_MEASURE_SKIP
 #define EQF_CONS_MEASURE_SKIP 0
 #endif
-
-// the lanes of one wave see each other's LDS stores behind this
-__device__ __forceinline__ void batch_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // x^T M^-1 x by the elimination rule of VIOWriter.cpp's quadInv (the reference's .inverse() route): Gaussian elimination with partial pivoting on [M | x], the
 // pivot the first row of largest magnitude, back substitution, then x^T y. One lane; w: K rows of [M | x] (row stride K + 1, destroyed), then K doubles that
@@ -815,11 +818,11 @@ template <bool REC> __device__ __forceinline__ void batch_nees_body(const NeesAr
     __shared__ int s_idx[BATCH_T];
     __shared__ int s_perm[NEES_NP];
     const NeesIn& in = na.in[blockIdx.x];
-    const int tid = threadIdx.x, L = BATCH_L, ld = na.ld;
+    const int tid = threadIdx.x, L = BATCH_L, ld = na.buf.ld;
     const int N = in.N, n = 21 + 3 * N, np = n + (n & 1);
-    const double* S = na.sig + (2 * (size_t)in.slot + in.cur) * na.sig_stride;
-    const double* lm = na.lm + (2 * (size_t)in.slot + in.cur) * na.lm_stride;
-    double* Z = na.scr + (size_t)in.slot * na.scr_stride;
+    const double* S = na.buf.sig_of(in.slot, in.cur);
+    const double* lm = na.buf.lm_of(in.slot, in.cur);
+    double* Z = na.buf.scr_of(in.slot);
 
     for (int r = tid; r < np; r += BATCH_T)
         if (r < 21 || r >= n)
@@ -831,10 +834,8 @@ template <bool REC> __device__ __forceinline__ void batch_nees_body(const NeesAr
         s_eps[21 + 3 * i] = e.x;
         s_eps[22 + 3 * i] = e.y;
         s_eps[23 + 3 * i] = e.z;
-        if constexpr (REC) { // |p_hat - p_true|, p_hat = Q^-1 q0 (eqf_batch_state_estimate's expression)
-            const V3 ph = (1.0 / lm[BATCH_QA * L + i]) * q_rot(q_inv(ldq(lm + BATCH_QQ * L, L, i)), ld3(lm, L, i));
-            rec->lm_err[i] = norm(ph - V3{in.p[3 * i], in.p[3 * i + 1], in.p[3 * i + 2]});
-        }
+        if constexpr (REC) // |p_hat - p_true|
+            rec->lm_err[i] = norm(batch_point_estimate(lm, i) - V3{in.p[3 * i], in.p[3 * i + 1], in.p[3 * i + 2]});
     }
     __syncthreads();
     if constexpr (REC) {
@@ -930,10 +931,7 @@ template <bool REC> __device__ __forceinline__ void batch_nees_body(const NeesAr
             for (int t = wave; t < ntiles; t += BATCH_T / 64) {
                 int bi, bj;
                 if (t < tri) {
-                    bi = 0;
-                    while ((bi + 1) * (bi + 2) / 2 <= t)
-                        ++bi;
-                    bj = t - bi * (bi + 1) / 2;
+                    batch_tri_tile(t, bi, bj);
                 } else {
                     bi = ntc;
                     bj = t - tri;
@@ -1052,29 +1050,22 @@ struct AugIn {
     double init_var;         // the slot's initialPointVariance
 };
 struct AugArgs {
-    int ld;
-    double* sig;
-    double* lm;
-    size_t sig_stride, lm_stride;
+    BatchBufs buf;
     const AugIn* in;
 };
 __global__ void __launch_bounds__(BATCH_T) k_batch_augment(const AugArgs aa) {
     __shared__ int s_gidx[BATCH_NMAX];
     const AugIn& in = aa.in[blockIdx.x];
-    const int tid = threadIdx.x, L = BATCH_L, ld = aa.ld;
+    const int tid = threadIdx.x, L = BATCH_L, ld = aa.buf.ld;
     const int nk = in.Nk, N2 = nk + in.nnew, n2 = 21 + 3 * N2, cur = in.cur, nxt = cur ^ 1;
-    const double* S0 = aa.sig + (2 * (size_t)in.slot + cur) * aa.sig_stride;
-    double* S1 = aa.sig + (2 * (size_t)in.slot + nxt) * aa.sig_stride;
-    const double* L0 = aa.lm + (2 * (size_t)in.slot + cur) * aa.lm_stride;
-    double* L1 = aa.lm + (2 * (size_t)in.slot + nxt) * aa.lm_stride;
+    const double* S0 = aa.buf.sig_of(in.slot, cur);
+    double* S1 = aa.buf.sig_of(in.slot, nxt);
+    const double* L0 = aa.buf.lm_of(in.slot, cur);
+    double* L1 = aa.buf.lm_of(in.slot, nxt);
     for (int r = tid; r < n2; r += BATCH_T)
         s_gidx[r] = r < 21 ? r : ((r - 21) / 3 < nk ? 21 + 3 * in.keep[(r - 21) / 3] + (r - 21) % 3 : -1);
     __syncthreads();
-    for (int t = tid; t < n2 * n2; t += BATCH_T) {
-        const int r = t % n2, c = t / n2;
-        const int gr = s_gidx[r], gc = s_gidx[c];
-        S1[r + (size_t)c * ld] = (gr >= 0 && gc >= 0) ? S0[gr + (size_t)gc * ld] : (r == c ? in.init_var : 0.0);
-    }
+    batch_gather_sigma(S1, S0, s_gidx, n2, ld, in.init_var);
     if (tid < N2) {
         const int i = tid;
         if (i < nk) {
@@ -1082,16 +1073,7 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_augment(const AugArgs aa) {
                 L1[pl * L + i] = L0[pl * L + in.keep[i]];
         } else {
             const int r = i - nk;
-            const double px = in.p[3 * r], py = in.p[3 * r + 1], pz = in.p[3 * r + 2];
-            L1[i] = px;
-            L1[L + i] = py;
-            L1[2 * L + i] = pz;
-            store_chart_constants(L1 + (size_t)CC_OFF * L, L, i, px, py, pz, nullptr);
-            L1[BATCH_QQ * L + i] = 1.0;
-            L1[(BATCH_QQ + 1) * L + i] = 0.0;
-            L1[(BATCH_QQ + 2) * L + i] = 0.0;
-            L1[(BATCH_QQ + 3) * L + i] = 0.0;
-            L1[BATCH_QA * L + i] = 1.0;
+            batch_new_landmark(L1, i, in.p[3 * r], in.p[3 * r + 1], in.p[3 * r + 2]);
         }
     }
 }
@@ -1111,10 +1093,7 @@ struct CopyIn {
     int N;         // the source's landmarks
 };
 struct CopyArgs {
-    int ld;
-    double* sig;
-    double* lm;
-    size_t sig_stride, lm_stride;
+    BatchBufs buf;
     const CopyIn* in;
 };
 constexpr int BATCH_COPY_COLS = 16;
@@ -1123,12 +1102,12 @@ constexpr int BATCH_COPY_CHUNKS = (BATCH_NMAX + BATCH_COPY_COLS - 1) / BATCH_COP
 static_assert(BATCH_L % 2 == 0 && (BATCH_PLANES * BATCH_L) % 2 == 0, "k_batch_copy moves pairs of doubles");
 __global__ void __launch_bounds__(BATCH_T) k_batch_copy(const CopyArgs ca) {
     const CopyIn in = ca.in[blockIdx.x];
-    const int tid = threadIdx.x, L = BATCH_L, ld = ca.ld;
+    const int tid = threadIdx.x, L = BATCH_L, ld = ca.buf.ld;
     const int N = in.N, n = 21 + 3 * N;
     const int c0 = blockIdx.y * BATCH_COPY_COLS, cols = min(BATCH_COPY_COLS, n - c0);
     if (cols > 0) {
-        const double* S = ca.sig + (2 * (size_t)in.src + in.scur) * ca.sig_stride + (size_t)c0 * ld;
-        double* D = ca.sig + (2 * (size_t)in.dst + in.dnxt) * ca.sig_stride + (size_t)c0 * ld;
+        const double* S = ca.buf.sig_of(in.src, in.scur) + (size_t)c0 * ld;
+        double* D = ca.buf.sig_of(in.dst, in.dnxt) + (size_t)c0 * ld;
         const int half = n >> 1; // >= 10
         for (int t = tid; t < cols * half; t += BATCH_T) {
             const size_t o = (size_t)(t / half) * ld + 2 * (t % half);
@@ -1138,8 +1117,8 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_copy(const CopyArgs ca) {
             D[(size_t)tid * ld + n - 1] = S[(size_t)tid * ld + n - 1];
     }
     if (blockIdx.y == gridDim.y - 1) {
-        const double* S = ca.lm + (2 * (size_t)in.src + in.scur) * ca.lm_stride;
-        double* D = ca.lm + (2 * (size_t)in.dst + in.dnxt) * ca.lm_stride;
+        const double* S = ca.buf.lm_of(in.src, in.scur);
+        double* D = ca.buf.lm_of(in.dst, in.dnxt);
         const int half = N >> 1; // 0 for N <= 1: the loop does not run
         for (int t = tid; t < BATCH_PLANES * half; t += BATCH_T) {
             const int o = (t / half) * L + 2 * (t % half);
@@ -1160,23 +1139,20 @@ struct EstIn {
     Pose pc; // pose * cameraOffset of the slot's sensor estimate
 };
 struct EstArgs {
-    int ld;
-    const double* sig;
-    const double* lm;
-    size_t sig_stride, lm_stride;
+    BatchBufs buf;
     const EstIn* in;
     eqf_batch_estimate_record* rec;
 };
 __global__ void __launch_bounds__(BATCH_T) k_batch_estimate(const EstArgs ea) {
     const EstIn& in = ea.in[blockIdx.x];
     eqf_batch_estimate_record* rec = ea.rec + blockIdx.x;
-    const int tid = threadIdx.x, L = BATCH_L, ld = ea.ld, N = in.N;
-    const double* S = ea.sig + (2 * (size_t)in.slot + in.cur) * ea.sig_stride;
-    const double* lm = ea.lm + (2 * (size_t)in.slot + in.cur) * ea.lm_stride;
+    const int tid = threadIdx.x, ld = ea.buf.ld, N = in.N;
+    const double* S = ea.buf.sig_of(in.slot, in.cur);
+    const double* lm = ea.buf.lm_of(in.slot, in.cur);
     for (int i = tid; i < BATCH_L; i += BATCH_T) {
         V3 ph{0.0, 0.0, 0.0}, pw{0.0, 0.0, 0.0};
         if (i < N) {
-            ph = (1.0 / lm[BATCH_QA * L + i]) * q_rot(q_inv(ldq(lm + BATCH_QQ * L, L, i)), ld3(lm, L, i));
+            ph = batch_point_estimate(lm, i);
             pw = pose_act(in.pc, ph);
         }
         rec->p[3 * i] = ph.x, rec->p[3 * i + 1] = ph.y, rec->p[3 * i + 2] = ph.z;

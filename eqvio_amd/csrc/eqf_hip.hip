@@ -1,4 +1,5 @@
 // eqf_hip.hip — context + C-ABI of the MI355X EqF core (see include/eqf_hip.h). gfx950 only.
+// The filter batch (include/eqf_batch.h) is compiled into this translation unit from eqf_batch.hpp (kernels) and eqf_batch_host.hpp (host side, included at the end).
 #include "eqf_hip.h"
 #include "eqf_kernels.hpp"
 #include "eqf_lookahead.hpp"
@@ -4021,954 +4022,5 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 
 } // extern "C"
 
-// ===================================================================================================
-// Filter batch (include/eqf_batch.h, kernel in eqf_batch.hpp): B slots of <= 64 landmarks, one launch per step.
-struct eqf_batch {
-    struct Slot {
-        SensorState xi0{};
-        GroupSensor X{};
-        std::vector<int> ids;
-        int cur = 0;
-        int flags = 0;
-        double depth = 0.0;
-        long nees_lu = 0; // eqf_batch_nees entries answered by the partial-pivot fallback
-        int inn_dof = 0;  // the last step's innovation statistics (eqf_batch_last_innovation)
-        double inn_nis = 0.0, inn_logdet = 0.0;
-        long tot_updates = 0, tot_dof = 0; // their sums over the steps that carried EQF_BATCH_UPDATED, in step order (eqf_batch_innovation_totals)
-        double tot_nis = 0.0, tot_logdet = 0.0;
-        eqvio_settings set{}; // the slot's own settings (eqf_batch_set_slot_settings; eqf_batch_create's until then)
-        BatchSlotSet ss{};    // what the kernels read of them: copied into the slot's packet entry of every step
-    };
-    int device = 0, slots = 0, cap = 0, ld = 0;
-    hipStream_t stream = nullptr;
-    double *d_sig = nullptr, *d_lm = nullptr, *d_scr = nullptr;
-    size_t sig_stride = 0, lm_stride = 0, scr_stride = 0;
-    BatchIn *h_in = nullptr, *d_in = nullptr;
-    BatchOut *h_out = nullptr, *d_out = nullptr;
-    ObsStep *h_steps = nullptr, *d_steps = nullptr;
-    int in_cap = 0, steps_cap = 0;
-    NeesIn *h_nin = nullptr, *d_nin = nullptr; // eqf_batch_nees packets
-    NeesOut *h_nout = nullptr, *d_nout = nullptr;
-    eqf_batch_consistency_record *h_rec = nullptr, *d_rec = nullptr; // eqf_batch_consistency records
-    AugIn *h_ain = nullptr, *d_ain = nullptr; // eqf_batch_augment packets
-    CopyIn *h_cin = nullptr, *d_cin = nullptr; // eqf_batch_copy_slots packets
-    EstIn *h_ein = nullptr, *d_ein = nullptr;  // eqf_batch_estimates packets
-    eqf_batch_estimate_record *h_erec = nullptr, *d_erec = nullptr; // eqf_batch_estimates records
-    int nin_cap = 0, nout_cap = 0, rec_cap = 0, aug_cap = 0, copy_cap = 0, ein_cap = 0, erec_cap = 0;
-    std::vector<Slot> s;
-};
-
-namespace {
-GroupSensor group_identity() {
-    GroupSensor g;
-    g.bgyr = v3(0, 0, 0);
-    g.bacc = v3(0, 0, 0);
-    g.A = pose_identity();
-    g.w = v3(0, 0, 0);
-    g.B = pose_identity();
-    return g;
-}
-int batch_grow_packets(eqf_batch* b, int entries, int steps) {
-    if (entries > b->in_cap) {
-        if (b->h_in)
-            HIPCHK(hipHostFree(b->h_in));
-        if (b->d_in)
-            HIPCHK(hipFree(b->d_in));
-        if (b->h_out)
-            HIPCHK(hipHostFree(b->h_out));
-        if (b->d_out)
-            HIPCHK(hipFree(b->d_out));
-        b->h_in = nullptr, b->d_in = nullptr, b->h_out = nullptr, b->d_out = nullptr, b->in_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&b->h_in, sizeof(BatchIn) * entries, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void**)&b->d_in, sizeof(BatchIn) * entries));
-        HIPCHK(hipHostMalloc((void**)&b->h_out, sizeof(BatchOut) * entries, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void**)&b->d_out, sizeof(BatchOut) * entries));
-        b->in_cap = entries;
-    }
-    if (steps > b->steps_cap) {
-        if (b->h_steps)
-            HIPCHK(hipHostFree(b->h_steps));
-        if (b->d_steps)
-            HIPCHK(hipFree(b->d_steps));
-        b->h_steps = nullptr, b->d_steps = nullptr, b->steps_cap = 0;
-        const int n = std::max(steps, 64);
-        HIPCHK(hipHostMalloc((void**)&b->h_steps, sizeof(ObsStep) * n, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void**)&b->d_steps, sizeof(ObsStep) * n));
-        b->steps_cap = n;
-    }
-    return 0;
-}
-double* batch_sig(eqf_batch* b, int slot, int which) { return b->d_sig + (2 * (size_t)slot + which) * b->sig_stride; }
-double* batch_lm(eqf_batch* b, int slot, int which) { return b->d_lm + (2 * (size_t)slot + which) * b->lm_stride; }
-// the slot's current landmark planes on the host: 8 doubles per landmark (q0[3], Q[4], a)
-int batch_fetch_landmarks(eqf_batch* b, int slot, std::vector<double>& out) {
-    const int N = (int)b->s[slot].ids.size();
-    std::vector<double> pl((size_t)BATCH_PLANES * BATCH_L);
-    HIPCHK(hipMemcpy(pl.data(), batch_lm(b, slot, b->s[slot].cur), sizeof(double) * pl.size(), hipMemcpyDeviceToHost));
-    out.assign(8 * (size_t)N, 0.0);
-    for (int i = 0; i < N; ++i) {
-        for (int c = 0; c < 3; ++c)
-            out[8 * i + c] = pl[c * BATCH_L + i];
-        for (int c = 0; c < 4; ++c)
-            out[8 * i + 3 + c] = pl[(BATCH_QQ + c) * BATCH_L + i];
-        out[8 * i + 7] = pl[BATCH_QA * BATCH_L + i];
-    }
-    return 0;
-}
-bool batch_slot_ok(const eqf_batch* b, int slot) { return b && slot >= 0 && slot < b->slots; }
-// the settings checks eqf_batch_create and eqf_batch_set_slot_settings share: 0, EQF_E_BAD_ARG or EQF_E_UNSUPPORTED
-int batch_settings_check(const eqvio_settings* st) {
-    if (st->coordinateChoice != EQVIO_COORD_EUCLIDEAN && st->coordinateChoice != EQVIO_COORD_INVDEPTH && st->coordinateChoice != EQVIO_COORD_NORMAL)
-        return EQF_E_BAD_ARG;
-    if (!st->fastRiccati || st->coordinateChoice == EQVIO_COORD_NORMAL)
-        return EQF_E_UNSUPPORTED; // accurate / discrete Riccati and the Normal chart: the per-context path (eqf_hip.h)
-    return 0;
-}
-// the values the kernels read of a slot's settings
-BatchSlotSet batch_slot_values(const eqvio_settings* st) {
-    BatchSlotSet ss;
-    ss.chart = st->coordinateChoice;
-    ss.star = st->useEquivariantOutput;
-    ss.discrete = st->useDiscreteInnovationLift;
-    ss.median = st->useMedianDepth;
-    ss.thrAbs = st->outlierThresholdAbs;
-    ss.thrProb = st->outlierThresholdProb;
-    ss.meas_var = st->measurementNoise * st->measurementNoise;
-    ss.init_var = st->initialPointVariance;
-    ss.init_depth = st->initialSceneDepth;
-    const double qv[4] = {st->velGyrNoise * st->velGyrNoise, st->velAccNoise * st->velAccNoise, st->velGyrBiasWalk * st->velGyrBiasWalk,
-                          st->velAccBiasWalk * st->velAccBiasWalk}; // constructInputGainMatrix (VIOFilterSettings.h:192-201)
-    for (int i = 0; i < 12; ++i)
-        ss.Qd[i] = qv[i / 3];
-    const double pv[8] = {st->biasOmegaProcessVariance, st->biasAccelProcessVariance, st->attitudeProcessVariance, st->positionProcessVariance,
-                          st->velocityProcessVariance,  st->cameraAttitudeProcessVariance, st->cameraPositionProcessVariance, st->pointProcessVariance};
-    std::memcpy(ss.Pd, pv, sizeof(pv));
-    return ss;
-}
-// every entry point that allocates, copies or launches runs on the batch's device, and leaves the caller's current device as it was
-struct BatchDevice {
-    int prev = -1;
-    explicit BatchDevice(const eqf_batch* b) {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        if (b && prev != b->device)
-            (void)hipSetDevice(b->device);
-    }
-    ~BatchDevice() {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-} // namespace
-
-int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, const eqvio_settings* st) {
-    if (!out || !st || slots < 1 || max_landmarks < 1 || max_landmarks > EQF_BATCH_MAX_LANDMARKS || device < 0)
-        return EQF_E_BAD_ARG;
-    if (int rc = batch_settings_check(st))
-        return rc;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device >= ndev)
-        return EQF_E_NO_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-        return EQF_E_NO_DEVICE;
-    HIPCHK(hipSetDevice(device));
-    eqf_batch* b = new eqf_batch();
-    b->device = device;
-    b->slots = slots;
-    b->cap = max_landmarks;
-    b->ld = pick_ld(BATCH_NMAX);
-    b->sig_stride = (size_t)b->ld * BATCH_NMAX;
-    b->lm_stride = (size_t)BATCH_PLANES * BATCH_L;
-    b->scr_stride = batch_scr_doubles(b->ld);
-    b->s.resize(slots);
-    for (auto& sl : b->s) {
-        sl.xi0 = unpack_sensor(std::vector<double>{0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0}.data());
-        sl.X = group_identity();
-        sl.set = *st;
-        sl.ss = batch_slot_values(st);
-    }
-    auto fail = [&](int rc) {
-        eqf_batch_destroy(b);
-        return rc;
-    };
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
-        return fail(EQF_E_CAPACITY);
-    if (hipMalloc((void**)&b->d_sig, sizeof(double) * b->sig_stride * 2 * slots) != hipSuccess ||
-        hipMalloc((void**)&b->d_lm, sizeof(double) * b->lm_stride * 2 * slots) != hipSuccess ||
-        hipMalloc((void**)&b->d_scr, sizeof(double) * b->scr_stride * slots) != hipSuccess)
-        return fail(EQF_E_CAPACITY);
-    if (hipMemsetAsync(b->d_sig, 0, sizeof(double) * b->sig_stride * 2 * slots, b->stream) != hipSuccess ||
-        hipMemsetAsync(b->d_lm, 0, sizeof(double) * b->lm_stride * 2 * slots, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
-        return fail(EQF_E_CAPACITY);
-    if (batch_grow_packets(b, std::min(slots, 64), 64 * 16))
-        return fail(EQF_E_CAPACITY);
-    *out = b;
-    return EQF_OK;
-}
-void eqf_batch_destroy(eqf_batch* b) {
-    if (!b)
-        return;
-    BatchDevice dev(b);
-    if (b->stream)
-        (void)hipStreamSynchronize(b->stream);
-    (void)hipFree(b->d_sig);
-    (void)hipFree(b->d_lm);
-    (void)hipFree(b->d_scr);
-    (void)hipFree(b->d_in);
-    (void)hipFree(b->d_out);
-    (void)hipFree(b->d_steps);
-    if (b->h_in)
-        (void)hipHostFree(b->h_in);
-    if (b->h_out)
-        (void)hipHostFree(b->h_out);
-    if (b->h_steps)
-        (void)hipHostFree(b->h_steps);
-    (void)hipFree(b->d_nin);
-    (void)hipFree(b->d_nout);
-    (void)hipFree(b->d_ain);
-    if (b->h_nin)
-        (void)hipHostFree(b->h_nin);
-    if (b->h_nout)
-        (void)hipHostFree(b->h_nout);
-    if (b->h_ain)
-        (void)hipHostFree(b->h_ain);
-    (void)hipFree(b->d_cin);
-    if (b->h_cin)
-        (void)hipHostFree(b->h_cin);
-    (void)hipFree(b->d_rec);
-    if (b->h_rec)
-        (void)hipHostFree(b->h_rec);
-    (void)hipFree(b->d_ein);
-    if (b->h_ein)
-        (void)hipHostFree(b->h_ein);
-    (void)hipFree(b->d_erec);
-    if (b->h_erec)
-        (void)hipHostFree(b->h_erec);
-    if (b->stream)
-        (void)hipStreamDestroy(b->stream);
-    delete b;
-}
-int eqf_batch_slots(const eqf_batch* b) { return b ? b->slots : EQF_E_BAD_ARG; }
-int eqf_batch_max_landmarks(const eqf_batch* b) { return b ? b->cap : EQF_E_BAD_ARG; }
-int eqf_batch_num_landmarks(const eqf_batch* b, int slot) { return batch_slot_ok(b, slot) ? (int)b->s[slot].ids.size() : EQF_E_BAD_ARG; }
-void* eqf_batch_stream(eqf_batch* b) { return b ? (void*)b->stream : nullptr; }
-int eqf_batch_synchronize(eqf_batch* b) {
-    if (!b)
-        return EQF_E_BAD_ARG;
-    BatchDevice dev(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return 0;
-}
-
-// No device work: the values travel in the slot's packet entry of its next step / NEES / augment call.
-int eqf_batch_set_slot_settings(eqf_batch* b, int slot, const eqvio_settings* st) {
-    if (!b || !st)
-        return EQF_E_BAD_ARG;
-    if (int rc = batch_settings_check(st))
-        return rc;
-    if (!batch_slot_ok(b, slot))
-        return EQF_E_BAD_ARG;
-    eqf_batch::Slot& sl = b->s[slot];
-    if (st->coordinateChoice != sl.set.coordinateChoice && !sl.ids.empty())
-        return EQF_E_BAD_ARG; // the slot's Sigma is in the old chart's coordinates
-    sl.set = *st;
-    sl.ss = batch_slot_values(st);
-    return 0;
-}
-int eqf_batch_check_settings(const eqvio_settings* st) { return st ? batch_settings_check(st) : EQF_E_BAD_ARG; }
-int eqf_batch_get_slot_settings(const eqf_batch* b, int slot, eqvio_settings* out) {
-    if (!batch_slot_ok(b, slot) || !out)
-        return EQF_E_BAD_ARG;
-    *out = b->s[slot].set;
-    return 0;
-}
-
-int eqf_batch_set_state(eqf_batch* b, int slot, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N) {
-    if (!batch_slot_ok(b, slot) || !xi0_sensor || !X_sensor || N < 0 || N > b->cap || (N > 0 && (!ids || !q0 || !Q)))
-        return EQF_E_BAD_ARG;
-    eqf_batch::Slot& sl = b->s[slot];
-    BatchDevice dev(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (N > 0) {
-        double *d_p = nullptr, *d_Q = nullptr;
-        HIPCHK(hipMalloc((void**)&d_p, sizeof(double) * 8 * N));
-        d_Q = d_p + 3 * N;
-        HIPCHK(hipMemcpy(d_p, q0, sizeof(double) * 3 * N, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_Q, Q, sizeof(double) * 5 * N, hipMemcpyHostToDevice));
-        double* lm = batch_lm(b, slot, sl.cur);
-        hipLaunchKernelGGL(k_scatter_landmarks, dim3(1), dim3(64), 0, b->stream, N, 0, BATCH_L, d_p, d_Q, lm, lm + (size_t)BATCH_QQ * BATCH_L,
-                           lm + (size_t)BATCH_QA * BATCH_L);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(b->stream));
-        HIPCHK(hipFree(d_p));
-    }
-    sl.xi0 = unpack_sensor(xi0_sensor);
-    sl.X = unpack_group(X_sensor);
-    sl.ids.assign(ids, ids + N);
-    return 0;
-}
-int eqf_batch_get_state(eqf_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap) {
-    if (!batch_slot_ok(b, slot))
-        return EQF_E_BAD_ARG;
-    eqf_batch::Slot& sl = b->s[slot];
-    const int N = (int)sl.ids.size();
-    if (N > cap)
-        return EQF_E_CAPACITY;
-    BatchDevice dev(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (xi0_sensor)
-        pack_sensor(sl.xi0, xi0_sensor);
-    if (X_sensor)
-        pack_group(sl.X, X_sensor);
-    std::vector<double> lm;
-    if (int rc = batch_fetch_landmarks(b, slot, lm))
-        return rc;
-    for (int i = 0; i < N; ++i) {
-        if (ids)
-            ids[i] = sl.ids[i];
-        if (q0)
-            for (int c = 0; c < 3; ++c)
-                q0[3 * i + c] = lm[8 * i + c];
-        if (Q)
-            for (int c = 0; c < 5; ++c)
-                Q[5 * i + c] = lm[8 * i + 3 + c];
-    }
-    return N;
-}
-int eqf_batch_set_sigma(eqf_batch* b, int slot, const double* sig, int n) {
-    if (!batch_slot_ok(b, slot) || !sig || n != 21 + 3 * (int)b->s[slot].ids.size())
-        return EQF_E_BAD_ARG;
-    BatchDevice dev(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(hipMemcpy2D(batch_sig(b, slot, b->s[slot].cur), sizeof(double) * b->ld, sig, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
-    return 0;
-}
-int eqf_batch_get_sigma(eqf_batch* b, int slot, double* sig, int n) {
-    if (!batch_slot_ok(b, slot) || !sig || n != 21 + 3 * (int)b->s[slot].ids.size())
-        return EQF_E_BAD_ARG;
-    BatchDevice dev(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(hipMemcpy2D(sig, sizeof(double) * n, batch_sig(b, slot, b->s[slot].cur), sizeof(double) * b->ld, sizeof(double) * n, n, hipMemcpyDeviceToHost));
-    return 0;
-}
-int eqf_batch_state_estimate(eqf_batch* b, int slot, double* sensor, int* ids, double* p, int cap) {
-    if (!batch_slot_ok(b, slot))
-        return EQF_E_BAD_ARG;
-    eqf_batch::Slot& sl = b->s[slot];
-    const int N = (int)sl.ids.size();
-    if (N > cap)
-        return EQF_E_CAPACITY;
-    BatchDevice dev(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (sensor)
-        pack_sensor(sensor_action(sl.X, sl.xi0), sensor);
-    std::vector<double> lm;
-    if (int rc = batch_fetch_landmarks(b, slot, lm))
-        return rc;
-    for (int i = 0; i < N; ++i) {
-        if (ids)
-            ids[i] = sl.ids[i];
-        if (p) { // stateGroupAction landmark part: q_hat = Q^-1 q0 (VIOGroup.cpp:45-52)
-            const double* e = lm.data() + 8 * i;
-            const V3 qh = (1.0 / e[7]) * q_rot(q_inv(Qt{e[3], e[4], e[5], e[6]}), v3(e[0], e[1], e[2]));
-            pack_v3(qh, p + 3 * i);
-        }
-    }
-    return N;
-}
-int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth) {
-    if (!batch_slot_ok(b, slot))
-        return EQF_E_BAD_ARG;
-    if (flags)
-        *flags = b->s[slot].flags;
-    if (depth)
-        *depth = b->s[slot].depth;
-    return 0;
-}
-
-int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
-    if (!b || count < 0 || (count > 0 && (!frames || !status)))
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    BatchDevice dev(b);
-    int total_steps = 0;
-    for (int e = 0; e < count; ++e)
-        total_steps += std::max(frames[e].k, 0);
-    if (int rc = batch_grow_packets(b, count, total_steps))
-        return rc;
-    // host half: validation, the landmark bookkeeping the ids decide, the sensor-level terms and the observer steps' sensor part
-    std::vector<int> entry_of(b->slots, -1), listed;
-    std::vector<GroupSensor> X_after(count);
-    std::vector<std::vector<int>> surv_ids(count), new_ids(count);
-    std::vector<int> removed_old(count, 0);
-    int nin = 0, nsteps = 0;
-    std::vector<int> in_of(count, -1);
-    for (int e = 0; e < count; ++e) {
-        const eqf_batch_frame& f = frames[e];
-        status[e] = 0;
-        if (!batch_slot_ok(b, f.slot) || entry_of[f.slot] >= 0 || f.M < 0 || f.k < 0 || (f.M > 0 && (!f.ids || !f.y)) || !f.imu13_mean ||
-            (f.k > 0 && (!f.imu13_k || !f.dt_k)) || !camera_ok(&f.cam)) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        bool asc = true;
-        for (int j = 1; j < f.M; ++j)
-            asc = asc && f.ids[j] > f.ids[j - 1];
-        if (!asc) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        entry_of[f.slot] = e;
-        eqf_batch::Slot& sl = b->s[f.slot];
-        const int N0 = (int)sl.ids.size();
-        // removeOldLandmarks (VIOFilter.cpp:280-302) and the ids addNewLandmarks will append (:258-278)
-        std::vector<int> surv;
-        for (int i = 0; i < N0; ++i)
-            if (!sl.set.removeLostLandmarks || std::binary_search(f.ids, f.ids + f.M, sl.ids[i]))
-                surv.push_back(i);
-        std::vector<int> midx(f.M);
-        int nnew = 0;
-        for (int j = 0; j < f.M; ++j) {
-            int found = -1;
-            for (size_t t = 0; t < surv.size(); ++t)
-                if (sl.ids[surv[t]] == f.ids[j]) {
-                    found = (int)t;
-                    break;
-                }
-            if (found < 0)
-                for (int i = 0; i < N0 && found < 0; ++i)
-                    if (sl.ids[i] == f.ids[j])
-                        found = -2; // unmeasured-and-removed cannot happen: a measured id survives
-            midx[j] = found >= 0 ? found : -(1 + nnew++);
-        }
-        if ((int)surv.size() + nnew > b->cap || f.M > b->cap) {
-            status[e] = EQF_E_CAPACITY;
-            entry_of[f.slot] = -1;
-            continue;
-        }
-        BatchIn& in = b->h_in[nin];
-        in.slot = f.slot;
-        in.cur = sl.cur;
-        in.Ns = (int)surv.size();
-        in.M = f.M;
-        in.nnew = nnew;
-        in.k = f.k;
-        in.obs_off = nsteps;
-        in.max_outliers = (int)(size_t)((1.0 - sl.set.featureRetention) * f.M); // removeOutliers (VIOFilter.cpp:305)
-        in.ss = sl.ss;
-        Cam cam = make_cam(&f.cam);
-        in.cam = cam;
-        in.dt = f.dt_total;
-        for (size_t t = 0; t < surv.size(); ++t)
-            in.surv[t] = (int)surv[t];
-        for (int j = 0; j < f.M; ++j) {
-            in.midx[j] = midx[j];
-            in.y[2 * j] = f.y[2 * j];
-            in.y[2 * j + 1] = f.y[2 * j + 1];
-            if (midx[j] < 0) {
-                const V3 br = cam_undistort(cam, f.y[2 * j], f.y[2 * j + 1]); // measurement.cameraPtr->undistortPoint (VIOFilter.cpp:264)
-                const int r = -midx[j] - 1;
-                in.bear[3 * r] = br.x, in.bear[3 * r + 1] = br.y, in.bear[3 * r + 2] = br.z;
-                new_ids[e].push_back(f.ids[j]);
-            }
-        }
-        Common cm;
-        compute_common_at(sl.X, sl.xi0, f.imu13_mean, cm, in.ck); // integrateRiccatiStateFast at the current X
-        GroupSensor X = sl.X;
-        for (int s = 0; s < f.k; ++s)
-            observer_host_step(X, sl.xi0, f.imu13_k + 13 * s, f.dt_k[s], sl.set.useDiscreteVelocityLift, b->h_steps[nsteps + s]);
-        nsteps += f.k;
-        X_after[e] = X;
-        for (int i : surv)
-            surv_ids[e].push_back(sl.ids[i]);
-        removed_old[e] = (int)surv.size() < N0;
-        in_of[e] = nin++;
-    }
-    if (nin == 0)
-        return 0;
-    BatchArgs ba;
-    ba.ld = b->ld;
-    ba.sig = b->d_sig;
-    ba.lm = b->d_lm;
-    ba.scr = b->d_scr;
-    ba.sig_stride = b->sig_stride;
-    ba.lm_stride = b->lm_stride;
-    ba.scr_stride = b->scr_stride;
-    ba.in = b->d_in;
-    ba.steps = b->d_steps;
-    ba.out = b->d_out;
-    HIPCHK(hipMemcpyAsync(b->d_in, b->h_in, sizeof(BatchIn) * nin, hipMemcpyHostToDevice, b->stream));
-    if (nsteps)
-        HIPCHK(hipMemcpyAsync(b->d_steps, b->h_steps, sizeof(ObsStep) * nsteps, hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_batch_frame, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, sizeof(BatchOut) * nin, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    // host half of the results: landmark ids, the sensor lift
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        const BatchOut& o = b->h_out[in_of[e]];
-        eqf_batch::Slot& sl = b->s[frames[e].slot];
-        sl.X = X_after[e];
-        std::vector<int> ids;
-        for (size_t t = 0; t < surv_ids[e].size(); ++t)
-            if (!((o.outliers >> t) & 1ull))
-                ids.push_back(surv_ids[e][t]);
-        ids.insert(ids.end(), new_ids[e].begin(), new_ids[e].end());
-        int flags = (removed_old[e] ? EQF_BATCH_REMOVED_OLD : 0) | ((o.did & BATCH_DID_OUTLIERS) ? EQF_BATCH_REMOVED_OUTLIERS : 0) |
-                    ((o.did & BATCH_DID_ADDED) ? EQF_BATCH_ADDED : 0) | ((o.did & BATCH_DID_EMPTY) ? EQF_BATCH_EMPTY : 0);
-        if (o.status == 0 && (o.did & BATCH_DID_UPDATE)) {
-            sl.X = group_mul(sensor_lift_delta(o.gamma, sl.xi0, sl.set.coordinateChoice, sl.set.useDiscreteInnovationLift), sl.X);
-            flags |= EQF_BATCH_UPDATED;
-            if (o.did & BATCH_DID_INVALID) {
-                std::vector<int> kept;
-                for (size_t t = 0; t < ids.size(); ++t)
-                    if (!((o.invalid >> t) & 1ull))
-                        kept.push_back(ids[t]);
-                ids.swap(kept);
-                flags |= EQF_BATCH_REMOVED_INVALID;
-            }
-        } else if (o.status != 0) {
-            status[e] = o.status;
-        }
-        sl.ids.swap(ids);
-        sl.cur = o.cur;
-        sl.flags = flags;
-        sl.depth = o.depth;
-        sl.inn_dof = o.dof;
-        sl.inn_nis = o.nis;
-        sl.inn_logdet = o.logdet;
-        if (flags & EQF_BATCH_UPDATED) {
-            sl.tot_updates += 1;
-            sl.tot_dof += o.dof;
-            sl.tot_nis += o.nis;
-            sl.tot_logdet += o.logdet;
-        }
-        if ((int)sl.ids.size() != o.N)
-            status[e] = EQF_E_BAD_ARG; // bookkeeping disagreement: cannot happen
-    }
-    return 0;
-}
-
-int eqf_batch_last_innovation(const eqf_batch* b, int slot, int* dof, double* nis, double* logdet) {
-    if (!batch_slot_ok(b, slot))
-        return EQF_E_BAD_ARG;
-    const eqf_batch::Slot& sl = b->s[slot];
-    if (dof)
-        *dof = sl.inn_dof;
-    if (nis)
-        *nis = sl.inn_nis;
-    if (logdet)
-        *logdet = sl.inn_logdet;
-    return 0;
-}
-int eqf_batch_innovation_totals(const eqf_batch* b, int slot, long* updates, long* dof, double* nis, double* logdet) {
-    if (!batch_slot_ok(b, slot))
-        return EQF_E_BAD_ARG;
-    const eqf_batch::Slot& sl = b->s[slot];
-    if (updates)
-        *updates = sl.tot_updates;
-    if (dof)
-        *dof = sl.tot_dof;
-    if (nis)
-        *nis = sl.tot_nis;
-    if (logdet)
-        *logdet = sl.tot_logdet;
-    return 0;
-}
-int eqf_batch_reset_innovation_totals(eqf_batch* b, int slot) {
-    if (!b || slot >= b->slots)
-        return EQF_E_BAD_ARG;
-    for (int k = slot < 0 ? 0 : slot; k < (slot < 0 ? b->slots : slot + 1); ++k) {
-        eqf_batch::Slot& sl = b->s[k];
-        sl.tot_updates = sl.tot_dof = 0;
-        sl.tot_nis = sl.tot_logdet = 0.0;
-    }
-    return 0;
-}
-
-namespace {
-// a pinned host packet and its device copy, grown to n entries
-template <typename T> int batch_grow_pair(T*& h, T*& d, int& cap, int n) {
-    if (n <= cap)
-        return 0;
-    if (h)
-        HIPCHK(hipHostFree(h));
-    if (d)
-        HIPCHK(hipFree(d));
-    h = nullptr, d = nullptr, cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h, sizeof(T) * n, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&d, sizeof(T) * n));
-    cap = n;
-    return 0;
-}
-} // namespace
-
-namespace {
-// The host half eqf_batch_nees and eqf_batch_consistency share: the per-entry refusals, and for every accepted entry its packet in b->h_nin (the sensor
-// entries of eps - eqf_compute_nees's code -, the true points in state order). in_of[e]: entry e's packet, or -1; returns the packets.
-int batch_nees_pack(eqf_batch* b, int count, const eqf_batch_truth* truths, int* status, std::vector<int>& in_of) {
-    std::vector<int> listed(b->slots, 0), jt;
-    std::vector<std::pair<int, int>> order;
-    in_of.assign(count, -1);
-    int nin = 0;
-    for (int e = 0; e < count; ++e) {
-        const eqf_batch_truth& t = truths[e];
-        status[e] = 0;
-        if (!batch_slot_ok(b, t.slot) || listed[t.slot] || !t.sensor || t.n_true < 0 || (t.n_true > 0 && (!t.ids || !t.p))) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        listed[t.slot] = 1;
-        const eqf_batch::Slot& sl = b->s[t.slot];
-        const int N = (int)sl.ids.size();
-        order.resize(N);
-        for (int i = 0; i < N; ++i)
-            order[i] = {sl.ids[i], i};
-        std::sort(order.begin(), order.end());
-        jt.assign(N, -1);
-        for (int k = 0; k < t.n_true; ++k) { // the first true landmark of an id, as eqf_compute_nees
-            const auto it = std::lower_bound(order.begin(), order.end(), std::make_pair(t.ids[k], -1));
-            if (it != order.end() && it->first == t.ids[k] && jt[it->second] < 0)
-                jt[it->second] = k;
-        }
-        if (std::find(jt.begin(), jt.end(), -1) != jt.end()) {
-            status[e] = EQF_E_BAD_ARG; // the reference asserts the true state holds every filter landmark
-            continue;
-        }
-        NeesIn& in = b->h_nin[nin];
-        in.slot = t.slot;
-        in.cur = sl.cur;
-        in.N = N;
-        in.chart = sl.set.coordinateChoice;
-        nees_sensor_error(sl.xi0, sl.X, sl.set.coordinateChoice, t.sensor, in.eps);
-        for (int i = 0; i < N; ++i)
-            for (int c = 0; c < 3; ++c)
-                in.p[3 * i + c] = t.p[3 * jt[i] + c];
-        in_of[e] = nin++;
-    }
-    return nin;
-}
-NeesArgs batch_nees_args(eqf_batch* b) {
-    NeesArgs na;
-    na.ld = b->ld;
-    na.sig = b->d_sig;
-    na.lm = b->d_lm;
-    na.scr = b->d_scr;
-    na.sig_stride = b->sig_stride;
-    na.lm_stride = b->lm_stride;
-    na.scr_stride = b->scr_stride;
-    na.in = b->d_nin;
-    na.out = b->d_nout;
-    return na;
-}
-} // namespace
-
-int eqf_batch_nees(eqf_batch* b, int count, const eqf_batch_truth* truths, double* nees, int* status) {
-    if (!b || count < 0 || (count > 0 && (!truths || !nees || !status)))
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    BatchDevice dev(b);
-    if (int rc = batch_grow_pair(b->h_nin, b->d_nin, b->nin_cap, count))
-        return rc;
-    if (int rc = batch_grow_pair(b->h_nout, b->d_nout, b->nout_cap, count))
-        return rc;
-    for (int e = 0; e < count; ++e)
-        nees[e] = std::nan("");
-    std::vector<int> in_of;
-    const int nin = batch_nees_pack(b, count, truths, status, in_of);
-    if (nin == 0)
-        return 0;
-    const NeesArgs na = batch_nees_args(b);
-    HIPCHK(hipMemcpyAsync(b->d_nin, b->h_nin, sizeof(NeesIn) * nin, hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_batch_nees, dim3(nin), dim3(BATCH_T), 0, b->stream, na);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_nout, b->d_nout, sizeof(NeesOut) * nin, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        const NeesOut& o = b->h_nout[in_of[e]];
-        eqf_batch::Slot& sl = b->s[truths[e].slot];
-        nees[e] = o.sumsq / (double)(21 + 3 * (int)sl.ids.size());
-        sl.nees_lu += o.lu;
-    }
-    return 0;
-}
-int eqf_batch_consistency(eqf_batch* b, int count, const eqf_batch_truth* truths, eqf_batch_consistency_record* out, int* status) {
-    if (!b || count < 0 || (count > 0 && (!truths || !out || !status)))
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    BatchDevice dev(b);
-    if (int rc = batch_grow_pair(b->h_nin, b->d_nin, b->nin_cap, count))
-        return rc;
-    if (int rc = batch_grow_pair(b->h_rec, b->d_rec, b->rec_cap, count))
-        return rc;
-    std::vector<int> in_of;
-    const int nin = batch_nees_pack(b, count, truths, status, in_of);
-    if (nin == 0)
-        return 0;
-    const NeesArgs na = batch_nees_args(b); // na.out is not used: the kernel writes the records
-    HIPCHK(hipMemcpyAsync(b->d_nin, b->h_nin, sizeof(NeesIn) * nin, hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_batch_consistency, dim3(nin), dim3(BATCH_T), 0, b->stream, na, b->d_rec);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_rec, b->d_rec, sizeof(eqf_batch_consistency_record) * nin, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        eqf_batch::Slot& sl = b->s[truths[e].slot];
-        eqf_batch_consistency_record& r = out[e];
-        r = b->h_rec[in_of[e]];
-        const int N = (int)sl.ids.size();
-        r.nees = r.nees / (double)(21 + 3 * N); // the kernel left eps^T Sigma^-1 eps there
-        for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
-            r.ids[i] = i < N ? sl.ids[i] : 0;
-        sl.nees_lu += r.lu;
-    }
-    return 0;
-}
-// One packet, one launch of k_batch_estimate over the accepted entries, one copy back, one synchronisation. The host's part of a record (N, ids, the sensor
-// estimate by eqf_batch_state_estimate's expression) is written into out[e] after the copy; a refused entry's out[e] is never touched.
-int eqf_batch_estimates(eqf_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, int* status) {
-    if (!b || count < 0 || !slots || !out || !status)
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    std::vector<int> listed(b->slots, 0), in_of(count, -1);
-    int nin = 0;
-    for (int e = 0; e < count; ++e) { // the refusals, before any device is looked at
-        status[e] = 0;
-        if (!batch_slot_ok(b, slots[e]) || listed[slots[e]]) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        listed[slots[e]] = 1;
-        in_of[e] = nin++;
-    }
-    if (nin == 0)
-        return 0;
-    BatchDevice dev(b);
-    if (int rc = batch_grow_pair(b->h_ein, b->d_ein, b->ein_cap, nin))
-        return rc;
-    if (int rc = batch_grow_pair(b->h_erec, b->d_erec, b->erec_cap, nin))
-        return rc;
-    std::vector<SensorState> est(nin);
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        const eqf_batch::Slot& sl = b->s[slots[e]];
-        EstIn& in = b->h_ein[in_of[e]];
-        in.slot = slots[e];
-        in.cur = sl.cur;
-        in.N = (int)sl.ids.size();
-        in.pad = 0;
-        est[in_of[e]] = sensor_action(sl.X, sl.xi0);
-        in.pc = pose_mul(est[in_of[e]].pose, est[in_of[e]].cam);
-    }
-    EstArgs ea;
-    ea.ld = b->ld;
-    ea.sig = b->d_sig;
-    ea.lm = b->d_lm;
-    ea.sig_stride = b->sig_stride;
-    ea.lm_stride = b->lm_stride;
-    ea.in = b->d_ein;
-    ea.rec = b->d_erec;
-    HIPCHK(hipMemcpyAsync(b->d_ein, b->h_ein, sizeof(EstIn) * nin, hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_batch_estimate, dim3(nin), dim3(BATCH_T), 0, b->stream, ea);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_erec, b->d_erec, sizeof(eqf_batch_estimate_record) * nin, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        const eqf_batch::Slot& sl = b->s[slots[e]];
-        eqf_batch_estimate_record& r = out[e];
-        r = b->h_erec[in_of[e]]; // p, p_world, sigma_sensor
-        const int N = (int)sl.ids.size();
-        r.N = N;
-        r.reserved = 0;
-        pack_sensor(est[in_of[e]], r.sensor);
-        for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
-            r.ids[i] = i < N ? sl.ids[i] : 0;
-    }
-    return 0;
-}
-int eqf_batch_nees_lu_fallbacks(const eqf_batch* b, int slot, long* count) {
-    if (!batch_slot_ok(b, slot) || !count)
-        return EQF_E_BAD_ARG;
-    *count = b->s[slot].nees_lu;
-    return 0;
-}
-
-int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* entries, int* status) {
-    if (!b || count < 0 || (count > 0 && (!entries || !status)))
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    BatchDevice dev(b);
-    if (int rc = batch_grow_pair(b->h_ain, b->d_ain, b->aug_cap, count))
-        return rc;
-    std::vector<int> listed(b->slots, 0), in_of(count, -1);
-    std::vector<std::vector<int>> ids_after(count);
-    int nin = 0;
-    for (int e = 0; e < count; ++e) {
-        const eqf_batch_augment_entry& a = entries[e];
-        status[e] = 0;
-        if (!batch_slot_ok(b, a.slot) || listed[a.slot] || a.n_new < 0 || a.n_prov < 0 || (a.n_new > 0 && !a.new_ids) || (a.n_prov > 0 && (!a.prov_ids || !a.prov_p))) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        listed[a.slot] = 1;
-        const eqf_batch::Slot& sl = b->s[a.slot];
-        const int N0 = (int)sl.ids.size();
-        // removeOldLandmarks(newIds) (VIOFilter.cpp:280-302): the landmarks whose id is in newIds stay, in state order
-        std::vector<int> keep, ids;
-        for (int i = 0; i < N0; ++i)
-            if (std::find(a.new_ids, a.new_ids + a.n_new, sl.ids[i]) != a.new_ids + a.n_new) {
-                keep.push_back(i);
-                ids.push_back(sl.ids[i]);
-            }
-        const int nk = (int)keep.size();
-        // the ids of newIds not in the state, in newIds order, with the provided state's first landmark of that id (VIOFilter.cpp:118-127)
-        std::vector<int> from;
-        bool missing = false;
-        for (int j = 0; j < a.n_new && !missing; ++j) {
-            const int id = a.new_ids[j];
-            if (std::find(ids.begin(), ids.begin() + nk, id) != ids.begin() + nk)
-                continue;
-            const int* it = std::find(a.prov_ids, a.prov_ids + a.n_prov, id);
-            if (it == a.prov_ids + a.n_prov)
-                missing = true;
-            from.push_back((int)(it - a.prov_ids));
-            ids.push_back(id);
-        }
-        if (missing) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        if ((int)ids.size() > b->cap) {
-            status[e] = EQF_E_CAPACITY;
-            continue;
-        }
-        if (nk == N0 && from.empty())
-            continue; // nothing leaves, nothing comes: the slot stays as it is
-        AugIn& in = b->h_ain[nin];
-        in.slot = a.slot;
-        in.cur = sl.cur;
-        in.Nk = nk;
-        in.nnew = (int)from.size();
-        in.init_var = sl.set.initialPointVariance;
-        for (int i = 0; i < nk; ++i)
-            in.keep[i] = keep[i];
-        for (size_t r = 0; r < from.size(); ++r)
-            for (int c = 0; c < 3; ++c)
-                in.p[3 * r + c] = a.prov_p[3 * (size_t)from[r] + c];
-        ids_after[e].swap(ids);
-        in_of[e] = nin++;
-    }
-    if (nin == 0)
-        return 0;
-    AugArgs aa;
-    aa.ld = b->ld;
-    aa.sig = b->d_sig;
-    aa.lm = b->d_lm;
-    aa.sig_stride = b->sig_stride;
-    aa.lm_stride = b->lm_stride;
-    aa.in = b->d_ain;
-    HIPCHK(hipMemcpyAsync(b->d_ain, b->h_ain, sizeof(AugIn) * nin, hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_batch_augment, dim3(nin), dim3(BATCH_T), 0, b->stream, aa);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        eqf_batch::Slot& sl = b->s[entries[e].slot];
-        sl.ids.swap(ids_after[e]);
-        sl.cur ^= 1;
-    }
-    return 0;
-}
-
-// One launch for every accepted entry, one synchronisation. Everything that refuses an entry is decided on the host before the launch.
-int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst, int* status) {
-    if (!b || count < 0 || !src || !dst || !status)
-        return EQF_E_BAD_ARG;
-    if (count == 0)
-        return 0;
-    std::vector<int> listed(b->slots, 0), in_of(count, -1);
-    int nin = 0;
-    for (int e = 0; e < count; ++e) {
-        status[e] = 0;
-        if (!batch_slot_ok(b, src[e]) || !batch_slot_ok(b, dst[e]) || listed[dst[e]]) {
-            status[e] = EQF_E_BAD_ARG;
-            continue;
-        }
-        const eqf_batch::Slot &from = b->s[src[e]], &to = b->s[dst[e]];
-        if (!from.ids.empty() && to.set.coordinateChoice != from.set.coordinateChoice) {
-            status[e] = EQF_E_BAD_ARG; // the source's Sigma is in its own chart's coordinates (eqf_batch_set_slot_settings's rule)
-            continue;
-        }
-        listed[dst[e]] = 1;
-        if (src[e] != dst[e])
-            in_of[e] = nin++;
-    }
-    if (nin == 0)
-        return 0;
-    if (b->ld % 2 || b->sig_stride % 2 || b->lm_stride % 2)
-        return EQF_E_BAD_ARG; // k_batch_copy moves pairs of doubles: a column, a plane and a buffer must start on 16 bytes (pick_ld gives an even ld today)
-    BatchDevice dev(b);
-    if (int rc = batch_grow_pair(b->h_cin, b->d_cin, b->copy_cap, nin))
-        return rc;
-    // the sources' host halves as they are BEFORE the call: a slot may be a destination of one entry and the source of another
-    struct HostHalf {
-        SensorState xi0;
-        GroupSensor X;
-        std::vector<int> ids;
-    };
-    std::vector<HostHalf> held(nin);
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        const eqf_batch::Slot &from = b->s[src[e]], &to = b->s[dst[e]];
-        CopyIn& in = b->h_cin[in_of[e]];
-        in.src = src[e];
-        in.scur = from.cur;
-        in.dst = dst[e];
-        in.dnxt = to.cur ^ 1;
-        in.N = (int)from.ids.size();
-        held[in_of[e]] = HostHalf{from.xi0, from.X, from.ids};
-    }
-    CopyArgs ca;
-    ca.ld = b->ld;
-    ca.sig = b->d_sig;
-    ca.lm = b->d_lm;
-    ca.sig_stride = b->sig_stride;
-    ca.lm_stride = b->lm_stride;
-    ca.in = b->d_cin;
-    HIPCHK(hipMemcpyAsync(b->d_cin, b->h_cin, sizeof(CopyIn) * nin, hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(k_batch_copy, dim3(nin, BATCH_COPY_CHUNKS), dim3(BATCH_T), 0, b->stream, ca);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int e = 0; e < count; ++e) {
-        if (in_of[e] < 0)
-            continue;
-        eqf_batch::Slot& to = b->s[dst[e]];
-        HostHalf& h = held[in_of[e]];
-        to.xi0 = h.xi0;
-        to.X = h.X;
-        to.ids.swap(h.ids);
-        to.cur ^= 1;
-        to.flags = 0; // the last step's outcome was another state's: as a slot that never stepped
-        to.depth = 0.0;
-        to.inn_dof = 0;
-        to.inn_nis = to.inn_logdet = 0.0;
-    }
-    return 0;
-}
+// Filter batch (include/eqf_batch.h): its host side, in this translation unit for the helpers above
+#include "eqf_batch_host.hpp"

@@ -325,14 +325,11 @@ int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* s, int device, i
     if (!out || !s)
         return EQF_E_BAD_ARG;
     *out = nullptr;
-    { // the checks of eqf_batch_create, before anything touches a device
-        if (slots < 1 || max_landmarks < 1 || max_landmarks > EQF_BATCH_MAX_LANDMARKS || device < 0)
-            return EQF_E_BAD_ARG;
-        if (s->coordinateChoice < EQVIO_COORD_EUCLIDEAN || s->coordinateChoice > EQVIO_COORD_NORMAL)
-            return EQF_E_BAD_ARG;
-        if (!s->fastRiccati || s->coordinateChoice == EQVIO_COORD_NORMAL)
-            return EQF_E_UNSUPPORTED;
-    }
+    // the checks of eqf_batch_create, before anything touches a device: the sizes, then the settings
+    if (slots < 1 || max_landmarks < 1 || max_landmarks > EQF_BATCH_MAX_LANDMARKS || device < 0)
+        return EQF_E_BAD_ARG;
+    if (const int rc = eqf_batch_check_settings(s))
+        return rc;
     eqf_batch* core = nullptr;
     const int rc = eqf_batch_create(&core, device, slots, max_landmarks, s); // EQF_E_NO_DEVICE without a gfx950 device
     if (rc)
