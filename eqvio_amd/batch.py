@@ -65,6 +65,26 @@ class BatchEstimateRecord(C.Structure):
                 "ids": np.array(self.ids, dtype=np.int32)[:N], "p": np.array(self.p)[: 3 * N].reshape(N, 3), "p_world": np.array(self.p_world)[: 3 * N].reshape(N, 3)}
 
 
+class BatchPredictionEntry(C.Structure):
+    """eqf_batch_prediction_entry (include/eqf_batch.h)."""
+
+    _fields_ = [("slot", C.c_int), ("cam", Camera), ("k", C.c_int), ("imu13_k", c_double_p), ("dt_k", c_double_p)]
+
+
+class BatchPredictionRecord(C.Structure):
+    """eqf_batch_prediction_record (include/eqf_batch.h)."""
+
+    _fields_ = [("N", C.c_int), ("reserved", C.c_int), ("sensor", C.c_double * 23), ("ids", C.c_int * EQF_BATCH_MAX_LANDMARKS),
+                ("p", C.c_double * (3 * EQF_BATCH_MAX_LANDMARKS)), ("y", C.c_double * (2 * EQF_BATCH_MAX_LANDMARKS)),
+                ("out_cov", C.c_double * (4 * EQF_BATCH_MAX_LANDMARKS))]
+
+    def trimmed(self):
+        """The record as a dict of numpy arrays trimmed to N: sensor[23], ids[N], p (N, 3), y (N, 2), out_cov (N, 2, 2)."""
+        N = self.N
+        return {"N": N, "sensor": np.array(self.sensor), "ids": np.array(self.ids, dtype=np.int32)[:N], "p": np.array(self.p)[: 3 * N].reshape(N, 3),
+                "y": np.array(self.y)[: 2 * N].reshape(N, 2), "out_cov": np.array(self.out_cov)[: 4 * N].reshape(N, 2, 2)}
+
+
 def load_batch_protos():
     """Declare the prototypes of include/eqf_batch.h on libeqf_hip.so and of include/eqvio_batch.h on libeqvio_filter.so."""
     elib, flib = load_eqf_lib(), load_filter_lib()
@@ -85,6 +105,7 @@ def load_batch_protos():
         "eqf_batch_set_sigma": (C.c_int, [vp, C.c_int, c_double_p, C.c_int]),
         "eqf_batch_get_sigma": (C.c_int, [vp, C.c_int, c_double_p, C.c_int]),
         "eqf_batch_state_estimate": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int]),
+        "eqf_batch_sensor_estimate": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqf_batch_step": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
         "eqf_batch_last_result": (C.c_int, [vp, C.c_int, c_int_p, c_double_p]),
         "eqf_batch_stream": (vp, [vp]),
@@ -93,6 +114,7 @@ def load_batch_protos():
         "eqf_batch_nees_lu_fallbacks": (C.c_int, [vp, C.c_int, P(C.c_long)]),
         "eqf_batch_consistency": (C.c_int, [vp, C.c_int, P(BatchTruth), P(BatchConsistencyRecord), c_int_p]),
         "eqf_batch_estimates": (C.c_int, [vp, C.c_int, c_int_p, P(BatchEstimateRecord), c_int_p]),
+        "eqf_batch_predictions": (C.c_int, [vp, C.c_int, P(BatchPredictionEntry), P(BatchPredictionRecord), c_int_p]),
         "eqf_batch_augment": (C.c_int, [vp, C.c_int, P(BatchAugmentEntry), c_int_p]),
         "eqf_batch_last_innovation": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_double_p]),
         "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
@@ -112,6 +134,7 @@ def load_batch_protos():
         "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
         "eqvio_batch_run_prepared_recorded": (C.c_int, [vp, P(vp), C.c_int, C.c_int, C.c_char_p]),
         "eqvio_batch_estimates": (C.c_int, [vp, C.c_int, c_int_p, P(BatchEstimateRecord), c_double_p, c_int_p]),
+        "eqvio_batch_feature_predictions": (C.c_int, [vp, C.c_int, c_int_p, P(Camera), c_double_p, P(BatchPredictionRecord), c_int_p]),
         "eqvio_batch_state_estimate": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int]),
         "eqvio_batch_get_eqf": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
         "eqvio_batch_force_eqf": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int, c_double_p]),
@@ -252,6 +275,38 @@ class VIOFilterBatch:
         times, status = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
         self._chk(self.lib.eqvio_batch_estimates(self.h, n, _ip(sl), rec, _dp(times), _ip(status)))
         return rec, times[:n].copy(), status[:n].copy()
+
+    def predictions(self, entries, rec=None):
+        """Device level (eqf_batch_predictions). entries: list of (slot, cam, imus[k, 13], dts[k]): the slot's estimate taken through integrateSystemFunction
+        with the k samples and dts, its landmarks projected through cam, and their output covariances at the current estimate, for every listed slot in ONE
+        launch. Returns (records, status): the untrimmed BatchPredictionRecord array (rec, or a new zeroed one; a refused entry's record is left as it was;
+        .trimmed() gives numpy arrays) and the per-entry status codes."""
+        n = len(entries)
+        arr = (BatchPredictionEntry * max(n, 1))()
+        keep = []
+        for e, (slot, cam, imus, dts) in enumerate(entries):
+            imus, dts = _f64(imus).reshape(-1), _f64(dts).reshape(-1)
+            keep.append((imus, dts))
+            arr[e].slot, arr[e].cam, arr[e].k = slot, cam, len(dts)
+            arr[e].imu13_k = _dp(imus) if len(dts) else None
+            arr[e].dt_k = _dp(dts) if len(dts) else None
+        rec = (BatchPredictionRecord * max(n, 1))() if rec is None else rec
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.elib.eqf_batch_predictions(self.core_handle(), n, arr, rec, _ip(status)))
+        return rec, status[:n].copy()
+
+    def feature_predictions(self, entries, rec=None):
+        """Filter level (eqvio_batch_feature_predictions). entries: list of (slot, cam, stamp): getFeaturePredictions(cam, stamp) of every listed slot in ONE
+        launch, each slot's samples and dts taken from its own IMU buffer and time. A slot whose settings have useFeaturePredictions off gets N = 0. Returns
+        (records, status) as predictions."""
+        n = len(entries)
+        slots = _i32([e[0] for e in entries] if n else np.zeros(1, np.int32))
+        cams = (Camera * max(n, 1))(*[e[1] for e in entries])
+        stamps = _f64([e[2] for e in entries] if n else np.zeros(1))
+        rec = (BatchPredictionRecord * max(n, 1))() if rec is None else rec
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_feature_predictions(self.h, n, _ip(slots), cams, _dp(stamps), rec, _ip(status)))
+        return rec, status[:n].copy()
 
     def compute_nees(self, entries):
         """entries: list of (slot, true_sensor[23], true_ids, true_p[n, 3]). viewEqFState().computeNEES of every listed slot in ONE launch; returns the NEES
@@ -413,6 +468,14 @@ class BatchSlot:
         st = self.b.augment_landmark_states([(self.k, new_ids, ids, p)])
         if st[0] != 0:
             raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
+
+    def feature_predictions(self, cam, stamp):
+        """getFeaturePredictions(cam, stamp) of this slot (VIOFilterBatch.feature_predictions): (ids[N], y (N, 2), out_cov (N, 2, 2))."""
+        rec, st = self.b.feature_predictions([(self.k, cam, stamp)])
+        if st[0] != 0:
+            raise BatchError(f"slot {self.k}: {self.b.elib.eqf_error_string(int(st[0])).decode()}", int(st[0]))
+        r = rec[0].trimmed()
+        return r["ids"], r["y"], r["out_cov"]
 
     def state_estimate(self):
         s, ids, p = np.zeros(23), np.zeros(self.cap, np.int32), np.zeros(3 * self.cap)

@@ -1,5 +1,5 @@
 // Filter batch (include/eqf_batch.h): B independent filters of at most 64 landmarks, one workgroup per slot, ONE launch per frame of all of them.
-// The device side: the packet structs and the six kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
+// The device side: the packet structs and the seven kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
 // eqf_hip.hip includes both. Every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
 //
 // Per slot s, in HBM (fp64): two Sigma buffers (n x n column-major, leading dimension ld, n <= 21 + 3 * 64), two landmark buffers (35 SoA planes of stride
@@ -1160,6 +1160,59 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_estimate(const EstArgs ea) {
     }
     for (int t = tid; t < 441; t += BATCH_T)
         rec->sigma_sensor[t] = S[t % 21 + (size_t)(t / 21) * ld];
+}
+
+// eqf_batch_predictions (include/eqf_batch.h): entry e's workgroup, a lane per landmark, reads its slot's CURRENT landmark planes and Sigma buffer and writes,
+// into rec[e], landmark i's predicted camera-frame point p = T p_hat_i (p_hat = Q^-1 q0, eqf_batch_state_estimate's expression; T the product of the
+// cameraPoseChangeInv of the host's predictState steps, the identity for none), its pixel cam.projectPoint(p), and getOutputCovById's C0_i Sigma_ii C0_i^T at the
+// current estimate (k_output_cov's expressions: measure_one without the equivariant output, whose block does not depend on the pixel). A point with depth <= 0
+// gets whatever cam_project gives. Entries beyond N are written as 0. N, the ids and the predicted sensor state are the host's and are filled in there. The
+// kernel writes nothing but the record: no LDS, no scratch area, no reduction - a record's bytes do not depend on the launch it is part of.
+struct PredIn {
+    int slot, cur, N, chart;
+    Cam cam;
+    Pose T;
+};
+struct PredArgs {
+    BatchBufs buf;
+    const PredIn* in;
+    eqf_batch_prediction_record* rec;
+};
+constexpr int BATCH_PRED_T = BATCH_L; // one wave: a lane per landmark
+__global__ void __launch_bounds__(BATCH_PRED_T) k_batch_predict(const PredArgs pa) {
+    const PredIn& in = pa.in[blockIdx.x];
+    eqf_batch_prediction_record* rec = pa.rec + blockIdx.x;
+    const int i = threadIdx.x, L = BATCH_L, ld = pa.buf.ld;
+    V3 p{0.0, 0.0, 0.0};
+    double yu = 0.0, yv = 0.0, v[4] = {0.0, 0.0, 0.0, 0.0};
+    if (i < in.N) {
+        const double* Sig = pa.buf.sig_of(in.slot, in.cur);
+        const double* lm = pa.buf.lm_of(in.slot, in.cur);
+        p = pose_act(in.T, batch_point_estimate(lm, i));
+        cam_project(in.cam, p, yu, yv);
+        const MeasOut o = measure_one(in.chart, in.cam, ld3(lm, L, i), ldq(lm + BATCH_QQ * L, L, i), lm[BATCH_QA * L + i], 0.0, 0.0, false,
+                                      in.chart == EQVIO_COORD_INVDEPTH ? ld_cc(lm, L, i, CC_R0) : M3{});
+        const int l = 21 + 3 * i;
+        double S[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                S[r][c] = Sig[l + r + (size_t)(l + c) * ld];
+        double CS[2][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                CS[r][c] = o.c[r * 3 + 0] * S[0][c] + o.c[r * 3 + 1] * S[1][c] + o.c[r * 3 + 2] * S[2][c];
+        v[0] = CS[0][0] * o.c[0] + CS[0][1] * o.c[1] + CS[0][2] * o.c[2];
+        v[1] = CS[0][0] * o.c[3] + CS[0][1] * o.c[4] + CS[0][2] * o.c[5];
+        v[2] = CS[1][0] * o.c[0] + CS[1][1] * o.c[1] + CS[1][2] * o.c[2];
+        v[3] = CS[1][0] * o.c[3] + CS[1][1] * o.c[4] + CS[1][2] * o.c[5];
+    }
+    rec->p[3 * i] = p.x, rec->p[3 * i + 1] = p.y, rec->p[3 * i + 2] = p.z;
+    rec->y[2 * i] = yu, rec->y[2 * i + 1] = yv;
+    rec->out_cov[4 * i] = v[0], rec->out_cov[4 * i + 1] = v[1], rec->out_cov[4 * i + 2] = v[2], rec->out_cov[4 * i + 3] = v[3];
 }
 
 } // namespace eqf

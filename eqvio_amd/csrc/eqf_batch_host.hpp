@@ -60,6 +60,8 @@ struct eqf_batch {
     BatchPacket<CopyIn> cin; // eqf_batch_copy_slots
     BatchPacket<EstIn> ein;  // eqf_batch_estimates
     BatchPacket<eqf_batch_estimate_record> erec;
+    BatchPacket<PredIn> pin; // eqf_batch_predictions
+    BatchPacket<eqf_batch_prediction_record> prec;
     std::vector<Slot> s;
 };
 
@@ -224,6 +226,8 @@ void eqf_batch_destroy(eqf_batch* b) {
     b->cin.release();
     b->ein.release();
     b->erec.release();
+    b->pin.release();
+    b->prec.release();
     if (b->stream)
         (void)hipStreamDestroy(b->stream);
     delete b;
@@ -355,6 +359,12 @@ int eqf_batch_state_estimate(eqf_batch* b, int slot, double* sensor, int* ids, d
         }
     }
     return N;
+}
+int eqf_batch_sensor_estimate(const eqf_batch* b, int slot, double* sensor) {
+    if (!batch_slot_ok(b, slot) || !sensor)
+        return EQF_E_BAD_ARG;
+    pack_sensor(sensor_action(b->s[slot].X, b->s[slot].xi0), sensor);
+    return 0;
 }
 int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth) {
     if (!batch_slot_ok(b, slot))
@@ -720,6 +730,97 @@ int eqf_batch_estimates(eqf_batch* b, int count, const int* slots, eqf_batch_est
         r.N = N;
         r.reserved = 0;
         pack_sensor(est[scr.in_of[e]], r.sensor);
+        for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
+            r.ids[i] = i < N ? sl.ids[i] : 0;
+    }
+    return 0;
+}
+namespace {
+// integrateSystemFunction (VIOState.cpp:28-68), sensor part, with the arithmetic of the single filter's host mirror (eqvio_amd/host/VIOFilter.cpp): s becomes
+// the integrated state; returns the step's cameraPoseChangeInv, which takes every camera-frame landmark along
+Pose predict_sensor_step(SensorState& s, const double* imu13, double dt) {
+    const V3 gyr = v3(imu13[1], imu13[2], imu13[3]) - s.bgyr; // v_est = velocity - bias (IMUVelocity.cpp:52-58)
+    const V3 acc = v3(imu13[4], imu13[5], imu13[6]) - s.bacc;
+    const V3 gravity{0, 0, -kGravity};
+    SensorState ns;
+    ns.bgyr = s.bgyr + dt * v3(imu13[7], imu13[8], imu13[9]);
+    ns.bacc = s.bacc + dt * v3(imu13[10], imu13[11], imu13[12]);
+    Pose poseChange;
+    poseChange.R = so3_exp(dt * gyr);
+    const V3 inertialStep = dt * q_rot(s.pose.R, s.vel) + (0.5 * dt * dt) * (q_rot(s.pose.R, acc) + gravity);
+    poseChange.x = q_rot(q_inv(s.pose.R), inertialStep);
+    ns.pose = pose_mul(s.pose, poseChange);
+    const V3 inertialVelocityDiff = q_rot(s.pose.R, acc) + gravity;
+    ns.vel = q_rot(q_inv(ns.pose.R), q_rot(s.pose.R, s.vel) + dt * inertialVelocityDiff);
+    ns.cam = s.cam;
+    const Pose cameraPoseChangeInv = pose_mul(pose_mul(pose_inv(s.cam), pose_inv(poseChange)), s.cam);
+    s = ns;
+    return cameraPoseChangeInv;
+}
+} // namespace
+
+// One packet, one launch of k_batch_predict over the accepted entries, one copy back, one synchronisation. The host does the sensor-level chain of
+// predictState (k steps on 23 doubles) and folds the steps' cameraPoseChangeInv into one pose, so a packet entry has a fixed size whatever k is; its part of a
+// record (N, ids, the predicted sensor state) is written into out[e] after the copy; a refused entry's out[e] is never touched.
+int eqf_batch_predictions(eqf_batch* b, int count, const eqf_batch_prediction_entry* entries, eqf_batch_prediction_record* out, int* status) {
+    if (!b || count < 0 || (count > 0 && (!entries || !out || !status)))
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchScreen scr(b, count);
+    for (int e = 0; e < count; ++e) { // the refusals, before any device is looked at
+        const eqf_batch_prediction_entry& p = entries[e];
+        status[e] = 0;
+        bool ok = scr.fresh(b, p.slot) && camera_ok(&p.cam) && p.k >= 0 && (p.k == 0 || (p.imu13_k && p.dt_k));
+        for (int j = 0; ok && j < p.k; ++j)
+            ok = std::isfinite(p.dt_k[j]) && p.dt_k[j] >= 0.0;
+        if (!ok) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        scr.list(p.slot);
+        scr.accept(e);
+    }
+    const int nin = scr.nin;
+    if (nin == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = b->pin.grow(nin))
+        return rc;
+    if (int rc = b->prec.grow(nin))
+        return rc;
+    std::vector<SensorState> pred(nin);
+    for (int e = 0; e < count; ++e) {
+        if (scr.in_of[e] < 0)
+            continue;
+        const eqf_batch_prediction_entry& p = entries[e];
+        const eqf_batch::Slot& sl = b->s[p.slot];
+        PredIn& in = b->pin.h[scr.in_of[e]];
+        in.slot = p.slot;
+        in.cur = sl.cur;
+        in.N = (int)sl.ids.size();
+        in.chart = sl.set.coordinateChoice;
+        in.cam = make_cam(&p.cam);
+        SensorState& s = pred[scr.in_of[e]];
+        s = sensor_action(sl.X, sl.xi0);
+        in.T = pose_identity();
+        for (int j = 0; j < p.k; ++j)
+            in.T = pose_mul(predict_sensor_step(s, p.imu13_k + 13 * j, p.dt_k[j]), in.T);
+    }
+    const PredArgs pa{b->buf, b->pin.d, b->prec.d};
+    const auto launch = [&] { hipLaunchKernelGGL(k_batch_predict, dim3(nin), dim3(BATCH_PRED_T), 0, b->stream, pa); };
+    if (int rc = batch_round_trip(b, b->pin, nin, launch, &b->prec))
+        return rc;
+    for (int e = 0; e < count; ++e) {
+        if (scr.in_of[e] < 0)
+            continue;
+        const eqf_batch::Slot& sl = b->s[entries[e].slot];
+        eqf_batch_prediction_record& r = out[e];
+        r = b->prec.h[scr.in_of[e]]; // p, y, out_cov
+        const int N = (int)sl.ids.size();
+        r.N = N;
+        r.reserved = 0;
+        pack_sensor(pred[scr.in_of[e]], r.sensor);
         for (int i = 0; i < EQF_BATCH_MAX_LANDMARKS; ++i)
             r.ids[i] = i < N ? sl.ids[i] : 0;
     }

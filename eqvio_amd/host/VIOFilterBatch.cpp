@@ -15,14 +15,18 @@
 
 namespace eqvio_amd {
 
-ImuSelection selectImu(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime) { // VIOFilter.cpp:134-156
-    ImuSelection s;
-    s.dts.resize(buffer.size());
+std::vector<double> imuDts(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime) { // VIOFilter.cpp:137-145, VIO_eqf.cpp:142-147
+    std::vector<double> dts(buffer.size());
     for (size_t i = 0; i < buffer.size(); ++i) {
         const double t0 = std::max(buffer.at(i).stamp, currentTime);
         const double t1 = i + 1 < buffer.size() ? std::min(buffer.at(i + 1).stamp, newTime) : newTime;
-        s.dts[i] = std::max(t1 - t0, 0.0);
+        dts[i] = std::max(t1 - t0, 0.0);
     }
+    return dts;
+}
+ImuSelection selectImu(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime) { // VIOFilter.cpp:134-156
+    ImuSelection s;
+    s.dts = imuDts(buffer, currentTime, newTime);
     IMUVelocity acc = IMUVelocity::Zero();
     for (size_t i = 0; i < buffer.size(); ++i) {
         s.total += s.dts[i];
@@ -275,6 +279,51 @@ void VIOFilterBatch::processVisionData(int count, const int* slots, const double
     }
     stepPrepared(slots, stamps, status);
 }
+// getFeaturePredictions (VIOFilter.cpp:247-252) of every listed slot: the (sample, dt) lists of predictState from the slots' own buffers and times, then ONE
+// eqf_batch_predictions call for the slots whose settings have useFeaturePredictions on
+int VIOFilterBatch::getFeaturePredictions(int count, const int* slots, const eqvio_camera* cams, const double* stamps, eqf_batch_prediction_record* out, int* status) {
+    std::vector<eqf_batch_prediction_entry> entries;
+    std::vector<int> entryOf;
+    std::vector<std::vector<double>> imus, dts;
+    std::vector<char> listed(slotv.size(), 0);
+    entries.reserve(count), entryOf.reserve(count), imus.reserve(count), dts.reserve(count);
+    for (int e = 0; e < count; ++e) {
+        const int k = slots[e];
+        status[e] = 0;
+        if (k < 0 || k >= (int)slotv.size() || listed[k]) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        listed[k] = 1;
+        if (!slotSettings(k).useFeaturePredictions) { // the reference's empty measurement: nothing goes to the device
+            std::memset(&out[e], 0, sizeof(out[e]));
+            check(eqf_batch_sensor_estimate(batch, k, out[e].sensor), "eqf_batch_sensor_estimate");
+            continue;
+        }
+        const Slot& sl = slotv[k];
+        dts.push_back(imuDts(sl.velocityBuffer, sl.currentTime, stamps[e]));
+        imus.emplace_back(13 * sl.velocityBuffer.size());
+        for (size_t i = 0; i < sl.velocityBuffer.size(); ++i)
+            sl.velocityBuffer[i].pack(imus.back().data() + 13 * i);
+        entries.push_back(eqf_batch_prediction_entry{k, cams[e], (int)sl.velocityBuffer.size(), imus.back().data(), dts.back().data()});
+        entryOf.push_back(e);
+    }
+    const int n = (int)entries.size();
+    if (n == 0)
+        return 0;
+    if (n == count) // every entry goes: the records and codes land where the caller wants them
+        return eqf_batch_predictions(batch, n, entries.data(), out, status);
+    std::vector<eqf_batch_prediction_record> rec(n);
+    std::vector<int> st(n, 0);
+    if (const int rc = eqf_batch_predictions(batch, n, entries.data(), rec.data(), st.data()))
+        return rc;
+    for (int t = 0; t < n; ++t) {
+        status[entryOf[t]] = st[t];
+        if (st[t] == 0)
+            out[entryOf[t]] = rec[t];
+    }
+    return 0;
+}
 void VIOFilterBatch::processVisionData(int count, const int* slots, const VisionMeasurement* const* meas, int* status) {
     frames_.clear(), entry_.clear();
     std::vector<double> stamps(count);
@@ -402,6 +451,14 @@ int eqvio_batch_copy_slots(eqvio_batch* b, int count, const int* src, const int*
     if (!b || count < 0 || !src || !dst || !status)
         return EQF_E_BAD_ARG;
     return guarded(b, [&] { b->f->copySlots(count, src, dst, status); });
+}
+int eqvio_batch_feature_predictions(eqvio_batch* b, int count, const int* slots, const eqvio_camera* cams, const double* stamps, eqf_batch_prediction_record* out,
+                                    int* status) {
+    if (!b || count < 0 || !slots || !cams || !stamps || !out || !status)
+        return EQF_E_BAD_ARG;
+    int code = 0;
+    const int rc = guarded(b, [&] { code = b->f->getFeaturePredictions(count, slots, cams, stamps, out, status); });
+    return rc ? rc : code;
 }
 int eqvio_batch_estimates(eqvio_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, double* times, int* status) {
     if (!b || count < 0 || !slots || !out || !status)

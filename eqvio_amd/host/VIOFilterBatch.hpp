@@ -17,6 +17,8 @@ struct ImuSelection {
     IMUVelocity mean;
     double total = 0;
 };
+// the dt of every buffered sample up to newTime: the loop integrateUpToTime and VIO_eqf::predictState (VIO_eqf.cpp:139-151) share
+std::vector<double> imuDts(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime);
 ImuSelection selectImu(const std::vector<IMUVelocity>& buffer, double currentTime, double newTime);
 void trimImuBuffer(std::vector<IMUVelocity>& buffer, double currentTime);
 
@@ -60,6 +62,12 @@ class VIOFilterBatch {
                            const double* y_all, int* status);
     // the same for measurements already built (a replay's VisionMeasurement objects): one device step for every listed slot
     void processVisionData(int count, const int* slots, const VisionMeasurement* const* meas, int* status);
+    // getFeaturePredictions(cams[e], stamps[e]) (VIOFilter.cpp:247-252) of `count` distinct slots: each slot's state estimate pushed through its own buffered
+    // IMU samples up to the stamp (predictState's dts from its velocityBuffer and currentTime) and projected, with the landmarks' output covariances, in ONE
+    // eqf_batch_predictions call. A slot whose settings have useFeaturePredictions off gets the reference's empty measurement - N = 0, every array zero, sensor
+    // its current estimate, status 0 - and is not sent to the device; a slot that has not initialised has no sample: its current estimate. status[e] 0 or
+    // EQF_E_BAD_ARG (bad or repeated slot, bad camera: out[e] untouched). Nothing of any slot changes. Returns eqf_batch_predictions's code.
+    int getFeaturePredictions(int count, const int* slots, const eqvio_camera* cams, const double* stamps, eqf_batch_prediction_record* out, int* status);
     // the innovation statistics of the slot's updated steps since the last reset (eqf_batch_innovation_totals: the numbers are the device batch's)
     struct InnovationTotals {
         long updates = 0, dof = 0;

@@ -7,6 +7,8 @@
 // same converged filter, and the scores count the frames after the warm-up only.
 // --batch B --record DIR writes every slot's trajectory (the four state files of --output) to DIR/run_<k>/, and --batch B --groundtruth FILE scores every slot's
 // trajectory against ground truth: both from ONE estimates call per vision measurement over the live slots (eqf_batch_estimates).
+// --batch B --predictions scores every slot by how far a frame's measured features lie from where the slot predicted them (getFeaturePredictions at the
+// measurement's stamp, before the step): ONE predictions call per vision measurement over the live slots (eqf_batch_predictions).
 #include "DatasetReplay.hpp"
 #include "VIOFilterBatch.hpp"
 #include "VIOWriter.hpp"
@@ -29,7 +31,7 @@ static void usage() {
               "                 [--cameraFile sensor.yaml | camchain.yaml]   (intrinsics, distortion and camera offset from the dataset's own file, main_opt.cpp:114-147)\n"
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F]] [--record DIR]]\n"
+              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F]] [--record DIR] [--predictions]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
@@ -39,6 +41,10 @@ static void usage() {
               "  --record DIR   with --batch B: slot k's IMUState.csv, camera.csv, bias.csv and points.csv (the formats of --output) go to DIR/run_<k>/, one row per\n"
               "              vision measurement per live slot, from one estimates call over the live slots per measurement. With --warmup F slots 1 .. B-1 start\n"
               "              their files at the branch.\n"
+              "  --predictions   with --batch B: switches useFeaturePredictions on and, per vision measurement, asks every live slot where it expects its\n"
+              "              landmarks at the measurement's stamp (one predictions call over the live slots, after the IMU samples, before the step). Prints one\n"
+              "              more line per slot: the RMSE in pixels between predicted and measured features over the ids present in both - a score of the\n"
+              "              propagation side of a tuning that needs no true state. With --warmup F the frames after the warm-up count.\n"
               "  --sweep NAME=v0,...,v(B-1)   with --batch B: slot k runs with the filter setting NAME (a field of eqvio_settings) at value vk. Needs exactly B values.\n"
               "  --warmup F   with --batch B --sweep: the first F vision frames run in slot 0 alone, with the command line's settings; slot 0 is then copied into\n"
               "              slots 1 .. B-1 on the device, the sweep's values go to all B slots, and the scores count the frames after the warm-up only.\n"
@@ -48,7 +54,7 @@ static void usage() {
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
 static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime,
-                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth) {
+                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -64,6 +70,11 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         writers[k] = makeRunWriter(recordDir, k); // before any frame runs
     std::vector<eqf_batch_estimate_record> records(B);
     std::vector<std::vector<StampedPose>> trajectories(B);
+    // --predictions: per slot the sum of |y_pred - y_meas|^2 over the ids in both, and their number
+    std::vector<eqf_batch_prediction_record> predicted(predictions ? B : 0);
+    std::vector<eqvio_camera> predCams(B);
+    std::vector<double> predStamps(B), predSq(B, 0.0);
+    std::vector<long> predCount(B, 0);
     auto applySweep = [&] {
         for (int k = 0; k < B && swept; ++k) {
             eqvio_settings ek = es;
@@ -109,6 +120,23 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
                 continue;
             if (!branched && visionDataCounter == warmup)
                 branch(); // before the first frame after the warm-up, and behind every IMU sample that came before it
+            if (predictions && branched) { // where every live slot expects its landmarks at this stamp: one call, before the step
+                std::fill(predCams.begin(), predCams.end(), measData.cameraPtr->c);
+                std::fill(predStamps.begin(), predStamps.end(), measData.stamp);
+                check_rc(filters.getFeaturePredictions(live, slots.data(), predCams.data(), predStamps.data(), predicted.data(), status.data()), "eqf_batch_predictions");
+                for (int k = 0; k < live; ++k) {
+                    check_rc(status[k], "eqf_batch_predictions");
+                    const eqf_batch_prediction_record& r = predicted[k];
+                    for (int i = 0; i < r.N; ++i) {
+                        const auto it = measData.camCoordinates.find(r.ids[i]);
+                        if (it == measData.camCoordinates.end())
+                            continue;
+                        const double du = r.y[2 * i] - it->second[0], dv = r.y[2 * i + 1] - it->second[1];
+                        predSq[k] += du * du + dv * dv;
+                        ++predCount[k];
+                    }
+                }
+            }
             const std::vector<const VisionMeasurement*> meas(B, &measData);
             filters.processVisionData(live, slots.data(), meas.data(), status.data()); // one device step for all live slots
             for (int k = 0; k < live; ++k) {
@@ -162,6 +190,10 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
         std::printf("slot %d%s: position RMSE %.9g over %d frames\n", k, what.c_str(), t.rmse, t.frames);
     }
+    for (int k = 0; k < B && predictions; ++k) {
+        const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
+        std::printf("slot %d%s: prediction RMSE %.9g px over %ld features\n", k, what.c_str(), std::sqrt(predSq[k] / (double)predCount[k]), predCount[k]);
+    }
     std::printf("batch of %d slots: slots x vision updates/s %.1f\n", B, (double)B * visionDataCounter / elapsed);
     return 0;
 }
@@ -178,7 +210,7 @@ int main(int argc, char** argv) {
     cam->c.width = 752;
     cam->c.height = 480;
     double cameraLag = 0, startTime = -1, stopTime = -1;
-    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false;
+    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false;
     int batch = 0;
     std::string warmupText;
     Sweep sweep;
@@ -234,6 +266,7 @@ int main(int argc, char** argv) {
             else if (a == "--printCamera") printCamera = true;
             else if (a == "--batch") batch = std::atoi(val());
             else if (a == "--record") recordDir = val();
+            else if (a == "--predictions") predictions = true;
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
                 haveSweep = true;
@@ -254,6 +287,12 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "eqvio_opt: --record needs --batch\n");
             return 2;
         }
+        if (predictions && batch == 0) { // before any file or device is opened
+            std::fprintf(stderr, "eqvio_opt: --predictions needs --batch\n");
+            return 2;
+        }
+        if (predictions)
+            fs.useFeaturePredictions = true;
         int warmup = 0;
         if (haveWarmup) { // before any file or device is opened, as the refusals of --batch
             char* end = nullptr;
@@ -329,7 +368,7 @@ int main(int argc, char** argv) {
             std::vector<StampedPose> gt;
             if (!gtName.empty())
                 gt = TrackReplayServer::groundtruth(gtName, format);
-            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions);
         }
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150

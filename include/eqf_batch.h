@@ -82,6 +82,10 @@ int eqf_batch_num_landmarks(const eqf_batch* b, int slot);
 /* stateGroupAction(X, xi0): the 23 sensor doubles, ids and landmark points (3 per landmark). Returns N or < 0. */
 int eqf_batch_state_estimate(eqf_batch* b, int slot, double* sensor, int* ids, double* p, int cap);
 
+/* stateGroupAction(X, xi0), sensor part: eqf_batch_state_estimate's 23 doubles, bit for bit, from the host's half of the slot alone - no device is looked at,
+ * nothing is copied or synchronised. Returns 0, or EQF_E_BAD_ARG for a null batch, a bad slot or a null sensor. */
+int eqf_batch_sensor_estimate(const eqf_batch* b, int slot, double* sensor);
+
 /* Advances the `count` listed slots (distinct) by one frame each: one packet to the device, one launch, one copy back, one synchronisation.
  * A slot that is not listed is not touched, bit for bit. status[e] (count entries) is the result of entry e:
  *   0                  done;
@@ -185,6 +189,44 @@ typedef struct eqf_batch_estimate_record {
  * Returns 0 when the launch ran (whatever the per-entry codes) or count == 0, EQF_E_BAD_ARG for a null batch, slots, out or status or count < 0 (checked
  * before any device is looked at), or a HIP error. */
 int eqf_batch_estimates(eqf_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, int* status);
+
+/* One slot's prediction request for eqf_batch_predictions: the camera, and the (sample, dt) list VIO_eqf::predictState would integrate. */
+typedef struct eqf_batch_prediction_entry {
+    int slot;
+    eqvio_camera cam;
+    int k;                 /* steps of predictState, >= 0 */
+    const double* imu13_k; /* k samples of 13 doubles (eqf_batch_frame's layout); may be null when k == 0 */
+    const double* dt_k;    /* their dts, each >= 0 */
+} eqf_batch_prediction_entry;
+
+/* One slot's feature predictions. Entries of the fixed-size arrays beyond N read 0. */
+typedef struct eqf_batch_prediction_record {
+    int N, reserved;                              /* landmarks of the slot; 0 */
+    double sensor[23];                            /* sensor part of the predicted state (eqvio_types.h layout) */
+    int ids[EQF_BATCH_MAX_LANDMARKS];             /* state order */
+    double p[3 * EQF_BATCH_MAX_LANDMARKS];        /* predicted camera-frame points */
+    double y[2 * EQF_BATCH_MAX_LANDMARKS];        /* their pixels: cam.projectPoint(p) */
+    double out_cov[4 * EQF_BATCH_MAX_LANDMARKS];  /* getOutputCovById at the CURRENT estimate, row-major 2 x 2 */
+} eqf_batch_prediction_record;
+
+/* What VIOFilter::getFeaturePredictions (VIOFilter.cpp:247-252) and VIO_eqf::getOutputCovById (VIO_eqf.cpp:196-211) give, for the `count` listed slots
+ * (distinct): one packet to the device, one launch (k_batch_predict, one workgroup per accepted entry, a lane per landmark), one copy back, one
+ * synchronisation, whatever count is; nothing but the records crosses to the host.
+ * The predicted state is stateGroupAction(X, xi0) taken through integrateSystemFunction(state, imu_j, dt_j) for j = 0 .. k-1 (VIO_eqf::predictState's loop
+ * with the dts given). The host does the chain's sensor part - sensor is its result - and folds the steps' cameraPoseChangeInv into one pose T; the slot's
+ * workgroup forms p_i = T Q_i^-1 q0_i from its current landmark planes and y_i = cam.projectPoint(p_i). k == 0 gives the current estimate and its pixels:
+ * the yHat of removeOutliers, with p equal to eqf_batch_state_estimate's to rounding. A landmark whose predicted depth is <= 0 gets whatever the camera
+ * model's projection gives for it (non-finite or mirrored pixels), as in the single filter: it is not flagged.
+ * out_cov[4 i ..] is C0_i Sigma_ii C0_i^T with C0_i = outputMatrixCi at the slot's current xi0, X, Sigma and chart for entries[e].cam - eqf_output_cov_all's
+ * quantity. It does not depend on k, imu13_k or dt_k: like the reference's getOutputCovById it is not propagated to the stamp.
+ * The call is read-only: no slot's state, Sigma, landmark planes, settings, innovation totals, last innovation, last result or LU-fallback count change. A
+ * slot's record has the same bytes whichever call it is part of: alone, among others in any order, in a batch of any size (nothing is summed). status[e]:
+ *   0                  done;
+ *   EQF_E_BAD_ARG      bad slot index, repeated slot, bad camera, k < 0, k > 0 with a null imu13_k or dt_k, or a dt that is negative or not finite: out[e]
+ *                      is left untouched, byte for byte; the other entries are still done.
+ * Returns 0 when the launch ran (whatever the per-entry codes) or count == 0, EQF_E_BAD_ARG for a null batch, for null entries, out or status with
+ * count > 0, or for count < 0 (checked before any device is looked at), or a HIP error. */
+int eqf_batch_predictions(eqf_batch* b, int count, const eqf_batch_prediction_entry* entries, eqf_batch_prediction_record* out, int* status);
 
 /* One slot's augmentLandmarkStates for eqf_batch_augment: the ids the slot keeps and adds (n_new), and the provided state's landmarks (n_prov ids and
  * camera-frame points) the new ones are taken from. */

@@ -91,6 +91,16 @@ int eqvio_batch_run_sim_recorded(eqvio_batch* b, eqvio_sim* const* sims, int max
  * created with (identity pose, the settings' camera offset, no landmark) and -1, as a single filter does. Returns 0, EQF_E_BAD_ARG (a null batch, slots, out
  * or status, count < 0) or a HIP error. */
 int eqvio_batch_estimates(eqvio_batch* b, int count, const int* slots, eqf_batch_estimate_record* out, double* times, int* status);
+/* getFeaturePredictions(cams[e], stamps[e]) (VIOFilter.cpp:247-252) of `count` distinct slots in ONE launch (eqf_batch_predictions, include/eqf_batch.h: same
+ * records, a refused entry's record is left untouched). Per listed slot the (sample, dt) list is VIO_eqf::predictState's (VIO_eqf.cpp:139-151), from the slot's
+ * own IMU buffer and current time: t0 = max(stamp_i, currentTime), t1 = min(stamp_{i+1}, stamps[e]) or stamps[e] for the last sample, dt = max(t1 - t0, 0).
+ * out[e].y are the predicted pixels by id, out[e].out_cov the landmarks' output covariances at the current estimate (not propagated to the stamp, as the
+ * reference's getOutputCovById). Like the reference, a slot whose settings have useFeaturePredictions == 0 gets N = 0 and every array zero, with sensor its
+ * current estimate and status 0; it is not sent to the device, and if no entry is sent nothing is launched. A slot that has not initialised has no sample and
+ * gives its current estimate (the state it was created with). status[e]: 0 or EQF_E_BAD_ARG (bad or repeated slot, bad camera). Nothing of any slot changes.
+ * Returns 0, EQF_E_BAD_ARG (a null batch, slots, cams, stamps, out or status, count < 0), a HIP error or -1 (eqvio_batch_last_error). */
+int eqvio_batch_feature_predictions(eqvio_batch* b, int count, const int* slots, const eqvio_camera* cams, const double* stamps, eqf_batch_prediction_record* out,
+                                    int* status);
 /* per slot: stateEstimate, viewEqFState (xi0, X, Sigma), getTime, isInitialised, and the forcing of a whole EqF state (teacher forcing) */
 int eqvio_batch_state_estimate(eqvio_batch* b, int slot, double* sensor, int* ids, double* p, int cap); /* returns N or < 0 */
 int eqvio_batch_get_eqf(eqvio_batch* b, int slot, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap);
