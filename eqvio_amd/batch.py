@@ -120,6 +120,8 @@ def load_batch_protos():
         "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqf_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
         "eqf_batch_copy_slots": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
+        "eqf_batch_load_ctx": (C.c_int, [vp, vp, C.c_int, c_int_p, c_int_p]),
+        "eqf_batch_store_ctx": (C.c_int, [vp, C.c_int, vp]),
     }
     fprotos = {
         "eqvio_batch_create": (C.c_int, [P(vp), P(Settings), C.c_int, C.c_int, C.c_int]),
@@ -152,10 +154,14 @@ def load_batch_protos():
         "eqvio_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqvio_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_copy_slots": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
+        "eqvio_batch_load_filter": (C.c_int, [vp, vp, C.c_int, c_int_p, c_int_p]),
+        "eqvio_batch_store_filter": (C.c_int, [vp, C.c_int, vp]),
     }
     for lib, protos in ((elib, eprotos), (flib, fprotos)):
         for name, (res, args) in protos.items():
-            fn = getattr(lib, name)
+            if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_batch_load_ctx", "eqf_batch_store_ctx", "eqvio_batch_load_filter", "eqvio_batch_store_filter") and not hasattr(lib, name):
+                continue  # same-box A/B against the libraries of an older commit (as capi.load_eqf_lib): entry points that commit did not have yet
+            fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
     elib._batch_declared = sorted(eprotos)
@@ -418,6 +424,28 @@ class VIOFilterBatch:
         self._chk(self.lib.eqvio_batch_copy_slots(self.h, n, _ip(src), _ip(dst), _ip(status)))
         return [int(v) for v in status[:n]]
 
+    def load_filter(self, filter, slots):
+        """Every listed slot becomes the capi.VIOFilter `filter` - EqF state, IMU buffer, time, initialised flag - in ONE launch, without Sigma or the
+        landmarks crossing to the host (eqvio_batch_load_filter). The slots keep their own settings and innovation totals; the filter is unchanged. Returns the
+        per-slot status codes (EQF_E_BAD_ARG: bad index, repeated slot, or a chart other than the filter's while it holds landmarks; that slot is untouched);
+        raises BatchError when the whole call is refused (Normal chart or float Sigma store: EQF_E_UNSUPPORTED; more landmarks than the batch's capacity:
+        EQF_E_CAPACITY) or failed."""
+        n = len(slots)
+        sl = _i32(list(slots) if n else np.zeros(1, np.int32))
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_load_filter(self.h, filter.h, n, _ip(sl), _ip(status)))
+        return [int(v) for v in status[:n]]
+
+    def load_core(self, core, slots):
+        """The device level of load_filter (eqf_batch_load_ctx): every listed slot comes to hold the EqF state of the capi.EqfCore `core` - xi0, X, ids,
+        landmarks, Sigma - bit for bit, in ONE launch. The slots' IMU buffers, times and initialised flags are not touched. Returns the per-slot status codes;
+        raises BatchError when the whole call is refused or failed."""
+        n = len(slots)
+        sl = _i32(list(slots) if n else np.zeros(1, np.int32))
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.elib.eqf_batch_load_ctx(self.core_handle(), core.h, n, _ip(sl), _ip(status)))
+        return [int(v) for v in status[:n]]
+
     def slot(self, k):
         if not 0 <= k < self.slots:
             raise IndexError(k)
@@ -441,6 +469,16 @@ class BatchSlot:
         """This slot into every slot of dsts (one slot or a list), one launch (VIOFilterBatch.copy_slots); returns the status codes."""
         dsts = [dsts] if isinstance(dsts, (int, np.integer)) else list(dsts)
         return self.b.copy_slots([(self.k, int(d)) for d in dsts])
+
+    def store_to(self, target):
+        """This slot into a capi.VIOFilter (EqF state and the host half: eqvio_batch_store_filter) or a capi.EqfCore (EqF state alone: eqf_batch_store_ctx),
+        one launch, as set_state + set_sigma with the slot's values would leave it. The slot is unchanged; a refusal raises BatchError with its code."""
+        from eqvio_amd.capi import EqfCore
+
+        if isinstance(target, EqfCore):
+            self.b._chk(self.b.elib.eqf_batch_store_ctx(self.b.core_handle(), self.k, target.h))
+        else:
+            self.b._chk(self.b.lib.eqvio_batch_store_filter(self.b.h, self.k, target.h))
 
     def process_imu(self, imu13):
         self.b.process_imu(self.k, imu13)

@@ -1,5 +1,5 @@
 // Filter batch (include/eqf_batch.h): B independent filters of at most 64 landmarks, one workgroup per slot, ONE launch per frame of all of them.
-// The device side: the packet structs and the seven kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
+// The device side: the packet structs and the eight kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
 // eqf_hip.hip includes both. Every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
 //
 // Per slot s, in HBM (fp64): two Sigma buffers (n x n column-major, leading dimension ld, n <= 21 + 3 * 64), two landmark buffers (35 SoA planes of stride
@@ -1126,6 +1126,74 @@ __global__ void __launch_bounds__(BATCH_T) k_batch_copy(const CopyArgs ca) {
         }
         if ((N & 1) && tid < BATCH_PLANES)
             D[tid * L + N - 1] = S[tid * L + N - 1];
+    }
+}
+
+// eqf_batch_load_ctx / eqf_batch_store_ctx (include/eqf_batch.h): k_batch_copy's copy with a context (eqf_hip.h) on one side. The context keeps the same
+// landmark planes in two arrays - q0 with its chart constants (30 planes), Qq and Qa (5 planes) - of plane stride Ncap, and Sigma with its own leading
+// dimension; the slot's side is a BATCH_L-strided landmark buffer and a Sigma buffer of leading dimension buf.ld.
+// TO_CTX false (load): entry e copies the context's current buffers into slot in[e].slot's pair in[e].which - the slot's OTHER pair, which the host then names
+// current, so what the slot held (more rows, more landmarks, a stale pair) is never read again: k_batch_copy's argument. TO_CTX true (store): the one entry
+// (ga.one; no packet) copies the slot's CURRENT pair into the context's current buffers, which eqf_set_state / eqf_set_sigma write in place as well.
+// Grid and the Sigma chunks are k_batch_copy's: x = entry, y = chunk of BATCH_COPY_COLS columns, 16-byte accesses (both leading dimensions are even and every
+// Sigma buffer starts on 16 bytes: the host checks). The last y also moves the landmarks, a lane per landmark: q0, Qq and Qa are copied; the 27 chart constants
+// are formed from q0 by store_chart_constants, the one function every kernel that creates a landmark calls (k_scatter_landmarks of eqf_set_state and
+// eqf_batch_set_state among them), so the destination's planes are those of the route through the host, bit for bit, whatever plane stride they were made at.
+struct BridgeCtx {
+    double* sig;   // the context's current Sigma buffer
+    double* st;    // q0 (3 planes) and the chart constants behind them (CC_OFF), plane stride Ncap
+    double *qq, *qa; // Qq (4 planes of stride Ncap), Qa
+    int ld, Ncap;
+};
+struct BridgeIn {
+    int slot, which; // the slot and the pair of its buffers the copy reads (store) or writes (load)
+};
+struct BridgeArgs {
+    BatchBufs buf;
+    BridgeCtx cx;
+    const BridgeIn* in; // load: one entry per block x
+    BridgeIn one;       // store: the entry itself
+    int N;              // landmarks of the source
+};
+template <bool TO_CTX> __global__ void __launch_bounds__(BATCH_T) k_batch_bridge(const BridgeArgs ga) {
+    const BridgeIn in = TO_CTX ? ga.one : ga.in[blockIdx.x];
+    const int tid = threadIdx.x, L = BATCH_L, Ncap = ga.cx.Ncap;
+    const int N = ga.N, n = 21 + 3 * N;
+    const int c0 = blockIdx.y * BATCH_COPY_COLS, cols = min(BATCH_COPY_COLS, n - c0);
+    const int lds = TO_CTX ? ga.buf.ld : ga.cx.ld, ldd = TO_CTX ? ga.cx.ld : ga.buf.ld;
+    if (cols > 0) {
+        const double* S = (TO_CTX ? ga.buf.sig_of(in.slot, in.which) : ga.cx.sig) + (size_t)c0 * lds;
+        double* D = (TO_CTX ? ga.cx.sig : ga.buf.sig_of(in.slot, in.which)) + (size_t)c0 * ldd;
+        const int half = n >> 1; // >= 10
+        for (int t = tid; t < cols * half; t += BATCH_T) {
+            const int c = t / half, r = 2 * (t % half);
+            *reinterpret_cast<double2*>(D + (size_t)c * ldd + r) = *reinterpret_cast<const double2*>(S + (size_t)c * lds + r);
+        }
+        if ((n & 1) && tid < cols)
+            D[(size_t)tid * ldd + n - 1] = S[(size_t)tid * lds + n - 1];
+    }
+    if (blockIdx.y == gridDim.y - 1 && tid < N) {
+        const int i = tid;
+        double* lm = ga.buf.lm_of(in.slot, in.which);
+        if (TO_CTX) {
+            const double px = lm[i], py = lm[L + i], pz = lm[2 * L + i];
+            ga.cx.st[i] = px;
+            ga.cx.st[Ncap + i] = py;
+            ga.cx.st[2 * (size_t)Ncap + i] = pz;
+            store_chart_constants(ga.cx.st + (size_t)CC_OFF * Ncap, Ncap, i, px, py, pz, nullptr);
+            for (int c = 0; c < 4; ++c)
+                ga.cx.qq[(size_t)c * Ncap + i] = lm[(BATCH_QQ + c) * L + i];
+            ga.cx.qa[i] = lm[BATCH_QA * L + i];
+        } else {
+            const double px = ga.cx.st[i], py = ga.cx.st[Ncap + i], pz = ga.cx.st[2 * (size_t)Ncap + i];
+            lm[i] = px;
+            lm[L + i] = py;
+            lm[2 * L + i] = pz;
+            store_chart_constants(lm + (size_t)CC_OFF * L, L, i, px, py, pz, nullptr);
+            for (int c = 0; c < 4; ++c)
+                lm[(BATCH_QQ + c) * L + i] = ga.cx.qq[(size_t)c * Ncap + i];
+            lm[BATCH_QA * L + i] = ga.cx.qa[i];
+        }
     }
 }
 

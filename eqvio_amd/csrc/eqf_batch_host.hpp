@@ -58,6 +58,7 @@ struct eqf_batch {
     BatchPacket<eqf_batch_consistency_record> rec;
     BatchPacket<AugIn> ain;  // eqf_batch_augment
     BatchPacket<CopyIn> cin; // eqf_batch_copy_slots
+    BatchPacket<BridgeIn> brin; // eqf_batch_load_ctx
     BatchPacket<EstIn> ein;  // eqf_batch_estimates
     BatchPacket<eqf_batch_estimate_record> erec;
     BatchPacket<PredIn> pin; // eqf_batch_predictions
@@ -224,6 +225,7 @@ void eqf_batch_destroy(eqf_batch* b) {
     b->rec.release();
     b->ain.release();
     b->cin.release();
+    b->brin.release();
     b->ein.release();
     b->erec.release();
     b->pin.release();
@@ -983,4 +985,120 @@ int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst
         to.inn_nis = to.inn_logdet = 0.0;
     }
     return 0;
+}
+
+namespace {
+// what both directions of the bridge refuse of a context, before any device work: another device, the Normal chart (its sensor block of Sigma is in other
+// coordinates), the float Sigma store
+int bridge_ctx_check(const eqf_batch* b, const eqf_ctx* c) {
+    if (c->device != b->device)
+        return EQF_E_BAD_ARG;
+    if (c->chart == EQVIO_COORD_NORMAL || c->sig32)
+        return EQF_E_UNSUPPORTED;
+    return 0;
+}
+// the context's current buffers as k_batch_bridge takes them: read after enter(), which may flip them
+BridgeCtx bridge_ctx_buffers(eqf_ctx* c) { return BridgeCtx{c->sigma(), c->q0(), c->Qq(), c->Qa(), c->ld, c->Ncap}; }
+// k_batch_bridge moves pairs of doubles (k_batch_copy's rule, for both sides)
+bool bridge_aligned(const eqf_batch* b, const eqf_ctx* c) {
+    return b->buf.ld % 2 == 0 && b->buf.sig_stride % 2 == 0 && c->ld % 2 == 0 && reinterpret_cast<uintptr_t>(c->d_sigma[c->cur]) % 16 == 0;
+}
+} // namespace
+
+// The context is entered the way eqf_get_state enters it - an update taken from the early doorbell settled, held landmarks appended, a pending reshape flushed,
+// the observer's stream joined -, the packet and the one launch go onto the CONTEXT's stream behind all of that, and the one wait is the context's. The batch is
+// idle between its calls (every one of them ends in a synchronisation), so nothing of the batch's stream has to be ordered.
+int eqf_batch_load_ctx(eqf_batch* b, eqf_ctx* src, int count, const int* slots, int* status) {
+    if (!b || !src || !slots || !status || count < 0)
+        return EQF_E_BAD_ARG;
+    if (int rc = bridge_ctx_check(b, src))
+        return rc;
+    if (src->N > b->cap)
+        return EQF_E_CAPACITY;
+    if (count == 0)
+        return 0;
+    BatchScreen scr(b, count);
+    for (int e = 0; e < count; ++e) {
+        status[e] = 0;
+        if (!scr.fresh(b, slots[e]) || (src->N > 0 && b->s[slots[e]].set.coordinateChoice != src->chart)) {
+            status[e] = EQF_E_BAD_ARG; // the context's Sigma is in its own chart's coordinates (eqf_batch_set_slot_settings's rule)
+            continue;
+        }
+        scr.list(slots[e]);
+        scr.accept(e);
+    }
+    const int nin = scr.nin;
+    if (nin == 0)
+        return 0;
+    BatchDevice dev(b);
+    if (int rc = b->brin.grow(nin))
+        return rc;
+    if (int rc = enter(src))
+        return rc;
+    if (int rc = join_observer(src))
+        return rc;
+    if (!bridge_aligned(b, src))
+        return EQF_E_BAD_ARG; // (pick_ld gives even leading dimensions and hipMalloc 16-byte aligned buffers today)
+    for (int e = 0; e < count; ++e)
+        if (scr.in_of[e] >= 0)
+            b->brin.h[scr.in_of[e]] = BridgeIn{slots[e], b->s[slots[e]].cur ^ 1};
+    const BridgeArgs ga{b->buf, bridge_ctx_buffers(src), b->brin.d, BridgeIn{0, 0}, src->N};
+    HIPCHK(hipMemcpyAsync(b->brin.d, b->brin.h, sizeof(BridgeIn) * nin, hipMemcpyHostToDevice, src->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_bridge<false>), dim3(nin, BATCH_COPY_CHUNKS), dim3(BATCH_T), 0, src->stream, ga);
+    HIPCHK(hipGetLastError());
+    if (int rc = sync_ctx(src))
+        return rc;
+    for (int e = 0; e < count; ++e) {
+        if (scr.in_of[e] < 0)
+            continue;
+        eqf_batch::Slot& to = b->s[slots[e]];
+        to.xi0 = src->xi0;
+        to.X = src->X;
+        to.ids = src->ids;
+        to.cur ^= 1;
+        to.flags = 0; // eqf_batch_copy_slots's rule: the last step's outcome was another state's
+        to.depth = 0.0;
+        to.inn_dof = 0;
+        to.inn_nis = to.inn_logdet = 0.0;
+    }
+    return 0;
+}
+
+// eqf_set_state + eqf_set_sigma with the slot's values, the landmarks and Sigma arriving by one launch on the context's stream instead of two copies from the
+// host: the same entry (enter, capacity), the same bookkeeping (estimate cache, device measurement, held landmarks, the landmark generation - which drops a
+// staged measurement, the id lookup and the mapped ids), the same rounding of Sigma for EQF_OPT_SIGMA_FP32 = 1, and one wait at the end.
+int eqf_batch_store_ctx(eqf_batch* b, int slot, eqf_ctx* dst) {
+    if (!b || !dst || !batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    if (int rc = bridge_ctx_check(b, dst))
+        return rc;
+    const eqf_batch::Slot& sl = b->s[slot];
+    const int N = (int)sl.ids.size();
+    if (N > 0 && sl.set.coordinateChoice != dst->chart)
+        return EQF_E_BAD_ARG;
+    BatchDevice dev(b);
+    if (int rc = enter(dst))
+        return rc;
+    if (N > dst->Ncap)
+        if (int rc = grow_capacity(dst, std::max(N, 2 * dst->Ncap)))
+            return rc;
+    if (int rc = join_observer(dst))
+        return rc;
+    if (!bridge_aligned(b, dst))
+        return EQF_E_BAD_ARG;
+    const BridgeArgs ga{b->buf, bridge_ctx_buffers(dst), nullptr, BridgeIn{slot, sl.cur}, N};
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_bridge<true>), dim3(1, BATCH_COPY_CHUNKS), dim3(BATCH_T), 0, dst->stream, ga);
+    HIPCHK(hipGetLastError());
+    dst->est_valid = false, ++dst->est_epoch; // eqf_set_state's lines
+    dst->meas_valid = false;
+    dst->n_held = 0, dst->held_in_memory = false;
+    dst->xi0 = sl.xi0;
+    dst->X = sl.X;
+    dst->ids = sl.ids;
+    dst->N = N;
+    dst->dev_N = N;
+    ++dst->lm_gen;
+    if (int rc = round_sigma(dst)) // eqf_set_sigma's (a launch of its own, only with EQF_OPT_SIGMA_FP32 = 1)
+        return rc;
+    return sync_ctx(dst);
 }

@@ -315,6 +315,11 @@ int VIO_eqf::settleInvalid() const {
     }
     return rc;
 }
+void VIO_eqf::refreshIds() {
+    invalidPending_ = false; // it belonged to the landmark set that was replaced
+    ids_.resize(eqf_num_landmarks(ctx));
+    eqf_get_ids(ctx, ids_.data(), (int)ids_.size());
+}
 void VIO_eqf::removeInvalidLandmarks() { // VIO_eqf.cpp:213-223
     if (eqf_update_unsettled(ctx) == 1) {
         invalidPending_ = true;
@@ -568,6 +573,12 @@ VIOFilter::VIOFilter(const VIOState& xi0, const VIOFilter::Settings& s, const do
     filterState.setSigmaDiag(settings->constructInitialStateCovarianceDiag(xi0.cameraLandmarks.size()));
     filterState.currentTime = time;
     initialisedFlag = true;
+}
+void VIOFilter::adoptHostState(const std::vector<IMUVelocity>& buffer, double time, bool initialised) {
+    filterState.refreshIds();
+    velocityBuffer = buffer;
+    filterState.currentTime = time;
+    initialisedFlag = initialised;
 }
 void VIOFilter::processIMUData(const IMUVelocity& imu) { // :58-63
     if (!initialisedFlag)

@@ -24,6 +24,8 @@
 #include <string>
 #include <vector>
 
+struct eqvio_filter; // the C-ABI handle of include/eqvio_filter.h
+
 namespace eqvio_amd {
 
 using eqf::Pose;
@@ -206,6 +208,7 @@ struct VIO_eqf {
     void removeLandmarkById(const int& id);
     void removeLandmarksByIndex(const std::vector<int>& idx); // batched form of the above
     void removeInvalidLandmarks();
+    void refreshIds(); // the context's landmark set was replaced behind this object's back (eqf_batch_store_ctx): the ids are read from it again
     int settleInvalid() const; // a removal of invalid landmarks deferred past an unsettled update (EQF_OPT_EARLY_DOORBELL) happens now; returns how many left
     bool removeUnmeasured(const std::vector<int>& measurementIds); // false: ids not ascending, nothing done
     bool sameAsMapped(const std::vector<int>& measurementIds) const; // exactly the ids the last update mapped, one per landmark
@@ -274,6 +277,9 @@ class VIOFilter {
     VIOState stateEstimate() const;
     const VIO_eqf& viewEqFState() const;
     VIO_eqf& eqfState() { return filterState; }
+    // what the filter keeps on the host beside the EqF state, for moving a whole filter in or out (VIOFilterBatch::loadFilter / storeFilter)
+    const std::vector<IMUVelocity>& imuBuffer() const { return velocityBuffer; }
+    void adoptHostState(const std::vector<IMUVelocity>& buffer, double time, bool initialised); // after the context was given another filter's EqF state
 };
 
 // VIOFilter::Settings (include/eqvio/VIOFilterSettings.h:58-124): same fields and defaults; the gain matrices
@@ -301,5 +307,8 @@ struct VIOFilter::Settings {
     std::array<double, 12> constructInputGainDiag() const;
     double constructOutputGainVar() const { return measurementNoise * measurementNoise; }
 };
+
+// the VIOFilter behind a C-ABI handle (include/eqvio_filter.h; defined with the handle in filter_capi.cpp), for the layers that move whole filters
+VIOFilter* filterOf(::eqvio_filter* f);
 
 } // namespace eqvio_amd

@@ -181,6 +181,27 @@ void VIOFilterBatch::copySlots(int count, const int* src, const int* dst, int* s
             slotv.at(dst[e]) = std::move(held[e]);
 }
 
+int VIOFilterBatch::loadFilter(VIOFilter& src, int count, const int* slots, int* status) {
+    src.eqfState().settleInvalid(); // what every view of the filter's state does first
+    if (const int rc = eqf_batch_load_ctx(batch, src.eqfState().ctx, count, slots, status))
+        return rc;
+    for (int e = 0; e < count; ++e)
+        if (status[e] == 0) {
+            Slot& sl = slotv.at(slots[e]);
+            sl.velocityBuffer = src.imuBuffer();
+            sl.currentTime = src.getTime();
+            sl.initialised = src.isInitialised();
+        }
+    return 0;
+}
+int VIOFilterBatch::storeFilter(int k, VIOFilter& dst) {
+    dst.eqfState().settleInvalid(); // a deferred removal belongs to the state that is about to be replaced: done, not carried over
+    if (const int rc = eqf_batch_store_ctx(batch, k, dst.eqfState().ctx))
+        return rc;
+    const Slot& sl = slotv.at(k);
+    dst.adoptHostState(sl.velocityBuffer, sl.currentTime, sl.initialised);
+    return 0;
+}
 void VIOFilterBatch::startFromState(int k, const double* sensor, const int* ids, const double* p, int N, double time) { // VIOFilter.cpp:43-56
     Slot& sl = slotv.at(k);
     std::vector<double> Q(5 * (size_t)N);
@@ -451,6 +472,20 @@ int eqvio_batch_copy_slots(eqvio_batch* b, int count, const int* src, const int*
     if (!b || count < 0 || !src || !dst || !status)
         return EQF_E_BAD_ARG;
     return guarded(b, [&] { b->f->copySlots(count, src, dst, status); });
+}
+int eqvio_batch_load_filter(eqvio_batch* b, eqvio_filter* src, int count, const int* slots, int* status) {
+    if (!b || !src || count < 0 || !slots || !status)
+        return EQF_E_BAD_ARG;
+    int code = 0;
+    const int rc = guarded(b, [&] { code = b->f->loadFilter(*eqvio_amd::filterOf(src), count, slots, status); });
+    return rc ? rc : code;
+}
+int eqvio_batch_store_filter(eqvio_batch* b, int slot, eqvio_filter* dst) {
+    if (!slot_ok(b, slot) || !dst)
+        return EQF_E_BAD_ARG;
+    int code = 0;
+    const int rc = guarded(b, [&] { code = b->f->storeFilter(slot, *eqvio_amd::filterOf(dst)); });
+    return rc ? rc : code;
 }
 int eqvio_batch_feature_predictions(eqvio_batch* b, int count, const int* slots, const eqvio_camera* cams, const double* stamps, eqf_batch_prediction_record* out,
                                     int* status) {

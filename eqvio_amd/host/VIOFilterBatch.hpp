@@ -55,6 +55,13 @@ class VIOFilterBatch {
     // Entry e: slot dst[e] becomes slot src[e] as it was before the call - the EqF state on the device (eqf_batch_copy_slots: one launch, same status codes)
     // and the host half: IMU buffer, current time, initialised flag. The destination keeps its settings and innovation totals. A refused entry changes nothing.
     void copySlots(int count, const int* src, const int* dst, int* status);
+    // Every listed slot becomes the filter: its EqF state on the device (eqf_batch_load_ctx: one launch for the whole call, same status codes; a whole-call
+    // refusal is returned and nothing changes) and the host half copySlots moves - IMU buffer, current time, initialised flag. The destination keeps its own
+    // settings and innovation totals; a refused entry changes nothing. The filter is unchanged (a removal of invalid landmarks it had deferred happens first).
+    int loadFilter(VIOFilter& src, int count, const int* slots, int* status);
+    // The filter becomes the slot (eqf_batch_store_ctx, then the host half); it keeps its own settings. Returns eqf_batch_store_ctx's code; nothing changes
+    // unless that is 0.
+    int storeFilter(int slot, VIOFilter& dst);
     void startFromState(int slot, const double* sensor, const int* ids, const double* p, int N, double time);
     void processIMUData(int slot, const IMUVelocity& imu);
     // processVisionData for `count` slots in one device step; status per entry

@@ -12,6 +12,10 @@ struct eqvio_filter {
     double t_prop = 0, t_pre = 0, t_corr = 0;
 };
 
+namespace eqvio_amd {
+VIOFilter* filterOf(eqvio_filter* f) { return f->filter.get(); }
+} // namespace eqvio_amd
+
 namespace {
 VIOState unpackState(const double* s, const int* ids, const double* p, int N) {
     VIOState xi;

@@ -4,7 +4,8 @@
 // --batch B [--sweep NAME=v0,...] replays the dataset in the B slots of one filter batch (VIOFilterBatch.hpp), slot k with the k-th value, and scores every
 // slot by its innovation statistics (include/eqf_batch.h): a tuning sweep on a dataset without landmark truth. With --warmup F the first F frames run once, in
 // slot 0 under the command line's settings, and slot 0 is then copied into the other slots on the device (eqf_batch_copy_slots): every tuning starts from the
-// same converged filter, and the scores count the frames after the warm-up only.
+// same converged filter, and the scores count the frames after the warm-up only. With --warmupOnFilter the F frames run on one VIOFilter instead (the context
+// path, the fastest way this repository runs a single filter), which is then loaded into all B slots on the device (eqf_batch_load_ctx).
 // --batch B --record DIR writes every slot's trajectory (the four state files of --output) to DIR/run_<k>/, and --batch B --groundtruth FILE scores every slot's
 // trajectory against ground truth: both from ONE estimates call per vision measurement over the live slots (eqf_batch_estimates).
 // --batch B --predictions scores every slot by how far a frame's measured features lie from where the slot predicted them (getFeaturePredictions at the
@@ -31,7 +32,7 @@ static void usage() {
               "                 [--cameraFile sensor.yaml | camchain.yaml]   (intrinsics, distortion and camera offset from the dataset's own file, main_opt.cpp:114-147)\n"
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F]] [--record DIR] [--predictions]]\n"
+              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
@@ -49,12 +50,15 @@ static void usage() {
               "  --warmup F   with --batch B --sweep: the first F vision frames run in slot 0 alone, with the command line's settings; slot 0 is then copied into\n"
               "              slots 1 .. B-1 on the device, the sweep's values go to all B slots, and the scores count the frames after the warm-up only.\n"
               "              With F > 0 a sweep of coordinateChoice (Sigma is in the chart's coordinates) or of an initial variance of the sensor state (used only\n"
-              "              when a filter starts) is refused.");
+              "              when a filter starts) is refused.\n"
+              "  --warmupOnFilter   with --warmup F (F > 0): the F warm-up frames run on ONE single filter (the low-latency context path) with the command line's\n"
+              "              settings instead of in slot 0; the filter is then loaded into all B slots on the device in one call, the sweep's values are applied and\n"
+              "              scoring starts. With --record DIR every slot starts its files at the branch.");
 }
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
 static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime,
-                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions) {
+                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions, bool warmupOnFilter) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -63,6 +67,12 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         return 1;
     }
     VIOFilterBatch filters(core); // every slot as VIOFilter(fs): it initialises itself from its first IMU sample
+    // --warmupOnFilter: the warm-up's frames run here, on the context path, and no slot runs before the branch
+    std::unique_ptr<VIOFilter> warm;
+    if (warmupOnFilter) {
+        loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
+        warm = std::make_unique<VIOFilter>(fs);
+    }
     // --record / --groundtruth: the live slots' estimates after every vision measurement, one call for all of them
     const bool wantEstimates = !recordDir.empty() || groundtruth;
     std::vector<std::unique_ptr<VIOWriter>> writers(B);
@@ -90,14 +100,25 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     int live = warmup > 0 ? 1 : B;
     bool branched = warmup == 0;
     auto branch = [&] {
-        std::vector<int> src(B - 1, 0), dst(B - 1), st(B - 1, 0);
-        for (int k = 1; k < B; ++k)
-            dst[k - 1] = k;
-        if (B > 1)
-            filters.copySlots(B - 1, src.data(), dst.data(), st.data());
-        for (int k = 1; k < B; ++k)
-            if (st[k - 1] != 0)
-                throw std::runtime_error("--warmup: copying slot 0 into slot " + std::to_string(k) + ": " + eqf_error_string(st[k - 1]));
+        if (warm) { // the filter into all B slots, one call
+            std::vector<int> all(B), st(B, 0);
+            for (int k = 0; k < B; ++k)
+                all[k] = k;
+            check_rc(filters.loadFilter(*warm, B, all.data(), st.data()), "--warmupOnFilter: loading the filter into the slots");
+            for (int k = 0; k < B; ++k)
+                if (st[k] != 0)
+                    throw std::runtime_error("--warmupOnFilter: loading the filter into slot " + std::to_string(k) + ": " + eqf_error_string(st[k]));
+            warm.reset();
+        } else {
+            std::vector<int> src(B - 1, 0), dst(B - 1), st(B - 1, 0);
+            for (int k = 1; k < B; ++k)
+                dst[k - 1] = k;
+            if (B > 1)
+                filters.copySlots(B - 1, src.data(), dst.data(), st.data());
+            for (int k = 1; k < B; ++k)
+                if (st[k - 1] != 0)
+                    throw std::runtime_error("--warmup: copying slot 0 into slot " + std::to_string(k) + ": " + eqf_error_string(st[k - 1]));
+        }
         applySweep();
         check_rc(eqf_batch_reset_innovation_totals(filters.core(), -1), "eqf_batch_reset_innovation_totals");
         live = B;
@@ -137,6 +158,13 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
                     }
                 }
             }
+            if (warm) { // a warm-up frame on the single filter: no slot runs, nothing is scored or recorded
+                warm->processVisionData(measData);
+                ++visionDataCounter;
+                if (stopTime > 0 && warm->getTime() > stopTime)
+                    break;
+                continue;
+            }
             const std::vector<const VisionMeasurement*> meas(B, &measData);
             filters.processVisionData(live, slots.data(), meas.data(), status.data()); // one device step for all live slots
             for (int k = 0; k < live; ++k) {
@@ -164,11 +192,13 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
             const IMUVelocity imuData = dataServer.getIMU();
             if (startTime > 0 && imuData.stamp < startTime)
                 continue;
-            for (int k = 0; k < live; ++k)
+            if (warm)
+                warm->processIMUData(imuData);
+            for (int k = 0; k < live && !warm; ++k)
                 filters.processIMUData(k, imuData);
             ++imuDataCounter;
         }
-        if (stopTime > 0 && filters.slot(0).currentTime > stopTime)
+        if (stopTime > 0 && (warm ? warm->getTime() : filters.slot(0).currentTime) > stopTime)
             break;
     }
     const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopStartTime).count();
@@ -177,7 +207,10 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     if (warmup > 0) {
         if (!branched)
             throw std::runtime_error("--warmup " + std::to_string(warmup) + ": the sequence has only " + std::to_string(visionDataCounter) + " vision frames");
-        std::printf("warm-up: %d frames in slot 0, then copied into %d slots; scores over the %d frames after the warm-up\n", warmup, B - 1, scoredFrames);
+        if (warmupOnFilter)
+            std::printf("warm-up: %d frames on a single filter, then loaded into %d slots; scores over the %d frames after the warm-up\n", warmup, B, scoredFrames);
+        else
+            std::printf("warm-up: %d frames in slot 0, then copied into %d slots; scores over the %d frames after the warm-up\n", warmup, B - 1, scoredFrames);
     }
     for (int k = 0; k < B; ++k) {
         const VIOFilterBatch::InnovationTotals t = filters.innovationTotals(k);
@@ -210,7 +243,7 @@ int main(int argc, char** argv) {
     cam->c.width = 752;
     cam->c.height = 480;
     double cameraLag = 0, startTime = -1, stopTime = -1;
-    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false;
+    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false;
     int batch = 0;
     std::string warmupText;
     Sweep sweep;
@@ -267,6 +300,7 @@ int main(int argc, char** argv) {
             else if (a == "--batch") batch = std::atoi(val());
             else if (a == "--record") recordDir = val();
             else if (a == "--predictions") predictions = true;
+            else if (a == "--warmupOnFilter") warmupOnFilter = true;
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
                 haveSweep = true;
@@ -307,6 +341,10 @@ int main(int argc, char** argv) {
                 return 2;
             }
             warmup = (int)f;
+        }
+        if (warmupOnFilter && warmup == 0) { // before any file or device is opened
+            std::fprintf(stderr, "eqvio_opt: --warmupOnFilter needs --warmup F with F > 0 (it says where the warm-up's frames run)\n");
+            return 2;
         }
         if (batch != 0) { // what the filter batch refuses, before any file or device is opened
             std::string why = batch < 1 ? "needs B >= 1"
@@ -368,7 +406,7 @@ int main(int argc, char** argv) {
             std::vector<StampedPose> gt;
             if (!gtName.empty())
                 gt = TrackReplayServer::groundtruth(gtName, format);
-            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter);
         }
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150

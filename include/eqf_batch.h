@@ -265,6 +265,39 @@ int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* en
  * Returns 0 when the launch ran (whatever the per-entry codes), EQF_E_BAD_ARG for a null batch, src, dst or status or count < 0 (no device is looked at),
  * or a HIP error. */
 int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst, int* status);
+
+/* The bridge between a context (eqf_hip.h: one filter at low latency) and the slots, on the device: to fork a running filter into B what-if slots, to warm a
+ * sweep up on the fast path, to put the best of B tunings back into the filter that runs in real time.
+ *
+ * eqf_batch_load_ctx: every listed slot (distinct) comes to hold what the context holds - xi0, X, the landmark ids in state order, per landmark q0, Qq and Qa,
+ * and Sigma (n x n, n = 21 + 3 N): eqf_batch_get_state / _get_sigma of the slot then equal eqf_get_state / eqf_get_sigma of the context, bit for bit, and the
+ * slot is the one eqf_batch_set_state + _set_sigma with those values would have made, bit for bit in every later frame (the landmarks' chart constants are
+ * formed from q0 by the function those calls use). One launch for the whole call, whatever count is, and one synchronisation; nothing of Sigma or the landmark
+ * planes crosses to the host (the 46 sensor doubles and the ids live on the host on both sides and are copied there). The kernel reads the context's current
+ * buffers with their own plane stride and leading dimension and writes each destination's other buffers, which then become current: nothing the slot held
+ * before shows. The context is entered as by eqf_get_state (an update taken from the early doorbell is settled, held landmarks and a pending reshape are
+ * applied, the observer's stream is joined) and is otherwise not changed in any way its API can show.
+ * The destination keeps its own settings, its innovation totals and its eqf_batch_nees_lu_fallbacks count; its last result and last innovation read as on a
+ * slot that never stepped (eqf_batch_copy_slots's rule). Refusals are decided before any device work. Of the whole call - no slot is touched, status is not
+ * written:
+ *   EQF_E_BAD_ARG      null b, src, slots or status, or count < 0 (also on a machine without a GPU); a context on another device than the batch;
+ *   EQF_E_UNSUPPORTED  a context with the Normal chart (its sensor block of Sigma is in other coordinates) or the float Sigma store (EQF_OPT_SIGMA_FP32 = 2);
+ *   EQF_E_CAPACITY     the context holds more landmarks than eqf_batch_max_landmarks(b).
+ * Per entry, status[e] - the other entries are still done, a refused slot is untouched bit for bit:
+ *   0                  done;
+ *   EQF_E_BAD_ARG      bad slot index; a slot an earlier accepted entry of the call names; or a slot whose coordinateChoice is not the context's chart while
+ *                      the context holds landmarks (eqf_batch_set_slot_settings's rule; a context without landmarks loads into either chart).
+ * Returns 0 when it ran (whatever the per-entry codes) or count == 0, one of the codes above, or a HIP error.
+ *
+ * eqf_batch_store_ctx: the context comes to hold what the slot holds, exactly as after eqf_set_state + eqf_set_sigma with the slot's values - the estimate
+ * cache, a staged measurement, held landmarks and the id lookups are dropped, the landmark generation moves on, the capacity grows when the slot holds more
+ * landmarks than the context has room for - with one launch and one synchronisation and neither Sigma nor the planes over the bus (a context with
+ * EQF_OPT_SIGMA_FP32 = 1 rounds Sigma behind it, as eqf_set_sigma does). The slot is unchanged. Refusals, the context untouched:
+ *   EQF_E_BAD_ARG      null b or dst, a bad slot, a context on another device; a slot with landmarks whose coordinateChoice is not the context's chart;
+ *   EQF_E_UNSUPPORTED  a Normal-chart or float-store context.
+ * Returns 0, one of these codes, EQF_E_CAPACITY when the context could not grow, or a HIP error. */
+int eqf_batch_load_ctx(eqf_batch* b, eqf_ctx* src, int count, const int* slots, int* status);
+int eqf_batch_store_ctx(eqf_batch* b, int slot, eqf_ctx* dst);
 /* the hipStream_t the batch launches on, as void* */
 void* eqf_batch_stream(eqf_batch* b);
 int eqf_batch_synchronize(eqf_batch* b);

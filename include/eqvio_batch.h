@@ -117,6 +117,16 @@ int eqvio_batch_is_initialised(const eqvio_batch* b, int slot);
  * warms up once: run the first frames in one slot, copy it into the others, give them their settings. Returns 0, EQF_E_BAD_ARG (null arguments, count < 0)
  * or -1 (eqvio_batch_last_error). */
 int eqvio_batch_copy_slots(eqvio_batch* b, int count, const int* src, const int* dst, int* status);
+/* A whole filter between an eqvio_filter (include/eqvio_filter.h: the context path, one filter at low latency) and slots, without leaving the device: to
+ * fork a live filter into what-if slots, or to hand the best of B tunings to the filter that runs in real time.
+ * eqvio_batch_load_filter: every listed slot (distinct) becomes the filter - the EqF state by eqf_batch_load_ctx (include/eqf_batch.h: one launch for the whole
+ * call, the same refusals and status codes) and what the reference's VIOFilter keeps on the host: the IMU buffer, the current time and the initialised flag
+ * (the host half eqvio_batch_copy_slots moves). The destination keeps its own settings and innovation totals; a refused entry changes nothing, host half
+ * included. The filter is not changed.
+ * eqvio_batch_store_filter: the filter becomes the slot (eqf_batch_store_ctx, then the same host half); it keeps its own settings, the slot is unchanged.
+ * Both return 0, an EQF_E_* code for refused arguments (nothing changed), or -1 (eqvio_batch_last_error). */
+int eqvio_batch_load_filter(eqvio_batch* b, eqvio_filter* src, int count, const int* slots, int* status);
+int eqvio_batch_store_filter(eqvio_batch* b, int slot, eqvio_filter* dst);
 /* The innovation statistics of the slot's last step and their totals over the slot's updated steps (eqf_batch_last_innovation, _innovation_totals,
  * _reset_innovation_totals, include/eqf_batch.h: same meaning, same codes; the numbers are the device batch's, kept nowhere else). A slot that sits a step
  * out (stale stamp, ended sequence) adds nothing. For a score per slot of a replay: reset, eqvio_batch_run_prepared / _run_sim, read the totals. */
