@@ -21,6 +21,7 @@
 #include <signal.h>
 #include <sys/mman.h>
 #include <cerrno>
+#include <climits>
 
 using namespace eqf;
 
@@ -136,7 +137,64 @@ GroupSensor group_mul(const GroupSensor& a, const GroupSensor& b) {
 
 } // namespace
 
-struct eqf_ctx {
+// The members of a context are grouped by what a change of capacity (grow_capacity builds a second context and exchanges the two) does with them:
+// CtxOptions and CtxCounters are carried over whole, by one struct assignment each; CtxBuffers stays with the context that made the allocations; everything
+// else in eqf_ctx is state of the filter (moved through the host) or scratch of the buffers (left behind), bar the short list in grow_capacity.
+// One place each: a new option is a member of CtxOptions with its row in kOptions, a new counter a member of CtxCounters, a new buffer a pointer in eqf_ctx
+// with ONE alloc_device / alloc_pinned call (where it is first needed). None of them is mentioned in eqf_destroy or grow_capacity.
+
+// What eqf_set_option sets. Every id has a row in kOptions (below eqf_destroy), which eqf_get_option and eqf_set_option walk.
+struct CtxOptions {
+    int opt_dense = 0, opt_check = 0, opt_timing = 0, opt_f32 = 0, opt_early = 1, opt_fuse_asm = 1;
+    int opt_door = 1;                        // host doorbell instead of the stream completion signal for the two per-frame waits
+    int opt_spec = 1;                        // speculative frame tail allowed (eqf_stats_then_update)
+    int opt_la_home = 1;                     // EQF_OPT_LA_HOME
+    int opt_lookahead = 1;                   // EQF_OPT_LOOKAHEAD
+    int opt_zb = 1;                          // EQF_OPT_Z_IN_LOOKAHEAD
+    int opt_zb_large = 1;                    // ... also with 17 .. 32 panels (round 6); option value 2 = up to 16 panels only (round 5's behaviour, for A/B runs)
+    int opt_la_split = 1;                    // EQF_OPT_LA_SPLIT_ROWS
+    int opt_prop_tpw = 1;                    // EQF_OPT_TILES_PER_WORKGROUP
+    int opt_gather = 1;                      // EQF_OPT_GATHER_IN_PROPAGATE
+    int opt_early_door = 1;                  // EQF_OPT_EARLY_DOORBELL
+    int opt_quiet_wait = 1;                  // EQF_OPT_QUIET_DOOR_WAIT
+    int opt_la_watch_ahead = 1;              // (debug knob, option 102) LaArgs::watch_ahead
+    int opt_hold = 1;                        // EQF_OPT_HOLD_NEW_LANDMARKS
+    int opt_sel_one = 1;                     // EQF_OPT_SELECT_ONE_WORKGROUP
+    int opt_live_first = 1;                  // EQF_OPT_LIVE_COLUMNS_FIRST
+    int opt_measure_prop = 1;                // EQF_OPT_MEASURE_IN_PROPAGATE
+    int opt_lift_syrk = 1;                   // EQF_OPT_LIFT_WITH_SYRK
+    long long la_timeout_ticks = LA_TIMEOUT_TICKS; // EQF_OPT_LA_TIMEOUT_US: bound of every device-side wait of the look-ahead kernel (100 MHz ticks)
+};
+// What the *_stats getters, eqf_lookahead_home, eqf_nees_lu_fallbacks and eqf_host_wait_stats report, and the back-offs that count frames: they belong to the
+// handle, not to the buffers, and never restart when the capacity grows.
+struct CtxCounters {
+    long la_launches = 0, la_fallbacks = 0;  // eqf_lookahead_stats: look-ahead launches; of those, stalled ones that were redone on the launch chain
+    int la_consecutive_stalls = 0;           // three in a row switch the look-ahead kernel off for this context (the GPU is shared with something long-running)
+    long la_home_launches = 0;
+    long la_home_refused = 0;                // launches that found their blocks elsewhere (the offset is learnt again, the update is redone on the launch chain)
+    long la_book_timeouts = 0;               // updates that took the launch chain because the compute units did not come free within la_book's bound
+    long zb_launches = 0;
+    long early_rings = 0;                    // updates the host took from the early doorbell
+    long live_first_launches = 0;
+    long held_launches = 0;                  // propagation launches that created held landmarks themselves
+    long gather_launches = 0;                // propagation launches that applied a removal record themselves
+    long me_used = 0;
+    int spec_backoff = 0, spec_backoff_len = 0; // frames left without speculation after cancelled tails (doubling, <= 16; <= 256 with the device-side outlier decision), see eqf_stats_then_update
+    long spec_calls = 0, spec_queued = 0, spec_cancelled = 0; // eqf_stats_then_update: calls, tails queued speculatively, tails cancelled on the device
+    long sel_frames = 0, sel_discarded = 0;  // frames that took the device-side outlier decision, landmarks it discarded
+    long nees_lu_fallbacks = 0;              // computeNEES calls answered by the partial-pivot elimination (Sigma not numerically SPD)
+    // host-side wait statistics (eqf_host_wait_stats): doorbell waits and the time spent spinning in them
+    long wait_calls = 0, launch_calls = 0;
+    double wait_seconds = 0.0, launch_seconds = 0.0;
+};
+// Every device and pinned allocation of a context, recorded by alloc_device / alloc_pinned (below HIPCHK) and released by eqf_destroy. Pointer VALUES, so that
+// the lists exchange with their context in std::swap(*c, *t).
+struct CtxBuffers {
+    std::vector<void*> device, pinned;
+};
+
+struct eqf_ctx : CtxOptions, CtxCounters {
+    CtxBuffers own;
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr; // landmark part of the observer steps, concurrent with the Riccati propagation
@@ -172,27 +230,14 @@ struct eqf_ctx {
     int* d_pubf = nullptr;
     int* d_pubfl = nullptr;                  // EQF_OPT_LA_HOME: flags of the hand-offs that stay inside the home XCD's L2
     int la_home = 0;                         // the XCD block 0 of this context's grids runs on (an offset of the stream's hardware queue: learnt from a refused launch)
-    long la_home_refused = 0;                // launches that found their blocks elsewhere (the offset is learnt again, the update is redone on the launch chain)
-    int opt_la_home = 1;                     // EQF_OPT_LA_HOME
-    long la_home_launches = 0;
     bool la_home_force = false;              // the self-test exercises the HOME placement whoever else is on the device
     int reg_slot = -1;                       // this context's slot in the device's registry of contexts (shared memory: device_to_itself)
     unsigned reg_checks = 0;
     char* d_puby = nullptr;
     int la_njcap = 0, la_seq = 0;
     unsigned long long* d_ladbg = nullptr; // EQF_OPT_TRACE: stamps inside the look-ahead kernel (96 x 8)
-    int opt_lookahead = 1;                   // EQF_OPT_LOOKAHEAD
-    int opt_zb = 1;                          // EQF_OPT_Z_IN_LOOKAHEAD
-    int opt_zb_large = 1;                    // ... also with 17 .. 32 panels (round 6); option value 2 = up to 16 panels only (round 5's behaviour, for A/B runs)
-    int opt_la_split = 1;                    // EQF_OPT_LA_SPLIT_ROWS
-    int opt_prop_tpw = 1;                    // EQF_OPT_TILES_PER_WORKGROUP
-    int opt_gather = 1;                      // EQF_OPT_GATHER_IN_PROPAGATE
-    int opt_early_door = 1;                  // EQF_OPT_EARLY_DOORBELL
-    int opt_quiet_wait = 1;                  // EQF_OPT_QUIET_DOOR_WAIT
-    int opt_la_watch_ahead = 1;              // (debug knob, option 102) LaArgs::watch_ahead
     int early_seq_next = 0, early_armed_seq = 0; // the doorbell sequence the next look-ahead launch carries / the one the launch in flight carries
     bool early_allowed = false;              // the call in progress can take the early doorbell (eqf_stats_then_update / eqf_stats_select_update)
-    long early_rings = 0;                    // updates the host took from the early doorbell
     // An update taken from the early doorbell is UNSETTLED until the lift's doorbell has been seen: the sensor lift is applied, the landmark estimates and their
     // invalid flags (the lift kernel's) are not in yet. settle_update() waits for them; every entry point that needs the device or the estimates settles first,
     // eqf_propagate_fast settles behind its launch.
@@ -201,34 +246,23 @@ struct eqf_ctx {
     unsigned settle_gen = 0, settle_epoch = 0, est_epoch = 0; // est_epoch: bumped wherever the cached estimates are dropped (the state moved on)
     std::vector<int> settle_ids;             // the landmark ids at the update
     std::vector<int> invalid_ids;            // ... of which the lift flagged these as invalid (VIO_eqf::removeInvalidLandmarks' test): eqf_remove_invalid_at_update
-    int opt_hold = 1;                        // EQF_OPT_HOLD_NEW_LANDMARKS
-    int opt_sel_one = 1;                     // EQF_OPT_SELECT_ONE_WORKGROUP
-    int opt_live_first = 1;                  // EQF_OPT_LIVE_COLUMNS_FIRST
-    const int* la_live_cols = nullptr;       // ... and what launch_lookahead passes on
-    long live_first_launches = 0;
+    const int* la_live_cols = nullptr;       // EQF_OPT_LIVE_COLUMNS_FIRST: what launch_lookahead passes on
     // eqf_add_landmarks_held: the last n_held landmarks of the state wait for the next eqf_propagate_fast, which passes them through untouched (GatherArgs)
     int n_held = 0;
     double held_var = 0.0;
     bool held_in_memory = false;             // an entry point other than eqf_propagate_fast came in between: they were appended by an ordinary pass (still passed through untouched)
     double* h_held = nullptr;                // pinned: [0] variance, [1 + 3 t ..] point of held landmark t
     bool held_busy = false;                  // a propagation that reads h_held may still be queued (cleared by every host wait)
-    long held_launches = 0;                  // propagation launches that created held landmarks themselves
-    long gather_launches = 0;                // propagation launches that applied a removal record themselves
-    int opt_measure_prop = 1;                // EQF_OPT_MEASURE_IN_PROPAGATE
-    int opt_lift_syrk = 1;                   // EQF_OPT_LIFT_WITH_SYRK
-    // ... its state: what the propagation kernel's observer blocks evaluated the output blocks with (camera and C / C* of the LAST update call stand in for the
+    // EQF_OPT_MEASURE_IN_PROPAGATE's state: what the propagation kernel's observer blocks evaluated the output blocks with (camera and C / C* of the LAST update call stand in for the
     // coming one's; the update call checks), for which staged measurement
     bool pred_valid = false, me_valid = false;
     Cam pred_cam{}, me_cam{};
     int pred_star = 0, me_star = 0, me_M = 0;
     unsigned long me_gen = 0;
-    long me_used = 0;
     bool obs_one_chunk = false;              // the propagation launch in progress carries ALL observer steps of the call (more than kMaxSteps: further k_observer launches follow)
     bool tail_zb = false;                    // the update tail in flight has no Z in memory (built inside the look-ahead kernel): a retry on the chain builds it first
     double tail_var = 0.0;                   // ... and needs the measurement variance again
-    long zb_launches = 0;
     int cu_count = 256;                      // compute units of the device: the look-ahead kernel needs all its workgroups resident at once
-    long la_book_timeouts = 0;               // updates that took the launch chain because the compute units did not come free within la_book's bound
     std::vector<char> rm_drop;               // eqf_remove_landmarks' scratch
     std::vector<int> rm_ids, rm_map;
     std::vector<double> rm_est;
@@ -236,9 +270,6 @@ struct eqf_ctx {
     bool counted_alive = false;
     int la_cus_held = 0;                     // compute units this context has booked for a look-ahead launch in flight (la_book / la_release)
     int la_selftest = 0;                     // look-ahead self-test at creation: 0 not run (never eligible at this capacity), 1 passed, -1 failed (launch chain only)
-    long long la_timeout_ticks = LA_TIMEOUT_TICKS; // EQF_OPT_LA_TIMEOUT_US: bound of every device-side wait of the look-ahead kernel (100 MHz ticks)
-    long la_launches = 0, la_fallbacks = 0;  // eqf_lookahead_stats: look-ahead launches; of those, stalled ones that were redone on the launch chain
-    int la_consecutive_stalls = 0;           // three in a row switch the look-ahead kernel off for this context (the GPU is shared with something long-running)
     int tail_M = 0;                          // measurement count of the update tail in flight (finish_update's retry)
     bool tail_la = false;                    // ... and whether its factorisation was the look-ahead kernel
     int* d_perm = nullptr;                   // 2 x (ncap + 2) row permutations of the NEES elimination fallback
@@ -256,9 +287,6 @@ struct eqf_ctx {
     char* h_rs_ring = nullptr;     // kRing pinned packets: map[Ncap] ints | newp[3 Ncap] | var[Ncap] doubles
     char* d_rs = nullptr;
     size_t rs_bytes = 0;
-    int spec_backoff = 0, spec_backoff_len = 0; // frames left without speculation after cancelled tails (doubling, <= 16; <= 256 with the device-side outlier decision), see eqf_stats_then_update
-    long spec_calls = 0, spec_queued = 0, spec_cancelled = 0; // eqf_stats_then_update: calls, tails queued speculatively, tails cancelled on the device
-    long nees_lu_fallbacks = 0;              // computeNEES calls answered by the partial-pivot elimination (Sigma not numerically SPD)
     int ldzn = 0;
     double *d_Z = nullptr, *d_W = nullptr, *d_Linv = nullptr, *d_gamma = nullptr, *d_gpart = nullptr, *d_est = nullptr, *d_stats = nullptr, *d_scratch = nullptr, *d_F = nullptr, *d_tmp = nullptr;
     int* d_flags = nullptr;
@@ -295,28 +323,20 @@ struct eqf_ctx {
     std::vector<std::pair<int, int>> lookup; // sorted (id, index), valid for lookup_gen == lm_gen
     std::vector<int> renum_scratch;
     unsigned lookup_gen = ~0u;
-    // host-side wait statistics (eqf_host_wait_stats): doorbell waits and the time spent spinning in them
     // EQF_OPT_TRACE: device-side frame timeline (ring of TR_FRAMES frames x TR_SLOTS stamps, 100 MHz device wall clock)
     trace_t* d_trace = nullptr;
     unsigned trace_frame = 0;
     std::vector<long long> h_trace; // host steady_clock stamps (ns), TR_FRAMES x TR_HOST
-    long wait_calls = 0, launch_calls = 0;
-    double wait_seconds = 0.0, launch_seconds = 0.0;
     double* h_res = nullptr; // pinned result packet: stats[3 Ncap] | est[4 Ncap] | gamma[32]
     double* h_ocov = nullptr; // eqf_output_cov_all: pinned, 4 Ncap (allocated on first use)
     int* h_resflags = nullptr;
     int* h_sel = nullptr; // pinned: k_select_outliers' verdict, [0, N) discarded flags, [Ncap] candidates, [Ncap + 1] discarded
-    long sel_frames = 0, sel_discarded = 0; // frames that took the device-side outlier decision, landmarks it discarded
     static constexpr int kMaxSteps = kObsChunk;
     CommonK ck; // kernel-argument form of the last sensor-level packet
-    // options
-    int opt_dense = 0, opt_check = 0, opt_timing = 0, opt_f32 = 0, opt_early = 1, opt_fuse_asm = 1;
     bool sig32 = false; // Sigma stored as float (EQF_OPT_SIGMA_FP32 = 2)
-    int opt_door = 1;   // host doorbell instead of the stream completion signal for the two per-frame waits
     int* d_door = nullptr; // device counters (one per doorbell)
     int* h_door = nullptr; // pinned sequence numbers written by the last workgroup
     unsigned door_seq = 0; // wraps harmlessly: only equality is tested
-    int opt_spec = 1;      // speculative frame tail allowed (eqf_stats_then_update)
     int* d_spec = nullptr; // device word the statistics kernel sets to the sequence number to cancel a queued tail
     std::vector<double> last_gamma;
     int n_at_update = 0;
@@ -348,8 +368,41 @@ struct eqf_ctx {
             return (int)_e;                                                                            \
         }                                                                                              \
     } while (0)
+// the same for a function of this file: a non-zero status is the caller's
+#define EQFCHK(expr)          \
+    do {                      \
+        const int _r = (expr); \
+        if (_r)               \
+            return _r;        \
+    } while (0)
 
 namespace {
+
+// The only places that allocate for a context: count elements of T into the member p, recorded in c->own (released by eqf_destroy); zero = filled with 0 on the
+// context's stream (pinned memory: at once).
+template <class T>
+int alloc_device(eqf_ctx* c, T*& p, size_t count, bool zero = false) {
+    HIPCHK(hipMalloc(&p, sizeof(T) * count));
+    c->own.device.push_back(p);
+    if (zero)
+        HIPCHK(hipMemsetAsync(p, 0, sizeof(T) * count, c->stream));
+    return 0;
+}
+template <class T>
+int alloc_pinned(eqf_ctx* c, T*& p, size_t count, bool zero = false) {
+    HIPCHK(hipHostMalloc(&p, sizeof(T) * count));
+    c->own.pinned.push_back(p);
+    if (zero)
+        std::memset(p, 0, sizeof(T) * count);
+    return 0;
+}
+// one device buffer given back early (EQF_OPT_TRACE = 0): the member is null again
+template <class T>
+void free_device(eqf_ctx* c, T*& p) {
+    c->own.device.erase(std::remove(c->own.device.begin(), c->own.device.end(), (void*)p), c->own.device.end());
+    hipFree(p);
+    p = nullptr;
+}
 
 hipEvent_t get_event(eqf_ctx* c) {
     if (c->evused == c->evpool.size()) {
@@ -423,7 +476,6 @@ int spin_stream(hipStream_t st) {
 // the device's compute units: a context whose launch does not fit waits on the host until an earlier one has rung its doorbell. One filter never waits.
 namespace {
 std::atomic<int> ctx_alive[64]; // contexts of this process per device
-thread_local bool replaces_own_queue = false; // set by grow_capacity around eqf_create
 std::mutex la_gate_mutex;
 std::condition_variable la_gate_cv;
 int la_cus_booked[64] = {0}; // per device
@@ -715,14 +767,14 @@ int keep_last_gamma(eqf_ctx* c) {
         return 0;
     const int ng = c->n_at_update;
     HIPCHK(hipMemcpyAsync(c->h_buf, c->d_gamma, sizeof(double) * ng, hipMemcpyDeviceToHost, c->stream));
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     c->last_gamma.assign(c->h_buf, c->h_buf + ng);
     c->gamma_stale = false;
     return 0;
 }
 int read_flags(eqf_ctx* c) {
     HIPCHK(hipMemcpyAsync(c->h_flags, c->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     return 0;
 }
 // id -> state index. The filter looks up every measured id every frame: a sorted (id, index) table, rebuilt only when the
@@ -800,7 +852,7 @@ const char* eqf_error_string(int code) {
 }
 const char* eqf_kernel_name(int which) { return (which >= 0 && which < KN_COUNT) ? kNames[which] : "?"; }
 
-static int create_buffers(eqf_ctx* c, int max_landmarks);
+static int create_buffers(eqf_ctx* c, int max_landmarks, bool own_queue);
 static int grow_capacity(eqf_ctx* c, int new_cap);
 static int flush_reshape(eqf_ctx* c);
 static int round_sigma(eqf_ctx* c, const int* spec = nullptr, int spec_seq = 0);
@@ -819,7 +871,24 @@ static int enter(eqf_ctx* c, bool settle = true) {
     return flush_reshape(c);
 }
 static int lookahead_selftest(eqf_ctx* c);
-int eqf_create(eqf_ctx** out, int device, int max_landmarks, int coordinate_choice) {
+// EQF_OPTIONS="id=value,id=value": options applied to every new context (A/B runs of unchanged callers; a bad entry fails the creation)
+static int apply_env_options(eqf_ctx* c) {
+    const char* env = std::getenv("EQF_OPTIONS");
+    for (const char* q = env ? env : ""; *q;) {
+        char* end = nullptr;
+        const long id = std::strtol(q, &end, 10);
+        if (end == q || *end != '=')
+            return EQF_E_BAD_ARG;
+        q = end + 1;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || eqf_set_option(c, (int)id, (int)v) != 0 || (*end && *end != ','))
+            return EQF_E_BAD_ARG;
+        q = (*end == ',') ? end + 1 : end;
+    }
+    return 0;
+}
+// own_queue: grow_capacity builds the replacement of a context that HAS a hardware queue of its own (create_buffers) while that context is still counted - it keeps one
+static int create_ctx(eqf_ctx** out, int device, int max_landmarks, int coordinate_choice, bool own_queue) {
     if (!out || max_landmarks < 1 || (coordinate_choice != EQVIO_COORD_EUCLIDEAN && coordinate_choice != EQVIO_COORD_INVDEPTH && coordinate_choice != EQVIO_COORD_NORMAL))
         return EQF_E_BAD_ARG;
     int ndev = 0;
@@ -838,44 +907,20 @@ int eqf_create(eqf_ctx** out, int device, int max_landmarks, int coordinate_choi
     c->chart = coordinate_choice;
     c->cu_count = prop.multiProcessorCount;
     registry_enter(c);
-    const int rc = create_buffers(c, max_landmarks);
-    if (rc) { // a failed allocation half way (e.g. the pinned Sigma staging at a large capacity): release what exists
+    // a failed allocation half way (e.g. the pinned Sigma staging at a large capacity), a bad EQF_OPTIONS entry, a failed launch of the self-test: release what exists
+    int rc = create_buffers(c, max_landmarks, own_queue);
+    if (!rc)
+        rc = apply_env_options(c);
+    if (!rc) // the persistent look-ahead kernel against the launch chain on a fixed problem, before the context is used (see lookahead_selftest)
+        rc = lookahead_selftest(c);
+    if (rc) {
         eqf_destroy(c);
         return rc;
-    }
-    // EQF_OPTIONS="id=value,id=value": options applied to every new context (A/B runs of unchanged callers; a bad entry fails the creation)
-    if (const char* env = std::getenv("EQF_OPTIONS")) {
-        for (const char* q = env; *q;) {
-            char* end = nullptr;
-            const long id = std::strtol(q, &end, 10);
-            if (end == q || *end != '=') {
-                eqf_destroy(c);
-                return EQF_E_BAD_ARG;
-            }
-            q = end + 1;
-            const long v = std::strtol(q, &end, 10);
-            if (end == q || eqf_set_option(c, (int)id, (int)v) != 0) {
-                eqf_destroy(c);
-                return EQF_E_BAD_ARG;
-            }
-            q = (*end == ',') ? end + 1 : end;
-            if (*end && *end != ',') {
-                eqf_destroy(c);
-                return EQF_E_BAD_ARG;
-            }
-        }
-    }
-    {   // the persistent look-ahead kernel against the launch chain on a fixed problem, before the context is used (see lookahead_selftest)
-        const int st = lookahead_selftest(c);
-        if (st) {
-            eqf_destroy(c);
-            return st;
-        }
     }
     *out = c;
     return EQF_OK;
 }
-// every allocation of a context; on failure the caller destroys the partially built context (eqf_destroy accepts null members)
+int eqf_create(eqf_ctx** out, int device, int max_landmarks, int coordinate_choice) { return create_ctx(out, device, max_landmarks, coordinate_choice, false); }
 // Block -> lower tile of Sigma for k_syrk_sub with nt tiles per side, XCD aware: the tiles are sorted by (super-block of g x g tiles, column, row) with
 // g = sqrt(tiles / 8), the sorted list is cut into 8 equal runs, and run x is dealt to the blocks b = x, x + 8, x + 16 ... (block b runs on XCD b % 8). An XCD
 // then works through about one compact g x g square, column by column: ~2 g row panels of W in its L2 instead of all nt.
@@ -904,7 +949,8 @@ static void build_syrk_order(int nt, int* out) {
         start += len;
     }
 }
-static int create_buffers(eqf_ctx* c, int max_landmarks) {
+// every allocation of a context but the lazy ones; on failure the caller destroys the partially built context (eqf_destroy releases what c->own has recorded)
+static int create_buffers(eqf_ctx* c, int max_landmarks, bool own_queue) {
     c->Ncap = roundup(max_landmarks, 16);
     c->ncap = 21 + 3 * c->Ncap;
     c->ld = pick_ld(c->ncap);
@@ -919,8 +965,8 @@ static int create_buffers(eqf_ctx* c, int max_landmarks) {
     c->own_queue = false;
     const int before = ctx_alive[c->device & 63].fetch_add(1);
     const char* own_env = std::getenv("EQF_OWN_HW_QUEUES");
-    // (replaces_own_queue: grow_capacity builds the replacement of a context that HAS a queue of its own while that context is still counted - it keeps one)
-    if ((own_env && before < atoi(own_env)) || replaces_own_queue) {
+    // (own_queue: the replacement of a context that has a queue of its own, see create_ctx - ADVICE r5)
+    if ((own_env && before < atoi(own_env)) || own_queue) {
         std::vector<uint32_t> mask((size_t)(c->cu_count + 31) / 32, 0u);
         for (int i = 0; i < c->cu_count; ++i)
             mask[i >> 5] |= 1u << (i & 31);
@@ -939,42 +985,35 @@ static int create_buffers(eqf_ctx* c, int max_landmarks) {
     HIPCHK(hipEventCreateWithFlags(&c->ev_assembled, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_observer, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
-    const size_t sig_bytes = sizeof(double) * (size_t)c->ld * c->ncap;
+    const size_t Ncap = (size_t)c->Ncap;
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipMalloc(&c->d_sigma[b], sig_bytes));
-        HIPCHK(hipMemsetAsync(c->d_sigma[b], 0, sig_bytes, c->stream));
-        HIPCHK(hipMalloc(&c->d_st[b], sizeof(double) * (CC_OFF + CC_PLANES) * (size_t)c->Ncap));
-        HIPCHK(hipMemsetAsync(c->d_st[b], 0, sizeof(double) * (CC_OFF + CC_PLANES) * (size_t)c->Ncap, c->stream));
-        HIPCHK(hipMalloc(&c->d_lm[b], sizeof(double) * 5 * (size_t)c->Ncap));
-        HIPCHK(hipMemsetAsync(c->d_lm[b], 0, sizeof(double) * 5 * (size_t)c->Ncap, c->stream));
+        EQFCHK(alloc_device(c, c->d_sigma[b], (size_t)c->ld * c->ncap, true));
+        EQFCHK(alloc_device(c, c->d_st[b], (CC_OFF + CC_PLANES) * Ncap, true));
+        EQFCHK(alloc_device(c, c->d_lm[b], 5 * Ncap, true));
     }
-    HIPCHK(hipMalloc(&c->d_Al, sizeof(double) * 45 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_Bl, sizeof(double) * 9 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_common, sizeof(Common)));
-    HIPCHK(hipMalloc(&c->d_steps, sizeof(ObsStep) * eqf_ctx::kMaxSteps));
-    HIPCHK(hipMalloc(&c->d_C, sizeof(double) * 6 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_ytil, sizeof(double) * c->mcap));
-    HIPCHK(hipMalloc(&c->d_y, sizeof(double) * c->mcap));
-    HIPCHK(hipMalloc(&c->d_lmidx, sizeof(int) * c->Ncap));
-    HIPCHK(hipMalloc(&c->d_measof, sizeof(int) * c->Ncap));
-    HIPCHK(hipMalloc(&c->d_Z, sizeof(double) * (size_t)c->ldz * c->mcap));
-    HIPCHK(hipMalloc(&c->d_W, sizeof(double) * (size_t)c->ldz * c->mcap));
-    HIPCHK(hipMalloc(&c->d_Linv, sizeof(double) * 2048));
-    HIPCHK(hipMalloc(&c->d_gamma, sizeof(double) * (c->ncap + 8)));
-    HIPCHK(hipMalloc(&c->d_gpart, sizeof(double) * (GAMMA_G + 1) * (size_t)c->ld));
+    EQFCHK(alloc_device(c, c->d_Al, 45 * Ncap));
+    EQFCHK(alloc_device(c, c->d_Bl, 9 * Ncap));
+    EQFCHK(alloc_device(c, c->d_common, 1));
+    EQFCHK(alloc_device(c, c->d_steps, eqf_ctx::kMaxSteps));
+    EQFCHK(alloc_device(c, c->d_C, 6 * Ncap));
+    EQFCHK(alloc_device(c, c->d_ytil, c->mcap));
+    EQFCHK(alloc_device(c, c->d_y, c->mcap));
+    EQFCHK(alloc_device(c, c->d_lmidx, Ncap));
+    EQFCHK(alloc_device(c, c->d_measof, Ncap));
+    EQFCHK(alloc_device(c, c->d_Z, (size_t)c->ldz * c->mcap));
+    EQFCHK(alloc_device(c, c->d_W, (size_t)c->ldz * c->mcap));
+    EQFCHK(alloc_device(c, c->d_Linv, 2048));
+    EQFCHK(alloc_device(c, c->d_gamma, c->ncap + 8));
+    EQFCHK(alloc_device(c, c->d_gpart, (GAMMA_G + 1) * (size_t)c->ld));
     c->la_njcap = std::min(32, blocks(c->mcap, 32));
-    HIPCHK(hipMalloc(&c->d_pub, sizeof(double) * LA_TILE * la_pub_tiles(c->la_njcap)));
-    HIPCHK(hipMalloc(&c->d_pubf, sizeof(int) * la_pub_flags(c->la_njcap)));
-    HIPCHK(hipMalloc(&c->d_puby, 512 * (size_t)c->la_njcap));
-    HIPCHK(hipMemsetAsync(c->d_pubf, 0, sizeof(int) * la_pub_flags(c->la_njcap), c->stream)); // sequence 0 is never used by a launch
-    HIPCHK(hipMalloc(&c->d_pubfl, sizeof(int) * la_pub_flags(c->la_njcap)));
-    HIPCHK(hipMemsetAsync(c->d_pubfl, 0, sizeof(int) * la_pub_flags(c->la_njcap), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_puby, 0, 512 * (size_t)c->la_njcap, c->stream));
-    HIPCHK(hipMalloc(&c->d_est, sizeof(double) * 4 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_stats, sizeof(double) * 3 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_scratch, sizeof(double) * 8 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_flags, sizeof(int) * 8)); // [0] pivot not positive, [1] non-finite, [3] look-ahead stalled (sequence valued), [4] HOME placement refused (sequence valued)
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, sizeof(int) * 8, c->stream));
+    EQFCHK(alloc_device(c, c->d_pub, (size_t)LA_TILE * la_pub_tiles(c->la_njcap)));
+    EQFCHK(alloc_device(c, c->d_pubf, la_pub_flags(c->la_njcap), true)); // sequence 0 is never used by a launch
+    EQFCHK(alloc_device(c, c->d_pubfl, la_pub_flags(c->la_njcap), true));
+    EQFCHK(alloc_device(c, c->d_puby, 512 * (size_t)c->la_njcap, true));
+    EQFCHK(alloc_device(c, c->d_est, 4 * Ncap));
+    EQFCHK(alloc_device(c, c->d_stats, 3 * Ncap));
+    EQFCHK(alloc_device(c, c->d_scratch, 8 * Ncap));
+    EQFCHK(alloc_device(c, c->d_flags, 8, true)); // [0] pivot not positive, [1] non-finite, [3] look-ahead stalled (sequence valued), [4] HOME placement refused (sequence valued)
     {
         const int ntcap = blocks(c->ncap, 32);
         c->syrk_off.assign(ntcap + 2, 0);
@@ -983,33 +1022,30 @@ static int create_buffers(eqf_ctx* c, int max_landmarks) {
         std::vector<int> all(c->syrk_off[ntcap + 1]);
         for (int nt = 1; nt <= ntcap; ++nt)
             build_syrk_order(nt, all.data() + c->syrk_off[nt]);
-        HIPCHK(hipMalloc(&c->d_syrk_order, sizeof(int) * all.size()));
+        EQFCHK(alloc_device(c, c->d_syrk_order, all.size()));
         HIPCHK(hipMemcpy(c->d_syrk_order, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipHostMalloc(&c->h_common, sizeof(Common)));
-    HIPCHK(hipHostMalloc(&c->h_steps, sizeof(ObsStep) * eqf_ctx::kMaxSteps));
+    EQFCHK(alloc_pinned(c, c->h_common, 1));
+    EQFCHK(alloc_pinned(c, c->h_steps, eqf_ctx::kMaxSteps));
     c->hbuf_doubles = (size_t)c->ld * c->ncap; // large enough for a full Sigma transfer
-    HIPCHK(hipHostMalloc(&c->h_buf, sizeof(double) * c->hbuf_doubles));
-    HIPCHK(hipHostMalloc(&c->h_ibuf, sizeof(int) * 4 * (size_t)c->Ncap));
-    c->rs_bytes = (sizeof(int) + 4 * sizeof(double)) * (size_t)c->Ncap + 64;
-    HIPCHK(hipHostMalloc(&c->h_rs_ring, eqf_ctx::kRing * c->rs_bytes));
-    HIPCHK(hipMalloc(&c->d_rs, c->rs_bytes));
-    HIPCHK(hipHostMalloc(&c->h_flags, sizeof(int) * 4));
-    HIPCHK(hipHostMalloc(&c->h_lmidx, sizeof(int) * 2 * (size_t)c->Ncap));
-    HIPCHK(hipHostMalloc(&c->h_y, sizeof(double) * 2 * (size_t)c->Ncap));
-    HIPCHK(hipHostMalloc(&c->h_ylm, sizeof(double) * 3 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_meas, sizeof(double) * 5 * (size_t)c->Ncap));
-    HIPCHK(hipMalloc(&c->d_meas_idx, sizeof(int) * (size_t)c->Ncap));
-    HIPCHK(hipHostMalloc(&c->h_res, sizeof(double) * (7 * (size_t)c->Ncap + 32)));
-    HIPCHK(hipHostMalloc(&c->h_resflags, sizeof(int) * 4));
-    HIPCHK(hipHostMalloc(&c->h_sel, sizeof(int) * ((size_t)c->Ncap + 2)));
-    HIPCHK(hipHostMalloc(&c->h_held, sizeof(double) * (3 * (size_t)c->Ncap + 1)));
-    HIPCHK(hipHostMalloc(&c->h_door, sizeof(int) * 4));
-    std::memset(c->h_door, 0, sizeof(int) * 4);
-    HIPCHK(hipMalloc(&c->d_door, sizeof(int) * 4));
-    HIPCHK(hipMemset(c->d_door, 0, sizeof(int) * 4));
-    HIPCHK(hipMalloc(&c->d_spec, sizeof(int) * 4));
-    HIPCHK(hipMemset(c->d_spec, 0, sizeof(int) * 4));
+    EQFCHK(alloc_pinned(c, c->h_buf, c->hbuf_doubles));
+    EQFCHK(alloc_pinned(c, c->h_ibuf, 4 * Ncap));
+    c->rs_bytes = (sizeof(int) + 4 * sizeof(double)) * Ncap + 64;
+    EQFCHK(alloc_pinned(c, c->h_rs_ring, eqf_ctx::kRing * c->rs_bytes));
+    EQFCHK(alloc_device(c, c->d_rs, c->rs_bytes));
+    EQFCHK(alloc_pinned(c, c->h_flags, 4));
+    EQFCHK(alloc_pinned(c, c->h_lmidx, 2 * Ncap));
+    EQFCHK(alloc_pinned(c, c->h_y, 2 * Ncap));
+    EQFCHK(alloc_pinned(c, c->h_ylm, 3 * Ncap));
+    EQFCHK(alloc_device(c, c->d_meas, 5 * Ncap));
+    EQFCHK(alloc_device(c, c->d_meas_idx, Ncap));
+    EQFCHK(alloc_pinned(c, c->h_res, 7 * Ncap + 32));
+    EQFCHK(alloc_pinned(c, c->h_resflags, 4));
+    EQFCHK(alloc_pinned(c, c->h_sel, Ncap + 2));
+    EQFCHK(alloc_pinned(c, c->h_held, 3 * Ncap + 1));
+    EQFCHK(alloc_pinned(c, c->h_door, 4, true));
+    EQFCHK(alloc_device(c, c->d_door, 4, true));
+    EQFCHK(alloc_device(c, c->d_spec, 4, true));
     // identity state
     const double s0[23] = {0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0};
     c->xi0 = unpack_sensor(s0);
@@ -1036,77 +1072,10 @@ void eqf_destroy(eqf_ctx* c) {
         hipStreamSynchronize(c->stream);
     if (c->stream2)
         hipStreamSynchronize(c->stream2);
-    for (int b = 0; b < 2; ++b) {
-        hipFree(c->d_sigma[b]);
-        hipFree(c->d_lm[b]);
-        hipFree(c->d_st[b]);
-    }
-    hipFree(c->d_Al);
-    hipFree(c->d_Bl);
-    hipFree(c->d_common);
-    hipFree(c->d_steps);
-    hipFree(c->d_C);
-    hipFree(c->d_ytil);
-    hipFree(c->d_y);
-    hipFree(c->d_lmidx);
-    hipFree(c->d_measof);
-    hipFree(c->d_Z);
-    hipFree(c->d_W);
-    hipFree(c->d_Linv);
-    hipFree(c->d_gamma);
-    hipFree(c->d_gpart);
-    hipFree(c->d_pub);
-    hipFree(c->d_pubf);
-    hipFree(c->d_pubfl);
-    hipFree(c->d_puby);
-    if (c->d_ladbg)
-        hipFree(c->d_ladbg);
-    if (c->d_trace)
-        hipFree(c->d_trace);
-    hipFree(c->d_est);
-    hipFree(c->d_stats);
-    hipFree(c->d_scratch);
-    hipFree(c->d_flags);
-    hipFree(c->d_syrk_order);
-    if (c->d_Ebuf) {
-        hipFree(c->d_Ebuf);
-        hipFree(c->d_Yl);
-        hipFree(c->d_Fl);
-        hipFree(c->d_PhiB);
-        hipFree(c->d_expinfo);
-    }
-    if (c->d_Zn)
-        hipFree(c->d_Zn);
-    if (c->d_Wn)
-        hipFree(c->d_Wn);
-    if (c->d_perm)
-        hipFree(c->d_perm);
-    if (c->d_F)
-        hipFree(c->d_F);
-    if (c->d_tmp)
-        hipFree(c->d_tmp);
-    hipHostFree(c->h_common);
-    hipHostFree(c->h_steps);
-    hipHostFree(c->h_buf);
-    hipHostFree(c->h_ibuf);
-    hipHostFree(c->h_rs_ring);
-    hipFree(c->d_rs);
-    hipHostFree(c->h_flags);
-    hipHostFree(c->h_lmidx);
-    hipHostFree(c->h_y);
-    hipHostFree(c->h_ylm);
-    hipFree(c->d_meas);
-    hipFree(c->d_meas_idx);
-    hipHostFree(c->h_res);
-    if (c->h_ocov)
-        hipHostFree(c->h_ocov);
-    c->h_ocov = nullptr;
-    hipHostFree(c->h_resflags);
-    hipHostFree(c->h_sel);
-    hipHostFree(c->h_held);
-    hipHostFree(c->h_door);
-    hipFree(c->d_door);
-    hipFree(c->d_spec);
+    for (void* p : c->own.device)
+        hipFree(p);
+    for (void* p : c->own.pinned)
+        hipHostFree(p);
     if (c->ev_assembled)
         hipEventDestroy(c->ev_assembled);
     if (c->ev_observer)
@@ -1160,151 +1129,121 @@ static int round_sigma(eqf_ctx* c, const int* spec, int spec_seq) {
     return 0;
 }
 
+// One row per option: the id, its member of CtxOptions, and how eqf_set_option normalises a value before storing it. eqf_get_option, eqf_set_option and (through the
+// type of `member`: the whole of CtxOptions is assigned) grow_capacity follow this table. A null member: the value is not one plain int, both functions have a case for it.
+enum OptKind { OPT_PLAIN, OPT_BOOL /* value ? 1 : 0 */, OPT_RANGE /* lo <= value <= hi, else EQF_E_BAD_ARG */ };
+struct OptRow {
+    int id;
+    int CtxOptions::*member;
+    OptKind kind;
+    int lo, hi;
+};
+static const OptRow kOptions[] = {
+    {EQF_OPT_RICCATI_DENSE, &CtxOptions::opt_dense, OPT_PLAIN, 0, 0},
+    {EQF_OPT_CHECK_FINITE, &CtxOptions::opt_check, OPT_PLAIN, 0, 0},
+    {EQF_OPT_SIGMA_FP32, &CtxOptions::opt_f32, OPT_RANGE, 0, 3},
+    {EQF_OPT_SPECULATIVE, &CtxOptions::opt_spec, OPT_PLAIN, 0, 0},
+    {EQF_OPT_DOORBELL, &CtxOptions::opt_door, OPT_PLAIN, 0, 0},
+    {EQF_OPT_EARLY_LIFT, &CtxOptions::opt_early, OPT_PLAIN, 0, 0},
+    {EQF_OPT_FUSED_ASSEMBLY, &CtxOptions::opt_fuse_asm, OPT_PLAIN, 0, 0},
+    {EQF_OPT_LOOKAHEAD, &CtxOptions::opt_lookahead, OPT_PLAIN, 0, 0},
+    {EQF_OPT_LA_TIMEOUT_US, nullptr, OPT_RANGE, 0, INT_MAX},
+    {EQF_OPT_Z_IN_LOOKAHEAD, nullptr, OPT_PLAIN, 0, 0},
+    {EQF_OPT_LA_SPLIT_ROWS, &CtxOptions::opt_la_split, OPT_BOOL, 0, 0},
+    {EQF_OPT_LA_HOME, &CtxOptions::opt_la_home, OPT_PLAIN, 0, 0},
+    {EQF_OPT_TILES_PER_WORKGROUP, &CtxOptions::opt_prop_tpw, OPT_RANGE, 0, 8},
+    {EQF_OPT_GATHER_IN_PROPAGATE, &CtxOptions::opt_gather, OPT_BOOL, 0, 0},
+    {EQF_OPT_HOLD_NEW_LANDMARKS, &CtxOptions::opt_hold, OPT_BOOL, 0, 0},
+    {EQF_OPT_SELECT_ONE_WORKGROUP, &CtxOptions::opt_sel_one, OPT_BOOL, 0, 0},
+    {EQF_OPT_LIVE_COLUMNS_FIRST, &CtxOptions::opt_live_first, OPT_BOOL, 0, 0},
+    {EQF_OPT_EARLY_DOORBELL, &CtxOptions::opt_early_door, OPT_BOOL, 0, 0},
+    {EQF_OPT_QUIET_DOOR_WAIT, &CtxOptions::opt_quiet_wait, OPT_BOOL, 0, 0},
+    {EQF_OPT_MEASURE_IN_PROPAGATE, &CtxOptions::opt_measure_prop, OPT_BOOL, 0, 0},
+    {EQF_OPT_LIFT_WITH_SYRK, &CtxOptions::opt_lift_syrk, OPT_BOOL, 0, 0},
+    {EQF_OPT_TRACE, nullptr, OPT_PLAIN, 0, 0},
+    {100, &CtxOptions::opt_timing, OPT_PLAIN, 0, 0},
+    {102, &CtxOptions::opt_la_watch_ahead, OPT_BOOL, 0, 0}, // (debug knob, not in the header: same-process A/B of LaArgs::watch_ahead)
+};
+static const OptRow* option_row(int option) {
+    for (const OptRow& r : kOptions)
+        if (r.id == option)
+            return &r;
+    return nullptr;
+}
+
 int eqf_get_option(const eqf_ctx* c, int option, int* value) {
-    if (!c || !value)
+    const OptRow* row = c && value ? option_row(option) : nullptr;
+    if (!row)
         return EQF_E_BAD_ARG;
-    switch (option) {
-    case EQF_OPT_RICCATI_DENSE: *value = c->opt_dense; return 0;
-    case EQF_OPT_CHECK_FINITE: *value = c->opt_check; return 0;
-    case EQF_OPT_SPECULATIVE: *value = c->opt_spec; return 0;
-    case EQF_OPT_DOORBELL: *value = c->opt_door; return 0;
-    case EQF_OPT_EARLY_LIFT: *value = c->opt_early; return 0;
-    case EQF_OPT_FUSED_ASSEMBLY: *value = c->opt_fuse_asm; return 0;
-    case EQF_OPT_Z_IN_LOOKAHEAD: *value = c->opt_zb ? (c->opt_zb_large ? 1 : 2) : 0; return 0;
-    case EQF_OPT_LA_SPLIT_ROWS: *value = c->opt_la_split; return 0;
-    case EQF_OPT_TILES_PER_WORKGROUP: *value = c->opt_prop_tpw; return 0;
-    case EQF_OPT_GATHER_IN_PROPAGATE: *value = c->opt_gather; return 0;
-    case EQF_OPT_HOLD_NEW_LANDMARKS: *value = c->opt_hold; return 0;
-    case EQF_OPT_EARLY_DOORBELL: *value = c->opt_early_door; return 0;
-    case EQF_OPT_QUIET_DOOR_WAIT: *value = c->opt_quiet_wait; return 0;
-    case EQF_OPT_SELECT_ONE_WORKGROUP: *value = c->opt_sel_one; return 0;
-    case EQF_OPT_LIVE_COLUMNS_FIRST: *value = c->opt_live_first; return 0;
-    case EQF_OPT_LA_HOME: *value = c->opt_la_home; return 0;
-    case EQF_OPT_MEASURE_IN_PROPAGATE: *value = c->opt_measure_prop; return 0;
-    case EQF_OPT_LIFT_WITH_SYRK: *value = c->opt_lift_syrk; return 0;
-    case EQF_OPT_LOOKAHEAD: *value = c->opt_lookahead; return 0;
-    case EQF_OPT_LA_TIMEOUT_US: *value = (int)(c->la_timeout_ticks / 100); return 0;
-    case EQF_OPT_TRACE: *value = c->d_trace ? 1 : 0; return 0;
-    case EQF_OPT_SIGMA_FP32: *value = c->opt_f32; return 0;
-    case 100: *value = c->opt_timing; return 0;
-    case 102: *value = c->opt_la_watch_ahead; return 0;
-    default: return EQF_E_BAD_ARG;
-    }
+    if (row->member)
+        *value = c->*(row->member);
+    else if (option == EQF_OPT_Z_IN_LOOKAHEAD)
+        *value = c->opt_zb ? (c->opt_zb_large ? 1 : 2) : 0;
+    else if (option == EQF_OPT_LA_TIMEOUT_US)
+        *value = (int)(c->la_timeout_ticks / 100);
+    else // EQF_OPT_TRACE
+        *value = c->d_trace ? 1 : 0;
+    return 0;
 }
 int eqf_set_option(eqf_ctx* c, int option, int value) {
-    if (!c)
+    const OptRow* row = c ? option_row(option) : nullptr;
+    if (!row)
         return EQF_E_BAD_ARG;
-    switch (option) {
+    if (row->kind == OPT_BOOL)
+        value = value ? 1 : 0;
+    else if (row->kind == OPT_RANGE && (value < row->lo || value > row->hi))
+        return EQF_E_BAD_ARG;
+    switch (option) { // what an option does besides being stored
     case EQF_OPT_RICCATI_DENSE:
         if (value && c->sig32)
             return EQF_E_UNSUPPORTED;
-        c->opt_dense = value;
-        return 0;
-    case EQF_OPT_CHECK_FINITE:
-        c->opt_check = value;
-        return 0;
-    case EQF_OPT_SPECULATIVE:
-        c->opt_spec = value;
-        return 0;
-    case EQF_OPT_DOORBELL:
-        c->opt_door = value;
-        return 0;
-    case EQF_OPT_EARLY_LIFT:
-        c->opt_early = value;
-        return 0;
-    case EQF_OPT_FUSED_ASSEMBLY:
-        c->opt_fuse_asm = value;
-        return 0;
+        break;
+    case EQF_OPT_SIGMA_FP32:
+        if (value == 2 && c->opt_dense)
+            return EQF_E_UNSUPPORTED; // the float store exists for the structured fast path only
+        break; // (the conversion of the live Sigma: below, with the new value in place)
     case EQF_OPT_Z_IN_LOOKAHEAD:
         c->opt_zb = value ? 1 : 0, c->opt_zb_large = value == 2 ? 0 : 1;
         return 0;
-    case EQF_OPT_LA_SPLIT_ROWS:
-        c->opt_la_split = value ? 1 : 0;
-        return 0;
     case EQF_OPT_LA_HOME:
-        c->opt_la_home = value < 0 ? 0 : std::min(value, 2); // 2: also when the device is shared (tests)
-        return 0;
-    case EQF_OPT_TILES_PER_WORKGROUP:
-        if (value < 0 || value > 8)
-            return EQF_E_BAD_ARG;
-        c->opt_prop_tpw = value;
-        return 0;
-    case EQF_OPT_GATHER_IN_PROPAGATE:
-        c->opt_gather = value ? 1 : 0;
-        return 0;
-    case EQF_OPT_HOLD_NEW_LANDMARKS:
-        c->opt_hold = value ? 1 : 0;
-        return 0;
-    case EQF_OPT_SELECT_ONE_WORKGROUP:
-        c->opt_sel_one = value ? 1 : 0;
-        return 0;
-    case EQF_OPT_LIVE_COLUMNS_FIRST:
-        c->opt_live_first = value ? 1 : 0;
-        return 0;
-    case EQF_OPT_EARLY_DOORBELL:
-        c->opt_early_door = value ? 1 : 0;
-        return 0;
-    case EQF_OPT_QUIET_DOOR_WAIT:
-        c->opt_quiet_wait = value ? 1 : 0;
-        return 0;
+        value = value < 0 ? 0 : std::min(value, 2); // 2: also when the device is shared (tests)
+        break;
     case EQF_OPT_MEASURE_IN_PROPAGATE:
-        c->opt_measure_prop = value ? 1 : 0;
         c->me_valid = false;
-        return 0;
-    case EQF_OPT_LIFT_WITH_SYRK:
-        c->opt_lift_syrk = value ? 1 : 0;
-        return 0;
+        break;
     case EQF_OPT_LOOKAHEAD:
-        c->opt_lookahead = value;
         c->la_consecutive_stalls = 0;
-        return 0;
+        break;
     case EQF_OPT_LA_TIMEOUT_US:
-        if (value < 0)
-            return EQF_E_BAD_ARG;
         c->la_timeout_ticks = 100ll * value; // 100 MHz device wall clock
         return 0;
-    case EQF_OPT_TRACE: {
-        { int _r = sync_ctx(c); if (_r) return _r; }
+    case EQF_OPT_TRACE:
+        EQFCHK(sync_ctx(c));
         if (value && !c->d_trace) {
-            HIPCHK(hipMalloc(&c->d_trace, sizeof(trace_t) * TR_FRAMES * TR_SLOTS));
-            HIPCHK(hipMemset(c->d_trace, 0, sizeof(trace_t) * TR_FRAMES * TR_SLOTS));
-            if (!c->d_ladbg) {
-                HIPCHK(hipMalloc(&c->d_ladbg, 96 * 8 * sizeof(unsigned long long)));
-                HIPCHK(hipMemset(c->d_ladbg, 0, 96 * 8 * sizeof(unsigned long long)));
-            }
+            EQFCHK(alloc_device(c, c->d_trace, (size_t)TR_FRAMES * TR_SLOTS, true));
+            if (!c->d_ladbg)
+                EQFCHK(alloc_device(c, c->d_ladbg, 96 * 8, true));
             c->h_trace.assign((size_t)TR_FRAMES * TR_HOST, 0);
-        } else if (!value && c->d_trace) {
-            hipFree(c->d_trace);
-            c->d_trace = nullptr;
-        }
+        } else if (!value && c->d_trace)
+            free_device(c, c->d_trace);
         return 0;
-    }
-    case EQF_OPT_SIGMA_FP32: {
-        if (value < 0 || value > 3)
-            return EQF_E_BAD_ARG;
-        if (value == 2 && c->opt_dense)
-            return EQF_E_UNSUPPORTED; // the float store exists for the structured fast path only
-        c->opt_f32 = value;
-        { int _e = enter(c); if (_e) return _e; } // the live Sigma is converted: pending landmark bookkeeping first
-        const int rc = set_sigma_storage(c, value == 2);
-        return rc ? rc : round_sigma(c);
-    }
     case 100:
-        c->opt_timing = value;
         timing_reset(c);
-        return 0;
-    case 102: // (debug knob, not in the header: same-process A/B of LaArgs::watch_ahead)
-        c->opt_la_watch_ahead = value ? 1 : 0;
-        return 0;
-    default:
-        return EQF_E_BAD_ARG;
+        break;
     }
+    c->*(row->member) = value;
+    if (option == EQF_OPT_SIGMA_FP32) {
+        EQFCHK(enter(c)); // the live Sigma is converted: pending landmark bookkeeping first
+        EQFCHK(set_sigma_storage(c, value == 2));
+        return round_sigma(c);
+    }
+    return 0;
 }
 int eqf_synchronize(eqf_ctx* c) {
     if (!c)
         return EQF_E_BAD_ARG;
-    { int _r = settle_update(c); if (_r) return _r; }
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(settle_update(c));
+    EQFCHK(sync_ctx(c));
     return 0;
 }
 int eqf_num_landmarks(const eqf_ctx* c) { return c->N; }
@@ -1322,13 +1261,13 @@ void* eqf_stream(eqf_ctx* c) { return (void*)c->stream; }
 int eqf_set_state(eqf_ctx* c, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N) {
     if (!c || N < 0 || (N > 0 && (!ids || !q0 || !Q)))
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     if (N > c->Ncap) {
         const int rc = grow_capacity(c, std::max(N, 2 * c->Ncap));
         if (rc)
             return rc;
     }
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     c->est_valid = false, ++c->est_epoch;
     c->meas_valid = false;
     c->n_held = 0, c->held_in_memory = false;
@@ -1345,7 +1284,7 @@ int eqf_set_state(eqf_ctx* c, const double* xi0_sensor, const double* X_sensor, 
         hipLaunchKernelGGL(k_scatter_landmarks, dim3(blocks(N, 64)), dim3(64), 0, c->stream, N, 0, c->Ncap, c->d_scratch, c->d_scratch + 3 * N, c->q0(), c->Qq(),
                            c->Qa());
         HIPCHK(hipGetLastError());
-        { int _r = sync_ctx(c); if (_r) return _r; }
+        EQFCHK(sync_ctx(c));
     }
     return 0;
 }
@@ -1361,12 +1300,12 @@ int eqf_get_state(eqf_ctx* c, double* xi0_sensor, double* X_sensor, int* ids, do
     if (N > cap)
         return EQF_E_CAPACITY;
     if (N > 0) {
-        { int _e = enter(c); if (_e) return _e; }
-        { int _r = join_observer(c); if (_r) return _r; }
+        EQFCHK(enter(c));
+        EQFCHK(join_observer(c));
         hipLaunchKernelGGL(k_gather_landmarks_aos, dim3(blocks(N, 64)), dim3(64), 0, c->stream, N, c->Ncap, c->q0(), c->Qq(), c->Qa(), c->d_scratch);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c->h_buf, c->d_scratch, sizeof(double) * 8 * N, hipMemcpyDeviceToHost, c->stream));
-        { int _r = sync_ctx(c); if (_r) return _r; }
+        EQFCHK(sync_ctx(c));
         for (int i = 0; i < N; ++i) {
             if (ids)
                 ids[i] = c->ids[i];
@@ -1382,8 +1321,8 @@ int eqf_get_state(eqf_ctx* c, double* xi0_sensor, double* X_sensor, int* ids, do
 int eqf_set_sigma(eqf_ctx* c, const double* sig, int n) {
     if (!c || !sig || n != c->n())
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(enter(c));
+    EQFCHK(sync_ctx(c));
     std::memcpy(c->h_buf, sig, sizeof(double) * (size_t)n * n);
     if (c->sig32) { // doubles land in the other buffer, the conversion kernel writes the float store
         double* stage = c->d_sigma[1 - c->cur];
@@ -1393,22 +1332,22 @@ int eqf_set_sigma(eqf_ctx* c, const double* sig, int n) {
     } else {
         HIPCHK(hipMemcpy2DAsync(c->sigma(), sizeof(double) * c->ld, c->h_buf, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice, c->stream));
     }
-    { int _r = round_sigma(c); if (_r) return _r; }
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(round_sigma(c));
+    EQFCHK(sync_ctx(c));
     return 0;
 }
 int eqf_set_sigma_diag(eqf_ctx* c, const double* diag, int n) {
     if (!c || !diag || n != c->n())
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
-    { int _r = sync_ctx(c); if (_r) return _r; }
-    { int _r = keep_last_gamma(c); if (_r) return _r; }
+    EQFCHK(enter(c));
+    EQFCHK(sync_ctx(c));
+    EQFCHK(keep_last_gamma(c));
     std::memcpy(c->h_buf, diag, sizeof(double) * n);
     HIPCHK(hipMemcpyAsync(c->d_gamma, c->h_buf, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     LAUNCH_TS(c, k_set_diag, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, c->d_gamma, (TS*)c->sigma());
     HIPCHK(hipGetLastError());
-    { int _r = round_sigma(c); if (_r) return _r; }
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(round_sigma(c));
+    EQFCHK(sync_ctx(c));
     return 0;
 }
 int eqf_get_sigma_block(eqf_ctx* c, int r0, int c0, int rows, int cols, double* out) {
@@ -1416,7 +1355,7 @@ int eqf_get_sigma_block(eqf_ctx* c, int r0, int c0, int rows, int cols, double* 
         return EQF_E_BAD_ARG;
     if (rows == 0 || cols == 0)
         return 0;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     const double* src = c->sigma();
     if (c->sig32) { // widen into the other buffer first
         const int n = c->n();
@@ -1427,7 +1366,7 @@ int eqf_get_sigma_block(eqf_ctx* c, int r0, int c0, int rows, int cols, double* 
     }
     HIPCHK(hipMemcpy2DAsync(c->h_buf, sizeof(double) * rows, src + r0 + (size_t)c0 * c->ld, sizeof(double) * c->ld, sizeof(double) * rows, cols,
                             hipMemcpyDeviceToHost, c->stream));
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     std::memcpy(out, c->h_buf, sizeof(double) * (size_t)rows * cols);
     return 0;
 }
@@ -1437,8 +1376,10 @@ int eqf_get_sigma(eqf_ctx* c, double* sig, int n) {
     return eqf_get_sigma_block(c, 0, 0, n, n, sig);
 }
 
+// eqf_output_cov_all's pinned result, 4 Ncap (allocated on first use)
+static int ensure_ocov(eqf_ctx* c) { return c->h_ocov ? 0 : alloc_pinned(c, c->h_ocov, 4 * (size_t)c->Ncap); }
 static int fetch_estimates(eqf_ctx* c) { // d_est -> h_buf (4 planes of stride N)
-    { int _r = settle_update(c); if (_r) return _r; }
+    EQFCHK(settle_update(c));
     const int N = c->N;
     if (N == 0)
         return 0;
@@ -1446,8 +1387,8 @@ static int fetch_estimates(eqf_ctx* c) { // d_est -> h_buf (4 planes of stride N
         std::memcpy(c->h_buf, c->est_cache.data(), sizeof(double) * 4 * N);
         return 0;
     }
-    { int _e = enter(c); if (_e) return _e; }
-    { int _r = join_observer(c); if (_r) return _r; }
+    EQFCHK(enter(c));
+    EQFCHK(join_observer(c));
     // straight into the pinned staging buffer (no copy command behind the kernel: a blit and its boundary cost more than the 6 KB written across the bus)
     // (round 5) the host waits on a doorbell rung by the last of these kernels instead of the stream's completion signal (~8 us per state estimate read between propagation
     // and update: the reference's removeOutliers, the reference-side binding's member-for-member sequence)
@@ -1460,13 +1401,12 @@ static int fetch_estimates(eqf_ctx* c) { // d_est -> h_buf (4 planes of stride N
     // A caller that reads the state estimate between propagation and update is the reference's removeOutliers (src/VIOFilter.cpp:304-334), which asks for the output
     // covariance of every measured landmark next: computed here as well, for the camera of the last such request, behind the same wait (eqf_output_cov_all returns it)
     if (with_ocov) {
-        if (!c->h_ocov)
-            HIPCHK(hipHostMalloc(&c->h_ocov, sizeof(double) * 4 * (size_t)c->Ncap));
+        EQFCHK(ensure_ocov(c));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_output_cov<double>), dim3(blocks(N, 64)), dim3(64), 0, c->stream, N, c->Ncap, c->ld, c->chart, c->ocov_hint, c->q0(), c->Qq(), c->Qa(),
                            (const double*)c->sigma(), c->h_ocov, dcount, c->h_door + 2, door_seq);
         HIPCHK(hipGetLastError());
     }
-    { int _r = use_door ? door_wait(c, 2, door_seq) : sync_ctx(c); if (_r) return _r; }
+    EQFCHK(use_door ? door_wait(c, 2, door_seq) : sync_ctx(c));
     if (with_ocov)
         c->ocov_valid = true, c->ocov_cam = c->ocov_hint;
     return 0;
@@ -1515,18 +1455,17 @@ static int grow_capacity(eqf_ctx* c, int new_cap) {
     if (rc)
         return rc;
     eqf_ctx* t = nullptr;
-    replaces_own_queue = c->own_queue;
-    rc = eqf_create(&t, c->device, new_cap, c->chart);
-    replaces_own_queue = false;
+    rc = create_ctx(&t, c->device, new_cap, c->chart, c->own_queue);
     if (rc)
         return rc == EQF_E_NO_DEVICE ? rc : EQF_E_CAPACITY; // allocation failure at the new size
-    // EVERY option of eqf_set_option (tests/test_gpu_edge_cases.py: test_options_and_counters_survive_capacity_growth walks the enum)
-    const int opts[][2] = {{EQF_OPT_SIGMA_FP32, c->opt_f32}, {EQF_OPT_RICCATI_DENSE, c->opt_dense}, {EQF_OPT_CHECK_FINITE, c->opt_check}, {EQF_OPT_SPECULATIVE, c->opt_spec},
-                           {EQF_OPT_DOORBELL, c->opt_door}, {EQF_OPT_EARLY_LIFT, c->opt_early}, {EQF_OPT_FUSED_ASSEMBLY, c->opt_fuse_asm}, {EQF_OPT_LOOKAHEAD, c->opt_lookahead},
-                           {EQF_OPT_LA_TIMEOUT_US, (int)(c->la_timeout_ticks / 100)}, {EQF_OPT_Z_IN_LOOKAHEAD, c->opt_zb ? (c->opt_zb_large ? 1 : 2) : 0}, {EQF_OPT_LA_SPLIT_ROWS, c->opt_la_split}, {EQF_OPT_LA_HOME, c->opt_la_home}, {EQF_OPT_TILES_PER_WORKGROUP, c->opt_prop_tpw}, {EQF_OPT_GATHER_IN_PROPAGATE, c->opt_gather}, {EQF_OPT_HOLD_NEW_LANDMARKS, c->opt_hold}, {EQF_OPT_EARLY_DOORBELL, c->opt_early_door}, {EQF_OPT_QUIET_DOOR_WAIT, c->opt_quiet_wait}, {EQF_OPT_SELECT_ONE_WORKGROUP, c->opt_sel_one}, {EQF_OPT_LIVE_COLUMNS_FIRST, c->opt_live_first}, {EQF_OPT_MEASURE_IN_PROPAGATE, c->opt_measure_prop}, {EQF_OPT_LIFT_WITH_SYRK, c->opt_lift_syrk}, {EQF_OPT_TRACE, c->d_trace ? 1 : 0}, {100, c->opt_timing}};
-    for (const auto& o : opts)
-        if ((rc = eqf_set_option(t, o[0], o[1])) != 0)
-            break;
+    // Options: the ones that do something to the context when they are set go through eqf_set_option, the storage of Sigma before anything is stored in it;
+    // every other one is a member of CtxOptions (kOptions: there is no option outside it)
+    rc = eqf_set_option(t, EQF_OPT_SIGMA_FP32, c->opt_f32);
+    static_cast<CtxOptions&>(*t) = *c;
+    if (!rc)
+        rc = eqf_set_option(t, EQF_OPT_TRACE, c->d_trace ? 1 : 0);
+    if (!rc)
+        rc = eqf_set_option(t, 100, c->opt_timing);
     if (!rc)
         rc = eqf_set_state(t, xi0s, Xs, ids.data(), q0.data(), Q.data(), N);
     if (!rc)
@@ -1535,13 +1474,12 @@ static int grow_capacity(eqf_ctx* c, int new_cap) {
         eqf_destroy(t);
         return rc;
     }
-    // what is not state of the filter but of the handle: counters, the last Gamma, the generation of the landmark set
+    // what is not state of the filter but of the handle: every counter, and the last Gamma, the self-test's verdict, the predictions' camera, the held landmarks,
+    // the generation of the landmark set
+    static_cast<CtxCounters&>(*t) = *c;
     t->last_gamma = c->last_gamma, t->n_at_update = c->n_at_update;
-    t->spec_calls = c->spec_calls, t->spec_queued = c->spec_queued, t->spec_cancelled = c->spec_cancelled, t->spec_backoff = c->spec_backoff, t->spec_backoff_len = c->spec_backoff_len;
-    t->nees_lu_fallbacks = c->nees_lu_fallbacks, t->wait_calls = c->wait_calls, t->launch_calls = c->launch_calls, t->wait_seconds = c->wait_seconds, t->launch_seconds = c->launch_seconds;
-    t->la_launches = c->la_launches, t->la_fallbacks = c->la_fallbacks, t->la_home_launches = c->la_home_launches, t->la_home_refused = c->la_home_refused, t->la_book_timeouts = c->la_book_timeouts, t->zb_launches = c->zb_launches, t->la_consecutive_stalls = c->la_consecutive_stalls, t->early_rings = c->early_rings;
     t->la_selftest = c->la_selftest < 0 ? -1 : (t->la_selftest != 0 ? t->la_selftest : c->la_selftest); // a failure is never forgotten; otherwise the test that ran on the NEW buffers counts
-    t->me_used = c->me_used, t->pred_valid = c->pred_valid, t->pred_cam = c->pred_cam, t->pred_star = c->pred_star;
+    t->pred_valid = c->pred_valid, t->pred_cam = c->pred_cam, t->pred_star = c->pred_star;
     t->n_held = c->n_held, t->held_var = c->held_var, t->held_in_memory = c->n_held > 0; // (eqf_get_state above went through enter(): held landmarks are in memory now)
     t->lm_gen = c->lm_gen + 1;
     std::swap(*c, *t);
@@ -1584,7 +1522,7 @@ static int flush_reshape(eqf_ctx* c) {
         c->reshape_pending = false;
         return 0;
     }
-    { int _r = join_observer(c); if (_r) return _r; } // landmark kernels of a stand-alone observer call run on the second stream
+    EQFCHK(join_observer(c)); // landmark kernels of a stand-alone observer call run on the second stream
     bool pure_append = knew > 0 && knew <= APPEND_MAX && Nnew - knew == c->dev_N;
     for (int i = 0; pure_append && i < Nnew; ++i)
         pure_append = c->pend_map[i] == (i < c->dev_N ? i : -(i - c->dev_N + 1));
@@ -1984,6 +1922,12 @@ int eqf_remove_invalid_landmarks(eqf_ctx* c) {
     return rc ? rc : (int)bad.size();
 }
 
+// F and F Sigma of the dense Riccati modes, each the size of Sigma (allocated on first use)
+static int ensure_dense(eqf_ctx* c) {
+    if (!c->d_F)
+        EQFCHK(alloc_device(c, c->d_F, (size_t)c->ld * c->ncap));
+    return c->d_tmp ? 0 : alloc_device(c, c->d_tmp, (size_t)c->ld * c->ncap);
+}
 static int riccati_after_assemble(eqf_ctx* c, double dt, const double* Qdiag12, const double* Pdiag8, const ObsSteps* obs = nullptr, int obs_k = 0, bool fused = false,
                                   const GatherArgs* gather = nullptr);
 int eqf_integrate_riccati_fast(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
@@ -1991,7 +1935,7 @@ int eqf_integrate_riccati_fast(eqf_ctx* c, const double* imu13, double dt, const
         return EQF_E_UNSUPPORTED; // landmarks held for eqf_propagate_fast (eqf_add_landmarks_held): only that call knows to leave them alone
     if (!c || !imu13 || !Qdiag12 || !Pdiag8)
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     int rc = upload_common(c, imu13);
     if (rc)
         return rc;
@@ -2145,11 +2089,7 @@ static int riccati_after_assemble(eqf_ctx* c, double dt, const double* Qdiag12, 
         c->n_held = 0, c->held_in_memory = false; // they are ordinary landmarks from here on
     } else {
         // dense: F materialised, tmp = F Sigma (= (Sigma F^T)^T, Sigma symmetric), Sigma' = tmp F^T + noise
-        const size_t bytes = sizeof(double) * (size_t)c->ld * c->ncap;
-        if (!c->d_F)
-            HIPCHK(hipMalloc(&c->d_F, bytes));
-        if (!c->d_tmp)
-            HIPCHK(hipMalloc(&c->d_tmp, bytes));
+        EQFCHK(ensure_dense(c));
         KTimer t(c, KN_DENSE_GEMM);
         hipLaunchKernelGGL(k_build_F, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, dt, c->d_common, c->d_Al, c->d_F);
         HIPCHK(hipGetLastError());
@@ -2168,7 +2108,7 @@ static int riccati_after_assemble(eqf_ctx* c, double dt, const double* Qdiag12, 
         if (rc)
             return rc;
     }
-    { int _r = round_sigma(c); if (_r) return _r; }
+    EQFCHK(round_sigma(c));
     if (c->opt_check) {
         LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
         HIPCHK(hipGetLastError());
@@ -2188,19 +2128,15 @@ int eqf_integrate_riccati_accurate(eqf_ctx* c, const double* imu13, double dt, c
         return EQF_E_BAD_ARG;
     if (c->sig32)
         return EQF_E_UNSUPPORTED; // the float store exists for the structured fast path only
-    { int _e = enter(c); if (_e) return _e; }
-    const size_t bytes = sizeof(double) * (size_t)c->ld * c->ncap;
+    EQFCHK(enter(c));
     if (!c->d_Ebuf) {
-        HIPCHK(hipMalloc(&c->d_Ebuf, sizeof(double) * (EXPM_SMAX + 2) * 21 * 33));
-        HIPCHK(hipMalloc(&c->d_Yl, sizeof(double) * 99 * (size_t)c->Ncap));
-        HIPCHK(hipMalloc(&c->d_Fl, sizeof(double) * 9 * (size_t)c->Ncap));
-        HIPCHK(hipMalloc(&c->d_PhiB, sizeof(double) * (size_t)c->ld * 12));
-        HIPCHK(hipMalloc(&c->d_expinfo, sizeof(int) * 4));
+        EQFCHK(alloc_device(c, c->d_Ebuf, (size_t)(EXPM_SMAX + 2) * 21 * 33));
+        EQFCHK(alloc_device(c, c->d_Yl, 99 * (size_t)c->Ncap));
+        EQFCHK(alloc_device(c, c->d_Fl, 9 * (size_t)c->Ncap));
+        EQFCHK(alloc_device(c, c->d_PhiB, (size_t)c->ld * 12));
+        EQFCHK(alloc_device(c, c->d_expinfo, 4));
     }
-    if (!c->d_F)
-        HIPCHK(hipMalloc(&c->d_F, bytes));
-    if (!c->d_tmp)
-        HIPCHK(hipMalloc(&c->d_tmp, bytes));
+    EQFCHK(ensure_dense(c));
     int rc = upload_common(c, imu13);
     if (rc)
         return rc;
@@ -2276,12 +2212,9 @@ int eqf_integrate_riccati_discrete(eqf_ctx* c, const double* imu13, double dt, c
         return EQF_E_BAD_ARG;
     if (c->sig32)
         return EQF_E_UNSUPPORTED; // float store: structured fast path only
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     const size_t bytes = sizeof(double) * (size_t)c->ld * c->ncap;
-    if (!c->d_F)
-        HIPCHK(hipMalloc(&c->d_F, bytes));
-    if (!c->d_tmp)
-        HIPCHK(hipMalloc(&c->d_tmp, bytes));
+    EQFCHK(ensure_dense(c));
     int rc = upload_common(c, imu13); // B_t at the current X (inputMatrixB), for dt (B Q B^T + P)
     if (rc)
         return rc;
@@ -2334,7 +2267,7 @@ int eqf_integrate_riccati_discrete(eqf_ctx* c, const double* imu13, double dt, c
             Ass[r + 21 * j] = (col[0][r] - col[1][r]) / (2.0 * h);
     }
     const int N = c->N, n = c->n();
-    { int _r = sync_ctx(c); if (_r) return _r; } // h_buf staging
+    EQFCHK(sync_ctx(c)); // h_buf staging
     std::memcpy(c->h_buf, Ass, sizeof(Ass));
     HIPCHK(hipMemsetAsync(c->d_F, 0, bytes, c->stream));
     HIPCHK(hipMemcpy2DAsync(c->d_F, sizeof(double) * c->ld, c->h_buf, sizeof(double) * 21, sizeof(double) * 21, 21, hipMemcpyHostToDevice, c->stream));
@@ -2441,7 +2374,7 @@ int eqf_integrate_observer(eqf_ctx* c, const double* imu13_k, const double* dt_k
         return EQF_E_BAD_ARG;
     if (k == 0)
         return 0;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     c->est_valid = false, ++c->est_epoch;
     c->meas_valid = false;
     c->me_valid = false; // output blocks the propagation kernel evaluated belong to the Q_i from before these steps
@@ -2500,9 +2433,7 @@ int eqf_propagate_fast(eqf_ctx* c, const double* imu13_mean, double dt_total, co
         HIPCHK(hipSetDevice(c->device));
         c->ocov_valid = false;
     } else {
-        int _e = enter(c, false); // (an unsettled update is settled behind this call's launch: nothing it queues or computes needs the lift's results)
-        if (_e)
-            return _e;
+        EQFCHK(enter(c, false)); // (an unsettled update is settled behind this call's launch: nothing it queues or computes needs the lift's results)
     }
     ++c->trace_frame; // EQF_OPT_TRACE: a frame starts here
     host_stamp(c, TH_PROP_ENTRY);
@@ -2794,13 +2725,12 @@ int eqf_output_cov_all(eqf_ctx* c, const eqvio_camera* cam, double* out4N) {
         }
     }
     c->ocov_hint = make_cam(cam), c->ocov_hint_valid = true;
-    { int _e = enter(c); if (_e) return _e; }
-    { int _r = join_observer(c); if (_r) return _r; }
-    if (!c->h_ocov)
-        HIPCHK(hipHostMalloc(&c->h_ocov, sizeof(double) * 4 * (size_t)c->Ncap));
+    EQFCHK(enter(c));
+    EQFCHK(join_observer(c));
+    EQFCHK(ensure_ocov(c));
     LAUNCH_TS(c, k_output_cov, dim3(blocks(N, 64)), dim3(64), c->stream, N, c->Ncap, c->ld, c->chart, make_cam(cam), c->q0(), c->Qq(), c->Qa(), (const TS*)c->sigma(), c->h_ocov);
     HIPCHK(hipGetLastError());
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     std::memcpy(out4N, c->h_ocov, sizeof(double) * 4 * N);
     return 0;
 }
@@ -2811,8 +2741,8 @@ int eqf_outlier_stats(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const
     const int N = c->N;
     if (N == 0)
         return 0;
-    { int _e = enter(c); if (_e) return _e; }
-    { int _r = fit_measurement(c, M); if (_r) return _r; }
+    EQFCHK(enter(c));
+    EQFCHK(fit_measurement(c, M));
     c->staged_valid = c->stage_pending = c->stage_requested = false; // the pinned measurement packet is about to be rewritten
     if (c->busy_meas) {
         int r = sync_ctx(c);
@@ -3119,7 +3049,7 @@ static int launch_factor_tail(eqf_ctx* c, int M, int discreteCorr, const int* sp
                            c->d_gamma, c->d_flags, trace_slot(c, TR_SYRK), c->d_syrk_order + c->syrk_off[nt], lift_args(c, discreteCorr, spec, spec_seq, use_door, door_seq, la ? nullptr : c->d_gpart, stall_seq),
                            nlift, blocks(m, 32) <= 16 ? c->la_live_cols : (const int*)nullptr, nt <= SYRK_ARITH_TILES ? nt : 0);
         HIPCHK(hipGetLastError());
-        { int _r = round_sigma(c, spec, spec_seq); if (_r) return _r; }
+        EQFCHK(round_sigma(c, spec, spec_seq));
         if (c->opt_check) {
             LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
             HIPCHK(hipGetLastError());
@@ -3144,7 +3074,7 @@ static int launch_factor_tail(eqf_ctx* c, int M, int discreteCorr, const int* sp
 #undef SYRK_LAUNCH
         HIPCHK(hipGetLastError());
     }
-    { int _r = round_sigma(c, spec, spec_seq); if (_r) return _r; }
+    EQFCHK(round_sigma(c, spec, spec_seq));
     if (!c->opt_early) {
         rc = launch_lift(c, discreteCorr, spec, spec_seq, use_door, door_seq, nullptr, stall_seq);
         if (rc)
@@ -3328,7 +3258,7 @@ int eqf_vision_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const
         return 0; // VIO_eqf.cpp:108-109
     if (M > c->N)
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     const bool reuse = c->meas_valid && c->meas_star == (useEqv ? 1 : 0) && (int)c->meas_ids.size() == M && std::equal(ids, ids + M, c->meas_ids.begin()) &&
                        std::memcmp(c->h_y, y, sizeof(double) * 2 * M) == 0;
     int rc = 0;
@@ -3415,9 +3345,9 @@ static int stats_then_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids
         *updated = -1; // not applicable (a landmark has to be added first)
         return 0;
     }
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     host_stamp(c, TH_TAIL_ENTRY);
-    { int _r = join_observer(c); if (_r) return _r; } // before the flags below are evaluated, as in eqf_outlier_stats: a stand-alone observer call does not cost the frame its doorbell
+    EQFCHK(join_observer(c)); // before the flags below are evaluated, as in eqf_outlier_stats: a stand-alone observer call does not cost the frame its doorbell
     // speculation needs the doorbell-free conditions of both waits and the equivariant-output cache of the statistics kernel
     // A cancelled tail costs the frame a wasted launch sequence on top of the two-round-trip path it falls back to. Where outlier candidates
     // show up frame after frame (tight thresholds) speculation backs off: after a cancellation the next 1, 2, 4 .. 16 frames only compute
@@ -3613,7 +3543,7 @@ int eqf_selection_stats(eqf_ctx* c, long* frames, long* discarded, int reset) {
 int eqf_last_gamma(eqf_ctx* c, double* out, int cap) {
     if (!c || !out)
         return EQF_E_BAD_ARG;
-    { int _r = keep_last_gamma(c); if (_r) return _r; }
+    EQFCHK(keep_last_gamma(c));
     if ((int)c->last_gamma.size() > cap)
         return EQF_E_CAPACITY;
     std::memcpy(out, c->last_gamma.data(), sizeof(double) * c->last_gamma.size());
@@ -3623,7 +3553,7 @@ int eqf_last_gamma(eqf_ctx* c, double* out, int cap) {
 int eqf_compute_nees(eqf_ctx* c, const double* ts, const int* tids, const double* tp, int ntrue, double* nees) {
     if (!c || !ts || !nees || ntrue < 0 || (ntrue > 0 && (!tids || !tp)))
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     const int N = c->N, n = c->n();
     const int np = n + (n & 1); // even dimension for the 2x2-pivot elimination: pad with a unit diagonal entry
     // landmark group elements from the device
@@ -3655,12 +3585,12 @@ int eqf_compute_nees(eqf_ctx* c, const double* ts, const int* tids, const double
     if (!c->d_Zn) {
         const int npcap = c->ncap + 1;
         c->ldzn = pick_ld(npcap + 1);
-        HIPCHK(hipMalloc(&c->d_Zn, sizeof(double) * (size_t)c->ldzn * npcap));
-        HIPCHK(hipMalloc(&c->d_Wn, sizeof(double) * (size_t)c->ldzn * npcap));
-        HIPCHK(hipMalloc(&c->d_perm, sizeof(int) * 2 * (size_t)(c->ncap + 2)));
+        EQFCHK(alloc_device(c, c->d_Zn, (size_t)c->ldzn * npcap));
+        EQFCHK(alloc_device(c, c->d_Wn, (size_t)c->ldzn * npcap));
+        EQFCHK(alloc_device(c, c->d_perm, 2 * (size_t)(c->ncap + 2)));
     }
-    { int _r = keep_last_gamma(c); if (_r) return _r; } // d_gamma serves as the staging buffer of eps below
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(keep_last_gamma(c)); // d_gamma serves as the staging buffer of eps below
+    EQFCHK(sync_ctx(c));
     std::memcpy(c->h_buf, eps.data(), sizeof(double) * np);
     HIPCHK(hipMemcpyAsync(c->d_gamma, c->h_buf, sizeof(double) * np, hipMemcpyHostToDevice, c->stream)); // d_gamma as staging (ncap >= np? see below)
     HIPCHK(hipMemsetAsync(c->d_flags, 0, sizeof(int) * 4, c->stream));
@@ -3690,7 +3620,7 @@ int eqf_compute_nees(eqf_ctx* c, const double* ts, const int* tids, const double
         hipLaunchKernelGGL(k_ge_back, dim3(1), dim3(1024), sizeof(double) * (np + 16), c->stream, n, np, c->ldzn, c->d_Zn, c->d_perm + (np & 1) * pstride, c->d_gamma, c->d_stats);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c->h_buf, c->d_stats, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        { int _r = sync_ctx(c); if (_r) return _r; }
+        EQFCHK(sync_ctx(c));
     }
     *nees = c->h_buf[0] / (double)n;
     return 0;
@@ -3699,7 +3629,7 @@ int eqf_compute_nees(eqf_ctx* c, const double* ts, const int* tids, const double
 int eqf_debug_get_W(eqf_ctx* c, double* out, int rows, int cols) {
     if (!c || !out || rows <= 0 || cols <= 0 || rows > c->ldz || cols > c->mcap)
         return EQF_E_BAD_ARG;
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     HIPCHK(hipMemcpy2D(out, sizeof(double) * rows, c->d_W, sizeof(double) * c->ldz, sizeof(double) * rows, cols, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -3707,7 +3637,7 @@ int eqf_debug_get_W(eqf_ctx* c, double* out, int rows, int cols) {
 int eqf_debug_lookahead_stamps(eqf_ctx* c, unsigned long long* out768) {
     if (!c || !out768 || !c->d_ladbg)
         return EQF_E_BAD_ARG;
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     HIPCHK(hipMemcpy(out768, c->d_ladbg, 96 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -3797,8 +3727,8 @@ int eqf_nees_lu_fallbacks(eqf_ctx* c, long* count) {
 int eqf_debug_matrices_AB(eqf_ctx* c, const double* imu13, double* A_out, double* B_out) {
     if (!c || !imu13)
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(enter(c));
+    EQFCHK(sync_ctx(c));
     int rc = upload_common(c, imu13);
     if (rc)
         return rc;
@@ -3809,7 +3739,7 @@ int eqf_debug_matrices_AB(eqf_ctx* c, const double* imu13, double* A_out, double
     std::vector<double> Al(45 * (size_t)Ncap), Bl(9 * (size_t)Ncap);
     HIPCHK(hipMemcpyAsync(c->h_buf, c->d_Al, sizeof(double) * 45 * Ncap, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->h_buf + 45 * (size_t)Ncap, c->d_Bl, sizeof(double) * 9 * Ncap, hipMemcpyDeviceToHost, c->stream));
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     std::memcpy(Al.data(), c->h_buf, sizeof(double) * 45 * Ncap);
     std::memcpy(Bl.data(), c->h_buf + 45 * (size_t)Ncap, sizeof(double) * 9 * Ncap);
     const Common& cm = *c->h_common;
@@ -3906,7 +3836,7 @@ int eqf_debug_matrices_AB(eqf_ctx* c, const double* imu13, double* A_out, double
 int eqf_debug_matrix_C(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const double* y, int M, int useEqv, double* C_out, double* ytilde_out) {
     if (!c || !cam || M <= 0 || !ids || !y || M > c->N)
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     int rc = stage_measurement(c, ids, y, M);
     if (rc)
         return rc;
@@ -3917,7 +3847,7 @@ int eqf_debug_matrix_C(eqf_ctx* c, const eqvio_camera* cam, const int* ids, cons
     const int Ncap = c->Ncap, n = c->n();
     HIPCHK(hipMemcpyAsync(c->h_buf, c->d_C, sizeof(double) * 6 * Ncap, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->h_buf + 6 * (size_t)Ncap, c->d_ytil, sizeof(double) * 2 * M, hipMemcpyDeviceToHost, c->stream));
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     if (C_out) {
         std::fill(C_out, C_out + (size_t)2 * M * n, 0.0);
         for (int j = 0; j < M; ++j)
@@ -3933,7 +3863,7 @@ int eqf_debug_matrix_C(eqf_ctx* c, const eqvio_camera* cam, const int* ids, cons
 int eqf_mfma_f64_peak_clock(eqf_ctx* c, double* tflops, double* sclk_ghz) {
     if (!c || !tflops)
         return EQF_E_BAD_ARG;
-    { int _e = enter(c); if (_e) return _e; }
+    EQFCHK(enter(c));
     const int nblk = 256 * 8, iters = 4096;
     double* d_out = nullptr;
     unsigned long long* d_clk = nullptr;
@@ -3979,7 +3909,7 @@ int eqf_trace_read(eqf_ctx* c, unsigned long long* device_ticks, long long* host
         return EQF_E_BAD_ARG;
     if (!c->d_trace)
         return EQF_E_UNSUPPORTED;
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     HIPCHK(hipMemcpy(device_ticks, c->d_trace, sizeof(trace_t) * TR_FRAMES * TR_SLOTS, hipMemcpyDeviceToHost));
     std::memcpy(host_ns, c->h_trace.data(), sizeof(long long) * TR_FRAMES * TR_HOST);
     *last_frame = c->trace_frame;
@@ -4003,7 +3933,7 @@ int eqf_host_wait_stats(eqf_ctx* c, long* calls, double* seconds, int reset) {
 int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
     if (!c)
         return EQF_E_BAD_ARG;
-    { int _r = sync_ctx(c); if (_r) return _r; }
+    EQFCHK(sync_ctx(c));
     int cnt = 0;
     for (size_t q = 0; q < c->tev.size(); ++q) {
         auto& t = c->tev[q];

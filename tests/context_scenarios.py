@@ -234,8 +234,10 @@ class DeviceRun:
     updated: list = None
 
 
-def read_counters(core):
-    v = [C.c_long() for _ in range(9)]
+def read_counters(core, every=False):
+    """The counters that name the route a frame took (what a repeated run must reproduce). every=True: also the ones that depend on the host's timing or are not
+    about routes - every other *_stats getter, eqf_nees_lu_fallbacks and the wait count of eqf_host_wait_stats. Nothing is reset."""
+    v = [C.c_long() for _ in range(14)]
     lib, h = core.lib, core.h
     assert lib.eqf_lookahead_stats(h, C.byref(v[0]), C.byref(v[1]), 0) == 0
     assert lib.eqf_z_in_lookahead_stats(h, C.byref(v[2]), 0) == 0
@@ -243,7 +245,19 @@ def read_counters(core):
     assert lib.eqf_speculation_stats(h, C.byref(v[4]), C.byref(v[5]), C.byref(v[6]), 0) == 0
     assert lib.eqf_selection_stats(h, C.byref(v[7]), C.byref(v[8]), 0) == 0
     names = ("la", "la_fallbacks", "zb", "me", "calls", "queued", "cancelled", "sel", "discarded")
-    return {k: x.value for k, x in zip(names, v)}
+    if every:
+        assert lib.eqf_hold_stats(h, C.byref(v[9]), 0) == 0
+        assert lib.eqf_gather_stats(h, C.byref(v[10]), 0) == 0
+        assert lib.eqf_live_columns_stats(h, C.byref(v[11]), 0) == 0
+        assert lib.eqf_early_doorbell_stats(h, C.byref(v[12]), 0) == 0
+        assert lib.eqf_nees_lu_fallbacks(h, C.byref(v[13])) == 0
+        names += ("hold", "gather", "live", "early", "nees_lu")
+    out = {k: x.value for k, x in zip(names, v)}
+    if every:
+        calls, seconds = (C.c_long * 2)(), (C.c_double * 2)()
+        assert lib.eqf_host_wait_stats(h, calls, seconds, 0) == 0
+        out["wait_calls"] = calls[0]
+    return out
 
 
 def run_device(sc, orun, options=()):

@@ -255,18 +255,23 @@ def test_random_bookkeeping_sequences_match_the_oracle(seed):
 def test_options_and_counters_survive_capacity_growth():
     """growing the capacity rebuilds the context (eqf_hip.hip: grow_capacity) and must carry EVERY option of eqf_set_option and every counter
     over. Walks the option enum through eqf_get_option (so that a new option cannot be forgotten without this test failing: every id declared in
-    include/eqf_hip.h that the library knows is set to a non-default value before the growth and read back after it), and checks that the look-ahead
-    counters of eqf_lookahead_stats do not restart."""
+    include/eqf_hip.h that the library knows, and the two debug ids 100 and 102, is set to a non-default value before the growth and read back after it),
+    and checks that no counter restarts: before the growth one frame each makes the counters of eqf_lookahead_stats, eqf_speculation_stats,
+    eqf_selection_stats (with eqf_live_columns_stats: 3 panels), eqf_gather_stats and eqf_hold_stats non-zero, and everything
+    context_scenarios.read_counters reads is compared across the growth."""
     import ctypes as C
     import os
     import re
 
-    from eqvio_amd.capi import OPT_LA_TIMEOUT_US, OPT_LOOKAHEAD, OPT_SIGMA_FP32, OPT_TRACE, OPT_Z_IN_LOOKAHEAD
+    from batch_scenarios import frame_imus
+    from context_scenarios import FRAME_DT, read_counters
+    from eqvio_amd.capi import OPT_LA_TIMEOUT_US, OPT_LOOKAHEAD, OPT_SIGMA_FP32, OPT_SPECULATIVE, OPT_TRACE, OPT_Z_IN_LOOKAHEAD
+    from util import imu_selection
 
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "eqf_hip.h")).read()
     enum = hdr[hdr.index("/* options for eqf_set_option */"):]
     enum = enum[: enum.index("};")]
-    opt_ids = sorted({int(v) for v in re.findall(r"^\s+EQF_OPT_[A-Z0-9_]+\s*=\s*(\d+)", enum, re.M)} | {100})
+    opt_ids = sorted({int(v) for v in re.findall(r"^\s+EQF_OPT_[A-Z0-9_]+\s*=\s*(\d+)", enum, re.M)} | {100, 102})
     assert len(opt_ids) >= 12, opt_ids
     rng = np.random.default_rng(9)
     N = 40
@@ -277,10 +282,36 @@ def test_options_and_counters_survive_capacity_growth():
     core.set_state(xi0, Xs, ids, q0, Q)
     core.set_sigma(np.diag(settings.initial_cov_diag(N)))
     cam = default_camera()
+    var = settings.measurementNoise**2
     mid, y = synth_measurement(rng, cam, ids, q0, Q, noise_px=1.0)
-    core.vision_update(cam, mid, y, settings.measurementNoise**2, True, False)  # 3 panels: one look-ahead launch on the books
+    core.vision_update(cam, mid, y, var, True, False)  # 3 panels: one look-ahead launch on the books
     a, b = C.c_long(), C.c_long()
     assert core.lib.eqf_lookahead_stats(core.h, C.byref(a), C.byref(b), 0) == 0 and (a.value, b.value) == (1, 0)
+
+    # the other counters, each by the entry point that counts it (default options; 40 landmarks in a capacity of 48)
+    def measurement():  # every landmark of the current state, from the device's own estimate (a read: pending landmark bookkeeping is applied)
+        _, _, ids_now, q0_now, Q_now = core.get_state()
+        return synth_measurement(rng, cam, ids_now, q0_now, Q_now, noise_px=1.0)
+
+    def propagate(t0):
+        imus = frame_imus(rng, t0, t0 + FRAME_DT, 4)
+        dts, mean, total = imu_selection(imus, t0, t0 + FRAME_DT)
+        core.propagate_fast(mean, total, settings.input_gain_diag12(), settings.state_gain_diag8(), imus, dts, True)
+
+    mid, y = measurement()
+    assert core.stats_then_update(cam, mid, y, 1e9, 1e9, var, True, False)[0] == 1  # a speculative tail, not cancelled
+    mid, y = measurement()
+    y[2 * 7:2 * 7 + 2] += 60.0  # one measurement 85 px off: an outlier by the absolute threshold
+    core.set_option(OPT_SPECULATIVE, 0)  # straight to the device-side decision (what the back-off reaches after a cancelled tail)
+    upd, _, _, _, removed = core.stats_select_update(cam, mid, y, 30.0, 1e9, 5, var, True, False)
+    core.set_option(OPT_SPECULATIVE, 1)
+    assert upd == 1 and len(removed) == 1 and core.N == 39
+    core.remove_landmarks(np.array([3], np.int32))
+    propagate(0.0)  # the removal record (the discarded landmark and landmark 3) is applied by the propagation kernel
+    assert core.add_landmarks_held(np.array([900, 901], np.int32), rng.uniform(-1, 1, (2, 3)) + [0, 0, 5], 0.5)
+    propagate(FRAME_DT)  # ... which also creates the held landmarks
+    assert core.N == N
+
     # a non-default value for every option (values that are legal together: the dense Riccati excludes the float store, id 3 = 1 is its fp64 model)
     wanted = {}
     for oid in opt_ids:
@@ -289,12 +320,20 @@ def test_options_and_counters_survive_capacity_growth():
         core.set_option(oid, new)
         wanted[oid] = core.get_option(oid)
         assert wanted[oid] == new, oid
+    before = read_counters(core, every=True)
+    print("counters before the growth:", before)
+    for k in ("la", "zb", "calls", "queued", "sel", "discarded", "live", "gather", "hold", "wait_calls"):
+        assert before[k] > 0, (k, before)
     p = rng.uniform(-1, 1, (70, 3)) + [0, 0, 5]
     core.add_landmarks(np.arange(1000, 1070, dtype=np.int32), p, 0.5)  # 110 landmarks > capacity 40: the context is rebuilt
     assert core.N == 110
-    for oid in opt_ids:
-        assert core.get_option(oid) == wanted[oid], (oid, core.get_option(oid), wanted[oid])
-    assert core.lib.eqf_lookahead_stats(core.h, C.byref(a), C.byref(b), 0) == 0 and (a.value, b.value) == (1, 0)
+    after = read_counters(core, every=True)
+    print("counters after the growth: ", after)
+    # everything that was lost is named in one message: option id -> (read back, wanted), counter -> (before, after)
+    lost_options = {oid: (core.get_option(oid), wanted[oid]) for oid in opt_ids if core.get_option(oid) != wanted[oid]}
+    lost_counters = {k: (before[k], after[k]) for k in before if (after[k] < before[k] if k == "wait_calls" else after[k] != before[k])}  # (the growth itself reads state and Sigma back: it may wait)
+    assert not lost_options and not lost_counters, (lost_options, lost_counters)
+    assert core.lib.eqf_lookahead_stats(core.h, C.byref(a), C.byref(b), 0) == 0 and (a.value, b.value) == (before["la"], 0)
     assert OPT_LOOKAHEAD in opt_ids and OPT_Z_IN_LOOKAHEAD in opt_ids
 
 
