@@ -137,6 +137,36 @@ GroupSensor group_mul(const GroupSensor& a, const GroupSensor& b) {
 
 } // namespace
 
+// The vision update's tail - everything from the mapped measurement to the applied lift - is decided ONCE, before its first launch (plan_tail), and launched from that
+// value alone (launch_tail, launch_lookahead): no launch looks an option up again, and nothing is handed on through the context. The plan of the tail in flight is
+// a member of the context (eqf_ctx::tail): finish_update reads what was launched from it and derives the plan of a retry on the launch chain (retry_plan).
+struct TailPlan {
+    // sizes and call data
+    int M = 0, m = 0, n = 0, rows = 0; // measurements; columns of Z (2 M); dimension of Sigma; rows of Z (m + n + 1)
+    double meas_var = 0.0;
+    int discreteCorr = 0;
+    // speculation and waits
+    const int* spec = nullptr;      // the tail's cancellation word: every kernel compares *spec with spec_seq and returns at once if they match (nullptr: not speculative)
+    int spec_seq = 0;
+    bool use_door = false;          // the host waits for the lift's doorbell (door_seq), not for the stream
+    int door_seq = 0;
+    // measurement inputs
+    MeasFuse mf{};                  // measurement fusion (the speculative tail: nobody has evaluated the output blocks or the statistics in front of it); mf.enabled == 0: none
+    const int* live_cols = nullptr; // EQF_OPT_LIVE_COLUMNS_FIRST, up to 16 panels: the count k_stats_select leaves for the look-ahead kernel and k_syrk_lift
+    bool ident = false;             // "measurement j is landmark j": the Z-building prologue of the look-ahead kernel skips the index map
+    // decisions
+    bool la = false;                // the factorisation is one persistent look-ahead kernel, not one launch per panel (the launch chain)
+    bool chain_only = false;        // ... the chain although the kernel was eligible: its compute units did not come free (la_book), or this is the retry of a stalled launch
+    int zb = 0;                     // the look-ahead kernel builds Z itself: 1 from the output blocks in memory, 2 evaluating them as well, 3 from the propagation kernel's; 0: it reads Z
+    bool build_z = false;           // k_build_Z in front of the factorisation (zb == 0; on a retry: the stalled kernel had built Z in its registers)
+    bool in_prop = false;           // the output blocks are the ones the propagation kernel evaluated (ZB = 3 or k_build_Z<double, true, true>): what me_used counts
+    bool lift_with_syrk = false;    // lift and covariance update are one launch (k_syrk_lift), the lift's workgroups in front
+    bool lift_before_syrk = false;  // EQF_OPT_EARLY_LIFT: Gamma and the lift do not wait for the covariance update (two launches: the lift is the first one)
+    bool syrk_gamma = false;        // the covariance-update kernel produces Gamma = W z as a by-product of its diagonal tiles
+    int early_seq = 0;              // the doorbell sequence the look-ahead kernel rings itself (0: this tail rings no early doorbell)
+    bool sig32 = false, check = false; // Sigma stored as float; finite check behind the tail
+};
+
 // The members of a context are grouped by what a change of capacity (grow_capacity builds a second context and exchanges the two) does with them:
 // CtxOptions and CtxCounters are carried over whole, by one struct assignment each; CtxBuffers stays with the context that made the allocations; everything
 // else in eqf_ctx is state of the filter (moved through the host) or scratch of the buffers (left behind), bar the short list in grow_capacity.
@@ -236,8 +266,7 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     char* d_puby = nullptr;
     int la_njcap = 0, la_seq = 0;
     unsigned long long* d_ladbg = nullptr; // EQF_OPT_TRACE: stamps inside the look-ahead kernel (96 x 8)
-    int early_seq_next = 0, early_armed_seq = 0; // the doorbell sequence the next look-ahead launch carries / the one the launch in flight carries
-    bool early_allowed = false;              // the call in progress can take the early doorbell (eqf_stats_then_update / eqf_stats_select_update)
+    int early_armed_seq = 0;                 // the doorbell sequence the look-ahead launch in flight rings early (door_wait looks for it)
     // An update taken from the early doorbell is UNSETTLED until the lift's doorbell has been seen: the sensor lift is applied, the landmark estimates and their
     // invalid flags (the lift kernel's) are not in yet. settle_update() waits for them; every entry point that needs the device or the estimates settles first,
     // eqf_propagate_fast settles behind its launch.
@@ -246,7 +275,6 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     unsigned settle_gen = 0, settle_epoch = 0, est_epoch = 0; // est_epoch: bumped wherever the cached estimates are dropped (the state moved on)
     std::vector<int> settle_ids;             // the landmark ids at the update
     std::vector<int> invalid_ids;            // ... of which the lift flagged these as invalid (VIO_eqf::removeInvalidLandmarks' test): eqf_remove_invalid_at_update
-    const int* la_live_cols = nullptr;       // EQF_OPT_LIVE_COLUMNS_FIRST: what launch_lookahead passes on
     // eqf_add_landmarks_held: the last n_held landmarks of the state wait for the next eqf_propagate_fast, which passes them through untouched (GatherArgs)
     int n_held = 0;
     double held_var = 0.0;
@@ -260,8 +288,10 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     int pred_star = 0, me_star = 0, me_M = 0;
     unsigned long me_gen = 0;
     bool obs_one_chunk = false;              // the propagation launch in progress carries ALL observer steps of the call (more than kMaxSteps: further k_observer launches follow)
-    bool tail_zb = false;                    // the update tail in flight has no Z in memory (built inside the look-ahead kernel): a retry on the chain builds it first
-    double tail_var = 0.0;                   // ... and needs the measurement variance again
+    // The plan of the update tail in flight (queue_tail; finish_update's retry replaces it with its own). Scratch like the buffers it describes: a tail is never in
+    // flight across grow_capacity, eqf_destroy or the batch bridge's entry into a context - every one of them passes enter() (or sync_ctx), which settles first - so none
+    // of them mentions it.
+    TailPlan tail{};
     int cu_count = 256;                      // compute units of the device: the look-ahead kernel needs all its workgroups resident at once
     std::vector<char> rm_drop;               // eqf_remove_landmarks' scratch
     std::vector<int> rm_ids, rm_map;
@@ -270,8 +300,6 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     bool counted_alive = false;
     int la_cus_held = 0;                     // compute units this context has booked for a look-ahead launch in flight (la_book / la_release)
     int la_selftest = 0;                     // look-ahead self-test at creation: 0 not run (never eligible at this capacity), 1 passed, -1 failed (launch chain only)
-    int tail_M = 0;                          // measurement count of the update tail in flight (finish_update's retry)
-    bool tail_la = false;                    // ... and whether its factorisation was the look-ahead kernel
     int* d_perm = nullptr;                   // 2 x (ncap + 2) row permutations of the NEES elimination fallback
     static constexpr int kRing = 8; // pinned packets of the landmark bookkeeping: a ring, so that a flush need not drain the stream before reusing one
     int ring_pos = 0;
@@ -319,7 +347,6 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     int map_N = -1;
     bool map_all = false;
     bool map_ident = false; // ... and measurement j is landmark j for every j
-    bool tail_ident = false; // ... checked against the ids of the update being launched (launch_update_tail)
     std::vector<std::pair<int, int>> lookup; // sorted (id, index), valid for lookup_gen == lm_gen
     std::vector<int> renum_scratch;
     unsigned lookup_gen = ~0u;
@@ -675,6 +702,7 @@ Cam make_cam(const eqvio_camera* c) {
         k.d[i] = c->dist[i];
     return k;
 }
+bool same_cam(const Cam& x, const Cam& y) { return x.fx == y.fx && x.fy == y.fy && x.cx == y.cx && x.cy == y.cy && x.model == y.model && std::equal(x.d, x.d + 5, y.d); }
 bool camera_ok(const eqvio_camera* c) { return c->model >= EQVIO_CAMERA_PINHOLE && c->model <= EQVIO_CAMERA_EQUIDISTANT; }
 
 // Sensor-level terms of A and B (EqFStateMatrixA_euclid / EqFInputMatrixB_euclid sensor rows and the per-landmark
@@ -1125,6 +1153,12 @@ static int round_sigma(eqf_ctx* c, const int* spec, int spec_seq) {
         return 0;
     const int n = c->n();
     hipLaunchKernelGGL(k_round_f32, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, n, c->ld, c->sigma(), spec, spec_seq, c->opt_f32 == 3 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+static int launch_check_finite(eqf_ctx* c) { // EQF_OPT_CHECK_FINITE: behind a propagation, behind an update tail
+    const int n = c->n();
+    LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2110,8 +2144,7 @@ static int riccati_after_assemble(eqf_ctx* c, double dt, const double* Qdiag12, 
     }
     EQFCHK(round_sigma(c));
     if (c->opt_check) {
-        LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
-        HIPCHK(hipGetLastError());
+        EQFCHK(launch_check_finite(c));
         rc = read_flags(c);
         if (rc)
             return rc;
@@ -2552,13 +2585,18 @@ static int la_split_extra(const eqf_ctx* c, int NJ, int base) {
     const int extra = NJ > LA_SPLIT_FROM + 1 ? 2 * (NJ - LA_SPLIT_FROM) : 0;
     return (c->opt_la_split && base + extra <= c->cu_count) ? extra : 0;
 }
-static int launch_lookahead(eqf_ctx* c, int rows, int m, int ldz, const int* spec, int spec_seq, int zb = 0, const MeasFuse* zb_mf = nullptr) {
+// workgroups a look-ahead launch over m of `rows` rows books: the grid of launch_lookahead in the classic placement (+ 1: the statistics workgroup of the ZB >= 2 forms)
+static int la_workgroups(const eqf_ctx* c, int rows, int m) {
+    const int base = (2 * blocks(m, 32) - 1) + blocks(rows - m, 16);
+    return base + 1 + la_split_extra(c, blocks(m, 32), base);
+}
+// (p: what plan_tail decided - the self-test passes a plan of sizes only)
+static int launch_lookahead(eqf_ctx* c, const TailPlan& p) {
+    const int zb = p.zb;
     LaArgs a{};
-    a.rows = rows;
-    a.m = m;
-    a.ldz = ldz;
-    a.NJ = blocks(m, 32);
-    a.NI = (2 * a.NJ - 1) + blocks(rows - m, 16); // the owner + the S half-rows 2 .. 2 NJ - 1 + the T half-rows (16 rows each)
+    a.rows = p.rows, a.m = p.m, a.ldz = c->ldz;
+    a.NJ = blocks(p.m, 32);
+    a.NI = (2 * a.NJ - 1) + blocks(p.rows - p.m, 16); // the owner + the S half-rows 2 .. 2 NJ - 1 + the T half-rows (16 rows each)
     const int extra = la_split_extra(c, a.NJ, a.NI); // (0 up to 17 panels)
     a.split_from = extra ? LA_SPLIT_FROM : a.NJ;
     a.watch_ahead = c->opt_la_watch_ahead;
@@ -2568,75 +2606,54 @@ static int launch_lookahead(eqf_ctx* c, int rows, int m, int ldz, const int* spe
     // (from 6 panels on, unless forced: the 8 x slots grid costs a small kernel more than the shorter hops give it - N = 50: -2 %, N = 100: +3 %, N = 200: +2.3 %)
     const bool home = c->opt_la_home && a.NJ <= 16 && c->cu_count == 256 && c->d_pubfl &&
                       (c->opt_la_home == 2 || c->la_home_force || (a.NJ >= 6 && device_to_itself(c)));
-    a.home = home ? c->la_home : -1;
-    a.pubfl = c->d_pubfl;
-    const int home_grid = 8 * std::max(2 * a.NJ - 1, blocks(nT + (zb >= 2 ? 1 : 0), 7));
+    // The instantiations, by (MAXT = tiles a wave keeps in registers = ceil(NJ / 4): 4 up to 16 panels | 8, the 17 .. 32-panel form of round 6 - la_row2 + la_build_rows2,
+    // output blocks from memory: ZB = 1 or 3), ZB and HOME. nullptr: there is no such kernel, and the plan never asks for one (ZB = 2 and HOME end at 8 and 16 panels).
+    using LaKernel = void (*)(LaArgs);
+    static const LaKernel kernels[2][4][2] = {
+        {{k_chol_lookahead<4>, k_chol_lookahead<4, 0, true>}, {k_chol_lookahead<4, 1>, k_chol_lookahead<4, 1, true>}, {k_chol_lookahead<4, 2>, k_chol_lookahead<4, 2, true>},
+         {k_chol_lookahead<4, 3>, k_chol_lookahead<4, 3, true>}},
+        {{k_chol_lookahead<8>, nullptr}, {k_chol_lookahead<8, 1>, nullptr}, {nullptr, nullptr}, {k_chol_lookahead<8, 3>, nullptr}}};
+    const LaKernel kernel = kernels[a.NJ > 16 ? 1 : 0][zb][home ? 1 : 0];
+    if (!kernel)
+        return EQF_E_UNSUPPORTED; // (before anything of the context is touched: no sequence number, counter or armed doorbell for a launch that is not made)
+    a.home = home ? c->la_home : -1, a.pubfl = c->d_pubfl;
     if (home)
         ++c->la_home_launches;
     if (++c->la_seq <= 0) // positive: -1 is "no look-ahead launch in front" for k_lift / k_syrk_sub, 0 the initial state of every flag word
         c->la_seq = 1;
     a.seq = c->la_seq;
-    if (c->opt_early_door && c->early_seq_next) { // EQF_OPT_EARLY_DOORBELL: the last T half-row tells the host that the update will be applied (launch_factor_tail set the sequence)
+    if (p.early_seq) { // EQF_OPT_EARLY_DOORBELL: the last T half-row tells the host that the update will be applied
         a.early_cnt = c->d_door + 3, a.early_door = c->h_door + 3, a.early_gamma_host = c->h_res + 7 * (size_t)c->Ncap;
-        a.early_seq = c->early_seq_next, a.early_spec = spec, a.early_spec_seq = spec_seq;
-        c->early_armed_seq = c->early_seq_next;
+        a.early_seq = p.early_seq, a.early_spec = p.spec, a.early_spec_seq = p.spec_seq;
+        c->early_armed_seq = p.early_seq;
     }
-    c->early_seq_next = 0;
     a.timeout_ticks = c->la_timeout_ticks;
-    a.Z = c->d_Z;
-    a.W = c->d_W;
+    a.Z = c->d_Z, a.W = c->d_W, a.gamma = c->d_gamma, a.flags = c->d_flags;
     a.Linv0 = c->d_Linv; // k_build_Z leaves L_0^-1 where step 0 of the launch chain reads it
-    a.pub = c->d_pub;
-    a.pubf = c->d_pubf;
-    a.puby = c->d_puby;
-    a.gamma = c->d_gamma;
-    a.flags = c->d_flags;
-    a.spec = spec;
-    a.spec_seq = spec_seq;
-    a.live_cols = a.NJ <= 16 ? c->la_live_cols : nullptr; // (the instantiations up to 16 panels)
+    a.pub = c->d_pub, a.pubf = c->d_pubf, a.puby = c->d_puby;
+    a.spec = p.spec, a.spec_seq = p.spec_seq, a.live_cols = p.live_cols;
     if (a.live_cols)
         ++c->live_first_launches;
-    a.tr_steps = trace_slot(c, TR_STEP0);
-    a.dbg = c->d_trace ? c->d_ladbg : nullptr;
-    KTimer t(c, KN_CHOL_LOOKAHEAD); // ONE launch: the whole factorisation
-    // MAXT = tiles a wave keeps in registers = ceil(NJ / 4)
+    a.tr_steps = trace_slot(c, TR_STEP0), a.dbg = c->d_trace ? c->d_ladbg : nullptr;
     if (zb) { // EQF_OPT_Z_IN_LOOKAHEAD: the half-rows build their rows of Z themselves
-        const bool large = a.NJ > 16; // round 6: the 17 .. 32-panel form (la_row2 + la_build_rows2; output blocks from memory: zb = 1 or 3)
-        a.zb_sig = (const double*)c->sigma(), a.zb_ld = c->ld, a.zb_M = m / 2, a.zb_Mcap = c->Ncap, a.zb_var = c->tail_var;
+        a.zb_sig = (const double*)c->sigma(), a.zb_ld = c->ld, a.zb_M = p.m / 2, a.zb_Mcap = c->Ncap, a.zb_var = p.meas_var;
         a.zb_C = c->d_C, a.zb_ytil = c->d_ytil, a.zb_lmidx = c->d_lmidx, a.zb_linv0 = c->d_Linv;
         // (the pinned packet's mapping is the one this update was mapped with - map_measurement ran in this call or, for a staged measurement, in stage_prepare)
-        a.zb_ident = (zb != 2 && c->tail_ident) ? 1 : 0;
+        a.zb_ident = (zb != 2 && p.ident) ? 1 : 0;
         a.tr_zb = trace_slot(c, TR_BUILD_Z);
         ++c->zb_launches;
-        if (zb == 2) { // ... and evaluate the C blocks themselves; one more workgroup for the statistics and the speculation word (the kernel itself does not look at it)
-            a.zb_mf = *zb_mf;
+        if (zb >= 2) {
+            // ZB = 2: ... and evaluate the C blocks themselves; one more workgroup for the statistics and the speculation word (the kernel itself does not look at it)
+            // ZB = 3: C, yTilde, index map from the propagation kernel's observer blocks; the statistics workgroup as above
+            // (ZB = 1: C, yTilde, index map from the measurement kernel)
+            a.zb_mf = p.mf;
             a.spec = nullptr;
-            if (home)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 2, true>), dim3(home_grid), dim3(LA_T), 0, c->stream, a);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 2>), dim3(a.NI + 1), dim3(LA_T), 0, c->stream, a);
-        } else if (zb == 3) { // C, yTilde, index map from the propagation kernel's observer blocks; the statistics workgroup as above
-            a.zb_mf = *zb_mf;
-            a.spec = nullptr;
-            if (large)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<8, 3>), dim3(a.NI + extra + 1), dim3(LA_T), 0, c->stream, a);
-            else if (home)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 3, true>), dim3(home_grid), dim3(LA_T), 0, c->stream, a);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 3>), dim3(a.NI + 1), dim3(LA_T), 0, c->stream, a);
-        } else if (large)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<8, 1>), dim3(a.NI + extra), dim3(LA_T), 0, c->stream, a);
-        else if (home) // C, yTilde, index map from the measurement kernel
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 1, true>), dim3(home_grid), dim3(LA_T), 0, c->stream, a);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 1>), dim3(a.NI), dim3(LA_T), 0, c->stream, a);
-    } else if (a.NJ <= 16) {
-        if (home)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4, 0, true>), dim3(home_grid), dim3(LA_T), 0, c->stream, a);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<4>), dim3(a.NI), dim3(LA_T), 0, c->stream, a);
-    } else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_lookahead<8>), dim3(a.NI + extra), dim3(LA_T), 0, c->stream, a);
+        }
+    }
+    // classic placement: the NI workgroups above (+ the split block rows' second workgroups, + the statistics workgroup of ZB >= 2); HOME: 8 x the slots of the fullest XCD
+    const int grid = home ? 8 * std::max(2 * a.NJ - 1, blocks(nT + (zb >= 2 ? 1 : 0), 7)) : a.NI + extra + (zb >= 2 ? 1 : 0);
+    KTimer t(c, KN_CHOL_LOOKAHEAD); // ONE launch: the whole factorisation
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(LA_T), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2718,8 +2735,7 @@ int eqf_output_cov_all(eqf_ctx* c, const eqvio_camera* cam, double* out4N) {
         return 0;
     {
         const Cam k = make_cam(cam);
-        if (c->ocov_valid && k.fx == c->ocov_cam.fx && k.fy == c->ocov_cam.fy && k.cx == c->ocov_cam.cx && k.cy == c->ocov_cam.cy && k.model == c->ocov_cam.model &&
-            std::equal(k.d, k.d + 5, c->ocov_cam.d)) { // computed with the state estimate that was read just before (fetch_estimates); nothing has touched the state since
+        if (c->ocov_valid && same_cam(k, c->ocov_cam)) { // computed with the state estimate that was read just before (fetch_estimates); nothing has touched the state since
             std::memcpy(out4N, c->h_ocov, sizeof(double) * 4 * N);
             return 0;
         }
@@ -2735,6 +2751,49 @@ int eqf_output_cov_all(eqf_ctx* c, const eqvio_camera* cam, double* out4N) {
     return 0;
 }
 
+// The pinned measurement packet takes a new measurement: wait if a kernel may still read the old one, map the ids into it (h_lmidx | measof behind it), copy y.
+// An id without a landmark is, by the caller's choice: an error (map_measurement's require_all); the end of the call (*all_known = false, y NOT copied: nothing is
+// staged or queued for such a measurement); or simply not measured (y copied: the statistics of the others are computed).
+enum UnknownIds { UNKNOWN_IS_ERROR, UNKNOWN_STOPS, UNKNOWN_IS_UNMEASURED };
+// not_mapped (optional): set when the error returned is map_measurement's (ids not ascending, or an unknown id under UNKNOWN_IS_ERROR), not the wait's.
+static int measurement_into_packet(eqf_ctx* c, const int* ids, const double* y, int M, UnknownIds unknown, bool* all_known = nullptr, bool* not_mapped = nullptr) {
+    if (c->busy_meas)
+        EQFCHK(sync_ctx(c));
+    int* lmidx = c->h_lmidx;
+    if (const int rc = map_measurement(c, ids, M, unknown == UNKNOWN_IS_ERROR, lmidx, lmidx + c->Ncap)) {
+        if (not_mapped)
+            *not_mapped = true;
+        return rc;
+    }
+    bool all = true;
+    for (int j = 0; j < M && unknown != UNKNOWN_IS_ERROR; ++j)
+        all = all && (lmidx[j] >= 0);
+    if (all_known)
+        *all_known = all;
+    if (all || unknown == UNKNOWN_IS_UNMEASURED)
+        std::memcpy(c->h_y, y, sizeof(double) * 2 * M);
+    return 0;
+}
+// The one k_outlier_stats launch. ring_door: its last workgroup rings doorbell 0 with door_seq (else the host waits for the stream, or for a kernel behind this one);
+// stats_dev: a copy of the statistics in HBM for k_select_outliers, or nullptr. (The kernel's speculation word is not used: k_build_Z's fused form decides about a tail.)
+static int launch_outlier_stats(eqf_ctx* c, const Cam& cam, const double* ylm, int star, bool ring_door, int door_seq, double thrAbs, double thrProb, int spec_seq, double* stats_dev) {
+    KTimer t(c, KN_STATS);
+    LAUNCH_TS(c, k_outlier_stats, dim3(blocks(c->N, 64)), dim3(64), c->stream, c->N, c->Ncap, c->ld, c->chart, cam, ylm, c->q0(), c->Qq(), c->Qa(), (const TS*)c->sigma(), c->h_res, star,
+              c->d_C, c->d_ytil, c->d_lmidx, c->d_flags, ring_door ? c->d_door : nullptr, c->h_door, door_seq, thrAbs, thrProb, (int*)nullptr, spec_seq, stats_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the three statistics planes of the result packet, to whichever of the caller's arrays are there
+static void copy_stats(const eqf_ctx* c, double* absErr, double* probErr, double* depth2) {
+    const int N = c->N;
+    if (absErr)
+        std::memcpy(absErr, c->h_res, sizeof(double) * N);
+    if (probErr)
+        std::memcpy(probErr, c->h_res + N, sizeof(double) * N);
+    if (depth2)
+        std::memcpy(depth2, c->h_res + 2 * N, sizeof(double) * N);
+}
+
 int eqf_outlier_stats(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const double* y, int M, double* absErr, double* probErr, double* depth2) {
     if (!c || !cam || M < 0 || (M > 0 && (!ids || !y)) || !camera_ok(cam))
         return EQF_E_BAD_ARG;
@@ -2744,79 +2803,30 @@ int eqf_outlier_stats(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const
     EQFCHK(enter(c));
     EQFCHK(fit_measurement(c, M));
     c->staged_valid = c->stage_pending = c->stage_requested = false; // the pinned measurement packet is about to be rewritten
-    if (c->busy_meas) {
-        int r = sync_ctx(c);
-        if (r)
-            return r;
-    }
-    int* lmidx = c->h_lmidx;
-    int* measof = c->h_lmidx + c->Ncap;
-    int rc = map_measurement(c, ids, M, false, lmidx, measof);
-    if (rc)
-        return rc;
-    std::memcpy(c->h_y, y, sizeof(double) * 2 * M);
-    rc = join_observer(c);
-    if (rc)
-        return rc;
-    const bool use_door = c->opt_door && !c->obs_pending;
+    bool all_known = false;
+    EQFCHK(measurement_into_packet(c, ids, y, M, UNKNOWN_IS_UNMEASURED, &all_known));
+    EQFCHK(join_observer(c));
+    const bool use_door = c->opt_door && !c->obs_pending; // (not tail_use_door: no kernel of this call is behind the statistics, the finite check has nothing to look at)
     const int door_seq = (int)(++c->door_seq);
-    {
-        KTimer t(c, KN_STATS);
-        c->busy_meas = true;
-        LAUNCH_TS(c, k_outlier_stats, dim3(blocks(N, 64)), dim3(64), c->stream, N, c->Ncap, c->ld, c->chart, make_cam(cam), pack_by_landmark(c, measof, y), c->q0(), c->Qq(), c->Qa(),
-                  (const TS*)c->sigma(), c->h_res, 1, c->d_C, c->d_ytil, c->d_lmidx, c->d_flags, use_door ? c->d_door : nullptr, c->h_door, door_seq, 0.0, 0.0,
-                  (int*)nullptr, 0, (double*)nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    {
-        bool all_known = true;
-        for (int j = 0; j < M; ++j)
-            all_known = all_known && (lmidx[j] >= 0);
-        c->meas_valid = all_known;
-        c->meas_star = 1;
-        c->meas_ids.assign(ids, ids + M);
-    }
-    rc = use_door ? door_wait(c, 0, door_seq) : sync_ctx(c);
-    if (rc)
-        return rc;
-    if (absErr)
-        std::memcpy(absErr, c->h_res, sizeof(double) * N);
-    if (probErr)
-        std::memcpy(probErr, c->h_res + N, sizeof(double) * N);
-    if (depth2)
-        std::memcpy(depth2, c->h_res + 2 * N, sizeof(double) * N);
+    c->busy_meas = true;
+    EQFCHK(launch_outlier_stats(c, make_cam(cam), pack_by_landmark(c, c->h_lmidx + c->Ncap, y), 1, use_door, door_seq, 0.0, 0.0, 0, nullptr));
+    c->meas_valid = all_known;
+    c->meas_star = 1;
+    c->meas_ids.assign(ids, ids + M);
+    EQFCHK(use_door ? door_wait(c, 0, door_seq) : sync_ctx(c));
+    copy_stats(c, absErr, probErr, depth2);
     return 0;
 }
 
 static int stage_measurement(eqf_ctx* c, const int* ids, const double* y, int M) {
-    if (c->busy_meas) {
-        int r = sync_ctx(c);
-        if (r)
-            return r;
-    }
+    if (c->busy_meas)
+        EQFCHK(sync_ctx(c)); // (here, not only in measurement_into_packet: the staged flags below are dropped once the wait has succeeded)
     c->staged_valid = c->stage_pending = c->stage_requested = false; // the pinned measurement packet is about to be rewritten
-    int* lmidx = c->h_lmidx;
-    int* measof = c->h_lmidx + c->Ncap;
-    int rc = map_measurement(c, ids, M, true, lmidx, measof);
-    if (rc)
-        return rc;
-    std::memcpy(c->h_y, y, sizeof(double) * 2 * M);
+    EQFCHK(measurement_into_packet(c, ids, y, M, UNKNOWN_IS_ERROR));
     c->busy_meas = true;
     return join_observer(c);
 }
 
-// The device part of the vision update behind the measurement stage: Z, factorisation chain, Sigma update, lift. With
-// spec != nullptr every kernel first compares *spec with spec_seq and returns at once if they match (cancelled tail).
-static LiftArgs lift_args(eqf_ctx* c, int discreteCorr, const int* spec, int spec_seq, bool use_door, int door_seq, const double* gpart, int stall_seq) {
-    return LiftArgs{c->N, c->Ncap, c->chart, discreteCorr, c->d_gamma, c->q0(), c->Qq(), c->Qa(), c->h_res + 3 * (size_t)c->Ncap, c->h_res + 7 * (size_t)c->Ncap, c->d_flags,
-                    c->h_resflags, use_door ? c->d_door + 1 : nullptr, c->h_door + 1, door_seq, spec, spec_seq, gpart, c->ld, trace_slot(c, TR_LIFT), stall_seq};
-}
-static int launch_lift(eqf_ctx* c, int discreteCorr, const int* spec, int spec_seq, bool use_door, int door_seq, const double* gpart, int stall_seq) {
-    KTimer t(c, KN_LIFT);
-    hipLaunchKernelGGL(k_lift, dim3(blocks(c->N, 64)), dim3(64), 0, c->stream, lift_args(c, discreteCorr, spec, spec_seq, use_door, door_seq, gpart, stall_seq));
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 // Self-test at context creation (ADVICE r2 / VERDICT r3, r4): the look-ahead kernel's hand-offs rest on relaxed agent-scope flags, write-through stores,
 // s_waitcnt ordering and - EQF_OPT_LA_HOME - on plain stores being visible to the other compute units of one XCD (eqf_lookahead.hpp): measured behaviour of gfx950
 // under ROCm 7.2, not a guarantee of the HIP memory model. Before a context is used, fixed problems [S ; T ; y^T] of up to three shapes - 3 panels, the largest shape up to
@@ -2870,9 +2880,10 @@ static int lookahead_selftest_pass(eqf_ctx* c, bool& placement_refused) {
                     hipLaunchKernelGGL(k_chol_first, dim3(1), dim3(256), 0, c->stream, 32, c->ldz, c->d_Z, c->d_Linv, c->d_flags);
                     if (hipGetLastError() != hipSuccess)
                         return fail(EQF_E_NO_DEVICE);
-                    const int base = (2 * blocks(m, 32) - 1) + blocks(rows - m, 16);
-                    (void)la_book(c, base + 1 + la_split_extra(c, blocks(m, 32), base)); // (result ignored on purpose: a timeout books nothing, the launch is bounded and a stall repeats the attempt)
-                    rc = launch_lookahead(c, rows, m, c->ldz, nullptr, 0);
+                    (void)la_book(c, la_workgroups(c, rows, m)); // (result ignored on purpose: a timeout books nothing, the launch is bounded and a stall repeats the attempt)
+                    TailPlan sizes{}; // Z and L_0^-1 in memory, no speculation, no doorbell
+                    sizes.m = m, sizes.rows = rows;
+                    rc = launch_lookahead(c, sizes);
                 }
                 if (rc)
                     return fail(rc);
@@ -2946,145 +2957,171 @@ static int lookahead_selftest(eqf_ctx* c) {
     c->la_home_launches = 0; // (the self-test's own launches are not the filter's: eqf_lookahead_home counts what eqf_lookahead_stats counts)
     return 0;
 }
-static int launch_factor_tail(eqf_ctx* c, int M, int discreteCorr, const int* spec, int spec_seq, bool use_door, int door_seq, bool force_chain, int zb = 0,
-                              const MeasFuse* zb_mf = nullptr);
-static int launch_update_tail(eqf_ctx* c, const int* ids, int M, double meas_var, int discreteCorr, const int* spec, int spec_seq, bool use_door, int door_seq,
-                              const MeasFuse* fuse = nullptr, bool live_first = false) {
-    HP_SCOPE("abi.launch_update_tail");
-    const int n = c->n(), m = 2 * M;
-    const int rows = m + n + 1;
-    int rc = 0;
-    c->tail_la = false, c->tail_zb = false, c->tail_M = M; // retry state of finish_update: reset before anything of this tail is queued
+// ---------------------------------------------------------------------------------------------------------------- the update tail: one plan, one launch sequence
+// the host waits for the tail on the lift's doorbell: a later kernel (finite check) or the observer stream need the full wait
+static bool tail_use_door(const eqf_ctx* c) { return c->opt_door && !c->opt_check && !c->obs_pending; }
+// What a caller asks of the tail (queue_tail).
+struct TailCall {
+    const int* ids;
+    int M;
+    double meas_var;
+    int discreteCorr;
+    bool use_door; // the host will wait for the lift's doorbell door_seq, not for the stream
+    int door_seq;
+    const MeasFuse* fuse = nullptr; // measurement fusion (the speculative tail), or none
+    bool live_first = false;        // k_stats_select in front of this tail has put the measurements of the landmarks that stay first
+    bool takes_early = false;       // the caller can return on the look-ahead kernel's own doorbell (door_wait(.., &early))
+};
+// Every decision of a tail, from the context's options and state and the call, before the tail's first launch. chain_only: the look-ahead kernel's compute units did
+// not come free (la_book - which waits, and is therefore the caller's: queue_tail).
+static void plan_tail(const eqf_ctx* c, TailPlan& p, const TailCall& call, bool chain_only) {
+    const int M = call.M;
+    const MeasFuse* fuse = call.fuse;
+    p = TailPlan{};
+    p.M = M, p.m = 2 * M, p.n = c->n(), p.rows = p.m + p.n + 1;
+    p.meas_var = call.meas_var, p.discreteCorr = call.discreteCorr, p.use_door = call.use_door, p.door_seq = call.door_seq;
+    if (fuse) // with spec != nullptr every kernel of the tail first compares *spec with spec_seq and returns at once if they match (cancelled tail)
+        p.mf = *fuse, p.spec = fuse->spec_w, p.spec_seq = fuse->spec_seq;
+    p.sig32 = c->sig32, p.check = c->opt_check != 0;
+    const int NJ = blocks(p.m, 32);
     // "measurement j is landmark j" lets the Z-building prologue skip the index map: true only if the mapping in the pinned packet is the one of THESE ids
-    c->tail_ident = c->map_ident && c->map_gen == c->lm_gen && c->map_N == c->N && (int)c->map_ids.size() == M && std::equal(ids, ids + M, c->map_ids.begin());
-    if (live_first) // k_stats_select in front of this tail puts the measurements of the landmarks that stay first: the index map is not the identity
-        c->tail_ident = false;
-    // The look-ahead kernel's workgroups are booked against the device's compute units BEFORE anything of the tail depends on that kernel (who builds Z); if they
-    // do not come free within the bound (la_book), this update takes k_build_Z + the launch chain
-    bool chain_only = false;
-    LaBookingGuard booking{c}; // an error exit below gives the compute units back
-    if (lookahead_eligible(c, m)) {
-        const int base = (2 * blocks(m, 32) - 1) + blocks(rows - m, 16);
-        chain_only = !la_book(c, base + 1 + la_split_extra(c, blocks(m, 32), base));
-        if (chain_only)
-            ++c->la_book_timeouts;
-    }
+    // (k_stats_select in front of this tail puts the measurements of the landmarks that stay first: the index map is not the identity)
+    p.ident = !call.live_first && c->map_ident && c->map_gen == c->lm_gen && c->map_N == c->N && (int)c->map_ids.size() == M && std::equal(call.ids, call.ids + M, c->map_ids.begin());
+    p.live_cols = (call.live_first && NJ <= 16) ? c->d_spec + 2 : nullptr; // (the look-ahead instantiations up to 16 panels, and k_syrk_lift behind them)
+    // one persistent kernel instead of one launch per panel; Gamma complete in d_gamma (chain_only: k_build_Z + the launch chain after all)
+    const bool eligible = lookahead_eligible(c, p.m);
+    p.chain_only = chain_only, p.la = eligible && !chain_only;
     // EQF_OPT_Z_IN_LOOKAHEAD: with the C blocks in memory (k_measure / k_outlier_stats ran), fp64 Sigma and 3 .. 16 panels, the look-ahead kernel builds Z itself
     // (with measurement fusion - the speculative frame tail - it evaluates the C blocks as well, if the measurement has been staged to HBM: ZB = 2)
-    const bool zb_ok = c->opt_zb && !c->sig32 && !chain_only && lookahead_eligible(c, m) && (blocks(m, 32) <= 16 || c->opt_zb_large); // (round 6: 17 .. 32 panels too, la_build_rows2)
+    const bool zb_ok = c->opt_zb && !c->sig32 && !chain_only && eligible && (NJ <= 16 || c->opt_zb_large); // (round 6: 17 .. 32 panels too, la_build_rows2)
     // ZB = 2 up to 8 panels (N <= 128) only: measured +2.8 % at N = 50, +1.8 % at N = 100 and neutral at N = 200, where the tail's first launch then reaches
     // the GPU late
     // ZB = 3 (round 4, up to 16 panels): the propagation kernel's observer blocks have evaluated the output blocks of THIS measurement (staged, same landmark set) with
     // the camera and output choice this call asks for: the look-ahead kernel builds Z from them and one more workgroup computes the statistics
-    auto same_cam = [](const Cam& x, const Cam& y) {
-        return x.fx == y.fx && x.fy == y.fy && x.cx == y.cx && x.cy == y.cy && x.model == y.model && std::equal(x.d, x.d + 5, y.d);
-    };
-    const bool in_prop = fuse && c->me_valid && c->opt_measure_prop && fuse->y == c->d_meas && c->opt_early && c->me_M == M && c->me_gen == c->lm_gen &&
-                         c->me_star == fuse->star && same_cam(c->me_cam, fuse->cam);
-    c->me_valid = false;
-    const int zb = !zb_ok ? 0 : (!fuse ? 1 : (in_prop ? 3 : ((fuse->y == c->d_meas && c->opt_early && blocks(m, 32) <= 8) ? 2 : 0)));
-    if (zb == 3)
-        ++c->me_used;
-    c->tail_zb = zb != 0;
-    c->tail_var = meas_var;
-    if (!zb) {
-        KTimer t(c, KN_BUILD_Z);
-        // one extra grid row eliminates the first diagonal tile of S (no k_chol_first launch in this chain); with measurement fusion
-        // the kernel also evaluates C itself, one more grid row computes the outlier statistics and decides about the tail
-        MeasFuse mf{};
-        if (fuse)
-            mf = *fuse;
-        auto launch = [&](auto kern, auto* sig) {
-            hipLaunchKernelGGL(kern, dim3(blocks(n + M + 1, 256), blocks(M, BZ_JB) + 1 + (mf.enabled ? 1 : 0)), dim3(256), 0, c->stream, n, M, c->Ncap, c->ld, c->ldz, meas_var, c->d_lmidx, sig,
-                               c->d_C, c->d_ytil, c->d_Z, c->d_Linv, c->d_flags, mf.enabled ? (const int*)nullptr : spec, spec_seq, mf, trace_slot(c, TR_BUILD_Z));
-        };
-        if (mf.enabled && in_prop && !c->sig32) { // the propagation kernel has evaluated this measurement's output blocks: nobody evaluates them again
-            ++c->me_used;
-            launch(k_build_Z<double, true, true>, (const double*)c->sigma());
-        } else if (c->sig32) {
-            if (mf.enabled)
-                launch(k_build_Z<float, true>, (const float*)c->sigma());
-            else
-                launch(k_build_Z<float, false>, (const float*)c->sigma());
-        } else {
-            if (mf.enabled)
-                launch(k_build_Z<double, true>, (const double*)c->sigma());
-            else
-                launch(k_build_Z<double, false>, (const double*)c->sigma());
-        }
-        HIPCHK(hipGetLastError());
-    }
-    host_stamp(c, TH_BUILD_Z_OUT);
-    c->tail_M = M; // what a retry of the factorisation on the launch chain needs to know (finish_update)
-    c->la_live_cols = live_first ? c->d_spec + 2 : nullptr;
-    rc = launch_factor_tail(c, M, discreteCorr, spec, spec_seq, use_door, door_seq, chain_only, zb, fuse);
-    c->la_live_cols = nullptr;
-    booking.keep = rc == 0 && c->tail_la; // released by the doorbell wait (door_wait), sync_ctx or eqf_destroy
-    return rc;
-}
-// Everything behind k_build_Z: factorisation of Z (look-ahead kernel or launch chain), lift, covariance update. force_chain: the retry after a stalled
-// look-ahead kernel (Z and L_0^-1 are inputs of that kernel only, so the chain can start from them again).
-static int launch_factor_tail(eqf_ctx* c, int M, int discreteCorr, const int* spec, int spec_seq, bool use_door, int door_seq, bool force_chain, int zb, const MeasFuse* zb_mf) {
-    const int n = c->n(), m = 2 * M;
-    const int rows = m + n + 1;
-    int rc = 0;
-    const bool la = !force_chain && lookahead_eligible(c, m); // one persistent kernel instead of one launch per panel; Gamma complete in d_gamma
-    c->tail_la = la; // the retry state of finish_update always describes the tail in flight (with tail_zb / tail_M / tail_var, set by launch_update_tail)
-    LaBookingGuard booking{c}; // (booked by launch_update_tail, before it decided who builds Z; handed over to the doorbell wait when everything is queued)
-    if (la)
-        ++c->la_launches;
-    c->early_seq_next = (la && use_door && c->early_allowed && c->opt_early && c->opt_lift_syrk && !c->sig32 && c->opt_timing != 1 && !c->opt_check) ? door_seq : 0;
-    c->early_allowed = false;
-    rc = la ? launch_lookahead(c, rows, m, c->ldz, spec, spec_seq, zb, zb_mf) : launch_chain(c, rows, m, c->ldz, c->d_Z, c->d_W, true, spec, spec_seq, c->opt_early ? c->d_gpart : nullptr);
-    if (rc)
-        return rc;
-    booking.keep = la;
-    const int stall_seq = la ? c->la_seq : -1; // the stall word the kernels behind the factorisation compare (sequence valued: eqf_lookahead.hpp)
+    p.in_prop = fuse && c->me_valid && c->opt_measure_prop && fuse->y == c->d_meas && c->opt_early && c->me_M == M && c->me_gen == c->lm_gen && c->me_star == fuse->star &&
+                same_cam(c->me_cam, fuse->cam) && !c->sig32;
+    p.zb = !zb_ok ? 0 : (!fuse ? 1 : (p.in_prop ? 3 : ((fuse->y == c->d_meas && c->opt_early && NJ <= 8) ? 2 : 0)));
+    p.build_z = p.zb == 0;
     // EQF_OPT_LIFT_WITH_SYRK: lift and covariance update wait for the same kernel and touch different data - one launch, the lift's workgroups in front
     // (not with per-kernel timing, which wants the two spans apart, and not with fp32 storage, whose rounding pass follows the covariance update)
-    if (c->opt_early && c->opt_lift_syrk && !c->sig32 && c->opt_timing != 1 && c->N > 0) {
-        const int nt = blocks(n, 32), nlift = blocks(c->N, 64);
-        KTimer t(c, KN_SYRK);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_syrk_lift<double>), dim3(nlift + nt * (nt + 1) / 2), dim3(64 * SYRK_NW), 0, c->stream, n, m, c->ld, c->ldz, c->d_W, (double*)c->sigma(),
-                           c->d_gamma, c->d_flags, trace_slot(c, TR_SYRK), c->d_syrk_order + c->syrk_off[nt], lift_args(c, discreteCorr, spec, spec_seq, use_door, door_seq, la ? nullptr : c->d_gpart, stall_seq),
-                           nlift, blocks(m, 32) <= 16 ? c->la_live_cols : (const int*)nullptr, nt <= SYRK_ARITH_TILES ? nt : 0);
-        HIPCHK(hipGetLastError());
-        EQFCHK(round_sigma(c, spec, spec_seq));
-        if (c->opt_check) {
-            LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
-            HIPCHK(hipGetLastError());
-        }
-        return 0;
-    }
-    if (c->opt_early) { // Gamma, landmark lift, result packet and doorbell BEFORE the covariance update: the host round trip overlaps with it
-        rc = launch_lift(c, discreteCorr, spec, spec_seq, use_door, door_seq, la ? nullptr : c->d_gpart, stall_seq);
-        if (rc)
-            return rc;
-    }
-    {
-        const int nt = blocks(n, 32);
-        KTimer t(c, KN_SYRK);
-        const dim3 sg(nt * (nt + 1) / 2), sb(64 * SYRK_NW);
-#define SYRK_LAUNCH(TS_, G_) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_syrk_sub<TS_, G_>), sg, sb, 0, c->stream, n, m, c->ld, c->ldz, c->d_W, (TS_*)c->sigma(), nt, c->d_gamma, spec, spec_seq, G_ ? 1 : 0, c->d_flags, \
-                       trace_slot(c, TR_SYRK), c->d_syrk_order + c->syrk_off[nt], stall_seq)
-        const bool wg = !(c->opt_early || la); // EQF_OPT_EARLY_LIFT = 0 on the launch chain: Gamma = W z is a by-product of the diagonal tiles
-        if (c->sig32) { if (wg) SYRK_LAUNCH(float, true); else SYRK_LAUNCH(float, false); }
-        else { if (wg) SYRK_LAUNCH(double, true); else SYRK_LAUNCH(double, false); }
-#undef SYRK_LAUNCH
-        HIPCHK(hipGetLastError());
-    }
-    EQFCHK(round_sigma(c, spec, spec_seq));
-    if (!c->opt_early) {
-        rc = launch_lift(c, discreteCorr, spec, spec_seq, use_door, door_seq, nullptr, stall_seq);
-        if (rc)
-            return rc;
-    }
-    if (c->opt_check) {
-        LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
-        HIPCHK(hipGetLastError());
-    }
+    const bool lift_can_ride = c->opt_early && c->opt_lift_syrk && !c->sig32 && c->opt_timing != 1;
+    // ... and then the look-ahead kernel can announce the update a kernel boundary ahead of the lift, unless the host has to wait for a kernel behind the lift anyway (finite check)
+    const bool early_door_ok = lift_can_ride && !c->opt_check;
+    p.lift_with_syrk = lift_can_ride && c->N > 0;
+    p.lift_before_syrk = c->opt_early != 0; // Gamma, landmark lift, result packet and doorbell BEFORE the covariance update: the host round trip overlaps with it
+    p.syrk_gamma = !(p.lift_before_syrk || p.la); // EQF_OPT_EARLY_LIFT = 0 on the launch chain: Gamma = W z is a by-product of the diagonal tiles
+    // EQF_OPT_EARLY_DOORBELL: the last T half-row tells the host that the update will be applied
+    p.early_seq = (p.la && call.use_door && call.takes_early && c->opt_early_door && early_door_ok) ? call.door_seq : 0;
+}
+// The plan of the retry after a stalled look-ahead launch (finish_update): same sizes, the launch chain forced, no speculation, no fusion, no early doorbell, a
+// new door sequence. Z and L_0^-1 are inputs of the look-ahead kernel only, so the chain can start from them again - unless the stalled kernel had built Z in its
+// registers: then the chain needs it (and L_0^-1) in memory first.
+static TailPlan retry_plan(const TailPlan& stalled, bool use_door, int door_seq) {
+    TailPlan p = stalled;
+    p.use_door = use_door, p.door_seq = door_seq;
+    p.spec = nullptr, p.spec_seq = 0, p.mf = MeasFuse{};
+    p.live_cols = nullptr; // (the chain factorises every panel)
+    p.la = false, p.chain_only = true, p.early_seq = 0;
+    p.build_z = stalled.zb != 0, p.zb = 0, p.in_prop = false;
+    p.syrk_gamma = !p.lift_before_syrk;
+    return p;
+}
+static LiftArgs lift_args(eqf_ctx* c, const TailPlan& p, const double* gpart, int stall_seq) {
+    return LiftArgs{c->N, c->Ncap, c->chart, p.discreteCorr, c->d_gamma, c->q0(), c->Qq(), c->Qa(), c->h_res + 3 * (size_t)c->Ncap, c->h_res + 7 * (size_t)c->Ncap, c->d_flags,
+                    c->h_resflags, p.use_door ? c->d_door + 1 : nullptr, c->h_door + 1, p.door_seq, p.spec, p.spec_seq, gpart, c->ld, trace_slot(c, TR_LIFT), stall_seq};
+}
+static int launch_lift(eqf_ctx* c, const TailPlan& p, const double* gpart, int stall_seq) {
+    KTimer t(c, KN_LIFT);
+    hipLaunchKernelGGL(k_lift, dim3(blocks(c->N, 64)), dim3(64), 0, c->stream, lift_args(c, p, gpart, stall_seq));
+    HIPCHK(hipGetLastError());
     return 0;
+}
+// Z = [S ; T ; yTilde^T] in memory, for the launch chain or a look-ahead launch that does not build it itself.
+// One extra grid row eliminates the first diagonal tile of S (no k_chol_first launch in this chain); with measurement fusion
+// the kernel also evaluates C itself, one more grid row computes the outlier statistics and decides about the tail
+static int launch_build_Z(eqf_ctx* c, const TailPlan& p) {
+    KTimer t(c, KN_BUILD_Z);
+    const bool fused = p.mf.enabled != 0;
+    auto launch = [&](auto kern, auto* sig) {
+        hipLaunchKernelGGL(kern, dim3(blocks(p.n + p.M + 1, 256), blocks(p.M, BZ_JB) + 1 + (fused ? 1 : 0)), dim3(256), 0, c->stream, p.n, p.M, c->Ncap, c->ld, c->ldz, p.meas_var, c->d_lmidx, sig,
+                           c->d_C, c->d_ytil, c->d_Z, c->d_Linv, c->d_flags, fused ? (const int*)nullptr : p.spec, p.spec_seq, p.mf, trace_slot(c, TR_BUILD_Z));
+    };
+    if (p.in_prop) // the propagation kernel has evaluated this measurement's output blocks: nobody evaluates them again
+        launch(k_build_Z<double, true, true>, (const double*)c->sigma());
+    else if (p.sig32 && fused)
+        launch(k_build_Z<float, true>, (const float*)c->sigma());
+    else if (p.sig32)
+        launch(k_build_Z<float, false>, (const float*)c->sigma());
+    else if (fused)
+        launch(k_build_Z<double, true>, (const double*)c->sigma());
+    else
+        launch(k_build_Z<double, false>, (const double*)c->sigma());
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// The device part of the vision update behind the measurement stage, straight from the plan: Z (unless the look-ahead kernel builds it), the factorisation (look-ahead
+// kernel or launch chain), lift and covariance update in the planned order, rounding pass, finite check.
+static int launch_tail(eqf_ctx* c, const TailPlan& p) {
+    LaBookingGuard booking{c}; // (booked by queue_tail, before the plan decided who builds Z) an error exit below gives the compute units back
+    if (p.in_prop)
+        ++c->me_used;
+    if (p.build_z)
+        EQFCHK(launch_build_Z(c, p));
+    host_stamp(c, TH_BUILD_Z_OUT);
+    if (p.la) {
+        ++c->la_launches;
+        EQFCHK(launch_lookahead(c, p));
+    } else
+        EQFCHK(launch_chain(c, p.rows, p.m, c->ldz, c->d_Z, c->d_W, true, p.spec, p.spec_seq, p.lift_before_syrk ? c->d_gpart : nullptr));
+    const int stall_seq = p.la ? c->la_seq : -1; // the stall word the kernels behind the factorisation compare (sequence valued: eqf_lookahead.hpp)
+    const double* gpart = p.la ? nullptr : c->d_gpart; // (the look-ahead kernel leaves Gamma complete, the chain as partial vectors)
+    const int nt = blocks(p.n, 32);
+    if (p.lift_with_syrk) {
+        const int nlift = blocks(c->N, 64);
+        KTimer t(c, KN_SYRK);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_syrk_lift<double>), dim3(nlift + nt * (nt + 1) / 2), dim3(64 * SYRK_NW), 0, c->stream, p.n, p.m, c->ld, c->ldz, c->d_W, (double*)c->sigma(),
+                           c->d_gamma, c->d_flags, trace_slot(c, TR_SYRK), c->d_syrk_order + c->syrk_off[nt], lift_args(c, p, gpart, stall_seq), nlift, p.live_cols, nt <= SYRK_ARITH_TILES ? nt : 0);
+        HIPCHK(hipGetLastError());
+    } else {
+        if (p.lift_before_syrk)
+            EQFCHK(launch_lift(c, p, gpart, stall_seq));
+        KTimer t(c, KN_SYRK);
+        auto launch = [&](auto kern, auto* sig) {
+            hipLaunchKernelGGL(kern, dim3(nt * (nt + 1) / 2), dim3(64 * SYRK_NW), 0, c->stream, p.n, p.m, c->ld, c->ldz, c->d_W, sig, nt, c->d_gamma, p.spec, p.spec_seq, p.syrk_gamma ? 1 : 0, c->d_flags,
+                               trace_slot(c, TR_SYRK), c->d_syrk_order + c->syrk_off[nt], stall_seq);
+        };
+        if (p.sig32 && p.syrk_gamma)
+            launch(k_syrk_sub<float, true>, (float*)c->sigma());
+        else if (p.sig32)
+            launch(k_syrk_sub<float, false>, (float*)c->sigma());
+        else if (p.syrk_gamma)
+            launch(k_syrk_sub<double, true>, (double*)c->sigma());
+        else
+            launch(k_syrk_sub<double, false>, (double*)c->sigma());
+        HIPCHK(hipGetLastError());
+    }
+    EQFCHK(round_sigma(c, p.spec, p.spec_seq));
+    if (!p.lift_with_syrk && !p.lift_before_syrk)
+        EQFCHK(launch_lift(c, p, nullptr, stall_seq));
+    if (p.check)
+        EQFCHK(launch_check_finite(c));
+    booking.keep = p.la; // a look-ahead launch is in flight: released by the doorbell wait (door_wait), sync_ctx or eqf_destroy
+    return 0;
+}
+// Books the look-ahead kernel's workgroups, plans the tail into the context (c->tail: the tail in flight) and launches it.
+static int queue_tail(eqf_ctx* c, const TailCall& call) {
+    HP_SCOPE("abi.queue_tail");
+    // The look-ahead kernel's workgroups are booked against the device's compute units BEFORE anything of the tail depends on that kernel (who builds Z); if they
+    // do not come free within the bound (la_book), this update takes k_build_Z + the launch chain
+    bool chain_only = false;
+    if (lookahead_eligible(c, 2 * call.M)) {
+        chain_only = !la_book(c, la_workgroups(c, 2 * call.M + c->n() + 1, 2 * call.M));
+        if (chain_only)
+            ++c->la_book_timeouts;
+    }
+    plan_tail(c, c->tail, call, chain_only);
+    c->me_valid = false; // (the plan has looked at the propagation kernel's output blocks: they are this measurement's or nobody's)
+    return launch_tail(c, c->tail);
 }
 // Host part after the wait: the lift kernel wrote Gamma's sensor part, the new estimates / invalid flags (4N) and the status
 // flags straight into the pinned result packet; the sensor part of Delta is lifted here.
@@ -3098,7 +3135,7 @@ static int finish_update(eqf_ctx* c, int discreteCorr, bool retried = false) {
     // k_syrk_sub), the sensor lift below is not applied.
     // (round 5, found by the concurrent time-out soak: a launch that gives up half way may ALSO have raised the pivot flag - its pivot wave goes on eliminating
     // whatever is in its LDS until it notices - so the pivot flag of a stalled launch says nothing; the chain decides, from a cleared flag)
-    if (c->h_resflags[3] && c->tail_la && !retried) {
+    if (c->h_resflags[3] && c->tail.la && !retried) {
         // A bounded wait of the look-ahead kernel ran out: its workgroups were not all resident within the bound (another process or a long kernel
         // of this process holds the CUs). Nothing of the filter was modified, and Z / L_0^-1 are inputs of that kernel only: redo the factorisation
         // on the launch chain (which needs no co-residency), then lift and update Sigma as usual. Three stalls in a row switch the look-ahead
@@ -3118,32 +3155,22 @@ static int finish_update(eqf_ctx* c, int discreteCorr, bool retried = false) {
             c->opt_lookahead = 0;
         HIPCHK(hipMemsetAsync(c->d_flags + 3, 0, sizeof(int), c->stream));
         HIPCHK(hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
-        const bool use_door = c->opt_door && !c->opt_check && !c->obs_pending;
+        const bool use_door = tail_use_door(c);
         const int door_seq = (int)(++c->door_seq);
-        if (c->tail_zb) { // the stalled kernel had built Z in its registers: the chain needs it (and L_0^-1) in memory
-            const int n_ = c->n(), M_ = c->tail_M;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_build_Z<double, false>), dim3(blocks(n_ + M_ + 1, 256), blocks(M_, BZ_JB) + 1), dim3(256), 0, c->stream, n_, M_, c->Ncap, c->ld, c->ldz,
-                               c->tail_var, c->d_lmidx, (const double*)c->sigma(), c->d_C, c->d_ytil, c->d_Z, c->d_Linv, c->d_flags, (const int*)nullptr, 0, MeasFuse{}, (trace_t*)nullptr);
-            HIPCHK(hipGetLastError());
-            c->tail_zb = false;
-        }
-        int rc = launch_factor_tail(c, c->tail_M, discreteCorr, nullptr, 0, use_door, door_seq, true);
-        if (rc)
-            return rc;
-        rc = use_door ? door_wait(c, 1, door_seq) : sync_ctx(c);
-        if (rc)
-            return rc;
+        c->tail = retry_plan(c->tail, use_door, door_seq); // (the tail in flight is the retry from here on)
+        EQFCHK(launch_tail(c, c->tail));
+        EQFCHK(use_door ? door_wait(c, 1, door_seq) : sync_ctx(c));
         return finish_update(c, discreteCorr, true);
     }
     if (c->h_resflags[3] || c->h_flags[0]) {
         if (std::getenv("EQF_DEBUG_STATS"))
-            std::fprintf(stderr, "[eqf_hip] update failed: retried %d tail_la %d tail_zb %d resflags %d %d %d %d la_seq %d\n", (int)retried, (int)c->tail_la, (int)c->tail_zb, c->h_resflags[0],
+            std::fprintf(stderr, "[eqf_hip] update failed: retried %d look-ahead %d zb %d resflags %d %d %d %d la_seq %d\n", (int)retried, (int)c->tail.la, c->tail.zb, c->h_resflags[0],
                          c->h_resflags[1], c->h_resflags[2], c->h_resflags[3], c->la_seq);
         c->est_valid = false, ++c->est_epoch;
         c->meas_valid = false;
         return c->h_resflags[3] ? EQF_E_STALLED : EQF_E_NOT_SPD;
     }
-    if (c->tail_la)
+    if (c->tail.la)
         c->la_consecutive_stalls = 0;
     c->gamma_stale = true;
     c->n_at_update = n;
@@ -3156,7 +3183,7 @@ static int finish_update(eqf_ctx* c, int discreteCorr, bool retried = false) {
 // now; the landmark estimates and their invalid flags come with the lift's doorbell (settle_update).
 static int finish_update_early(eqf_ctx* c, int discreteCorr, int seq) {
     c->h_flags[0] = c->h_flags[1] = 0;
-    if (c->tail_la)
+    if (c->tail.la)
         c->la_consecutive_stalls = 0;
     c->gamma_stale = true;
     c->n_at_update = c->n();
@@ -3261,12 +3288,8 @@ int eqf_vision_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const
     EQFCHK(enter(c));
     const bool reuse = c->meas_valid && c->meas_star == (useEqv ? 1 : 0) && (int)c->meas_ids.size() == M && std::equal(ids, ids + M, c->meas_ids.begin()) &&
                        std::memcmp(c->h_y, y, sizeof(double) * 2 * M) == 0;
-    int rc = 0;
-    if (!reuse) {
-        rc = stage_measurement(c, ids, y, M);
-        if (rc)
-            return rc;
-    }
+    if (!reuse)
+        EQFCHK(stage_measurement(c, ids, y, M));
     c->meas_valid = false;
     if (!reuse) {
         KTimer t(c, KN_MEASURE);
@@ -3274,14 +3297,11 @@ int eqf_vision_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const
                            c->Qa(), c->d_C, c->d_ytil, c->d_lmidx, c->d_flags);
         HIPCHK(hipGetLastError());
     }
-    const bool use_door = c->opt_door && !c->opt_check && !c->obs_pending; // a later kernel (finite check) or the observer stream need the full wait
+    const bool use_door = tail_use_door(c);
     const int door_seq = (int)(++c->door_seq);
-    rc = launch_update_tail(c, ids, M, meas_var, discreteCorr, nullptr, 0, use_door, door_seq);
-    if (rc)
-        return rc;
-    rc = use_door ? door_wait(c, 1, door_seq) : sync_ctx(c);
-    if (rc)
-        return rc;
+    TailCall call{ids, M, meas_var, discreteCorr, use_door, door_seq};
+    EQFCHK(queue_tail(c, call));
+    EQFCHK(use_door ? door_wait(c, 1, door_seq) : sync_ctx(c));
     return finish_update(c, discreteCorr);
 }
 
@@ -3309,29 +3329,142 @@ static int stage_prepare(eqf_ctx* c) {
     const int M = c->staged_M;
     if (c->N == 0 || M > c->N)
         return 0;
-    if (c->busy_meas) {
-        int r = sync_ctx(c);
-        if (r)
-            return r;
-    }
-    int* lmidx = c->h_lmidx;
-    int* measof = c->h_lmidx + c->Ncap;
-    const int rc = map_measurement(c, c->staged_ids.data(), M, false, lmidx, measof);
-    if (rc)
+    bool all_known = false, not_mapped = false;
+    const int rc = measurement_into_packet(c, c->staged_ids.data(), c->staged_y.data(), M, UNKNOWN_STOPS, &all_known, &not_mapped);
+    if (not_mapped)
         return 0; // ids not ascending: the update call will report it
-    for (int j = 0; j < M; ++j)
-        if (lmidx[j] < 0)
-            return 0; // an id without a landmark: nothing staged, the update call takes its ordinary route
-    std::memcpy(c->h_y, c->staged_y.data(), sizeof(double) * 2 * M);
-    pack_by_landmark(c, measof, c->staged_y.data());
+    if (rc)
+        return rc;
+    if (!all_known)
+        return 0; // an id without a landmark: nothing staged, the update call takes its ordinary route
+    pack_by_landmark(c, c->h_lmidx + c->Ncap, c->staged_y.data());
     c->staged_gen = c->lm_gen;
     c->stage_pending = true;
     return 0;
 }
 
+// What stats_then_update (below) hands to one of its three routes: the call's arguments and what its prologue found.
+struct StatsCall {
+    const eqvio_camera* cam;
+    const int* ids;
+    const double* y;
+    int M, useEqv, discreteCorr, max_outliers;
+    double thrAbs, thrProb, meas_var;
+    double *absErr, *probErr, *depth2;
+    int *updated, *removed_idx, *n_removed;
+    bool same_as_staged; // the pinned packet already holds this measurement, mapped and packed by stage_prepare (and the propagation kernel has copied it to HBM)
+    bool use_door;
+    int seq;             // the doorbell sequence of this call (and the speculation sequence of its tail)
+};
+// The epilogue of the two routes that update, in two halves (the routes count and look at the cancellation word in between): wait on the doorbells or the stream
+// and copy the statistics out ...
+static int await_tail(eqf_ctx* c, const StatsCall& s, bool* early) {
+    host_stamp(c, TH_TAIL_OUT);
+    *early = false;
+    EQFCHK(s.use_door ? door_wait(c, 1, s.seq, early) : sync_ctx(c));
+    copy_stats(c, s.absErr, s.probErr, s.depth2);
+    return 0;
+}
+// ... and apply the update, from whichever doorbell announced it
+static int apply_tail(eqf_ctx* c, const StatsCall& s, bool early) {
+    EQFCHK(early ? finish_update_early(c, s.discreteCorr, s.seq) : finish_update(c, s.discreteCorr));
+    *s.updated = 1;
+    return 0;
+}
+// Route 1, the device-side decision. Outlier candidates frame after frame (speculation has backed off): statistics, the outlier decision (k_select_outliers: the
+// discarded landmarks' measurements are masked out of C) and the whole update queued at once, ONE host wait. The discarded landmarks leave the
+// state after the update (an unmeasured landmark can be marginalised before or after it).
+static int stats_select_route(eqf_ctx* c, const StatsCall& s) {
+    const int N = c->N, M = s.M;
+    const int* measof = c->h_lmidx + c->Ncap;
+    // EQF_OPT_LIVE_COLUMNS_FIRST: up to 16 panels the look-ahead kernel ends with the last panel that holds a column of a landmark that stays (k_stats_select orders them)
+    const bool live_first = N <= SEL_ONE_WG && c->opt_sel_one && c->opt_live_first && blocks(2 * M, 32) <= 16 && blocks(2 * M, 32) >= 3;
+    if (N <= SEL_ONE_WG && c->opt_sel_one) { // statistics and decision as one launch of one workgroup
+        KTimer t(c, KN_STATS);
+        LAUNCH_TS(c, k_stats_select, dim3(1), dim3(512), c->stream, N, c->Ncap, c->ld, c->chart, make_cam(s.cam),
+                  s.same_as_staged ? (const double*)(c->d_meas + 2 * (size_t)c->Ncap) /* the staged copy in HBM: no PCIe round trip in front of the statistics */ : pack_by_landmark(c, measof, s.y), c->q0(), c->Qq(), c->Qa(),
+                  (const TS*)c->sigma(), c->h_res, s.useEqv ? 1 : 0, c->d_C, c->d_ytil, c->d_lmidx, c->d_flags, s.thrAbs, s.thrProb, s.max_outliers, M, c->h_sel, live_first ? c->d_spec + 2 : (int*)nullptr);
+        HIPCHK(hipGetLastError());
+    } else {
+        EQFCHK(launch_outlier_stats(c, make_cam(s.cam), s.same_as_staged ? (const double*)c->h_ylm : pack_by_landmark(c, measof, s.y), s.useEqv ? 1 : 0, /* ring_door */ false, s.seq, s.thrAbs, s.thrProb, s.seq, c->d_stats));
+        hipLaunchKernelGGL(k_select_outliers, dim3(1), dim3(256), 0, c->stream, N, c->Ncap, M, c->d_stats, s.thrAbs, s.thrProb, s.max_outliers, c->d_lmidx, c->d_C, c->d_ytil, c->h_sel);
+        HIPCHK(hipGetLastError());
+    }
+    c->meas_valid = false;
+    TailCall call{s.ids, M, s.meas_var, s.discreteCorr, s.use_door, s.seq};
+    call.live_first = live_first, call.takes_early = true;
+    EQFCHK(queue_tail(c, call));
+    bool early;
+    EQFCHK(await_tail(c, s, &early));
+    ++c->sel_frames;
+    if (c->h_sel[c->Ncap] == 0) // a frame without an outlier candidate ends the back-off
+        c->spec_backoff = c->spec_backoff_len = 0;
+    EQFCHK(apply_tail(c, s, early));
+    std::vector<int> idx;
+    for (int i = 0; i < N; ++i)
+        if (c->h_sel[i])
+            idx.push_back(i);
+    if (s.n_removed)
+        *s.n_removed = (int)idx.size();
+    if (s.removed_idx)
+        std::copy(idx.begin(), idx.end(), s.removed_idx);
+    c->sel_discarded += (long)idx.size();
+    return idx.empty() ? 0 : eqf_remove_landmarks(c, idx.data(), (int)idx.size());
+}
+// Route 2, a plain statistics call: the caller decides and calls eqf_vision_update
+static int stats_only_route(eqf_ctx* c, const StatsCall& s) {
+    const int N = c->N;
+    EQFCHK(launch_outlier_stats(c, make_cam(s.cam), s.same_as_staged ? (const double*)c->h_ylm : pack_by_landmark(c, c->h_lmidx + c->Ncap, s.y), s.useEqv ? 1 : 0, s.use_door, s.seq, s.thrAbs, s.thrProb,
+                                s.seq, nullptr));
+    c->meas_valid = true;
+    EQFCHK(s.use_door ? door_wait(c, 0, s.seq) : sync_ctx(c));
+    copy_stats(c, s.absErr, s.probErr, s.depth2);
+    bool candidate = false; // a frame without an outlier candidate ends the back-off
+    for (int i = 0; i < N && !candidate; ++i)
+        candidate = c->h_res[i] > s.thrAbs || c->h_res[N + i] > s.thrProb;
+    if (!candidate)
+        c->spec_backoff = c->spec_backoff_len = 0;
+    return 0;
+}
+// Route 3, the speculative tail: measurement, statistics and Z in ONE kernel (k_build_Z with measurement fusion), then the factorisation,
+// the lift and the covariance update, all queued at once. An outlier candidate cancels everything behind the first kernel.
+static int stats_speculative_route(eqf_ctx* c, const StatsCall& s) {
+    MeasFuse mf{};
+    mf.enabled = 1;
+    mf.N = c->N, mf.Ncap = c->Ncap, mf.chart = c->chart, mf.star = s.useEqv ? 1 : 0;
+    mf.cam = make_cam(s.cam);
+    if (s.same_as_staged) // the kernels read the measurement from its copy in HBM
+        mf.y = c->d_meas, mf.lmidx = c->d_meas_idx, mf.ylm = c->d_meas + 2 * (size_t)c->Ncap;
+    else
+        mf.y = c->h_y, mf.lmidx = c->h_lmidx, mf.ylm = pack_by_landmark(c, c->h_lmidx + c->Ncap, s.y);
+    mf.q0 = c->q0(), mf.Qq = c->Qq(), mf.Qa = c->Qa();
+    mf.out = c->h_res;
+    mf.C = c->d_C, mf.ytil = c->d_ytil, mf.lmidx_dev = c->d_lmidx;
+    mf.thrAbs = s.thrAbs, mf.thrProb = s.thrProb;
+    mf.spec_w = c->d_spec, mf.spec_seq = s.seq;
+    c->meas_valid = false; // consumed by the tail below (restored if the tail is cancelled)
+    TailCall call{s.ids, s.M, s.meas_var, s.discreteCorr, s.use_door, s.seq};
+    call.fuse = &mf, call.takes_early = true;
+    EQFCHK(queue_tail(c, call));
+    bool early;
+    EQFCHK(await_tail(c, s, &early));
+    ++c->spec_queued;
+    if (!early && c->h_resflags[2]) { // cancelled on the device: nothing was modified, C / residuals of the statistics kernel are still valid (the early doorbell does not ring for a cancelled tail)
+        ++c->spec_cancelled;
+        // (up to 256 frames when the caller lets the device take the outlier decision: a frame with candidates then costs one round trip anyway, a cancelled tail two and a wasted
+        //  launch sequence - with candidates in nearly every frame, the shipped thresholds, the cap of 16 wasted a tail every 17th frame)
+        c->spec_backoff_len = std::min(s.max_outliers >= 0 ? 256 : 16, std::max(1, 2 * c->spec_backoff_len));
+        c->spec_backoff = c->spec_backoff_len;
+        c->meas_valid = true;
+        return 0;
+    }
+    c->spec_backoff = c->spec_backoff_len = 0;
+    return apply_tail(c, s, early);
+}
 // See include/eqf_hip.h. Statistics and update queued back to back; the statistics kernel cancels the tail on the device if
 // the host has an outlier decision to make.
 // max_outliers < 0: the caller decides about outliers itself (eqf_stats_then_update); >= 0: eqf_stats_select_update
+// The prologue every such call shares; it picks one of the three routes above.
 static int stats_then_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const double* y, int M, double thrAbs, double thrProb, double meas_var, int useEqv,
                              int discreteCorr, double* absErr, double* probErr, double* depth2, int* updated, int max_outliers, int* removed_idx, int* n_removed) {
     HP_SCOPE("abi.stats_then_update");
@@ -3357,164 +3490,29 @@ static int stats_then_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids
         --c->spec_backoff;
         speculate = false;
     }
-    const bool use_door = c->opt_door && !c->opt_check && !c->obs_pending;
+    StatsCall s{cam, ids, y, M, useEqv, discreteCorr, max_outliers, thrAbs, thrProb, meas_var, absErr, probErr, depth2, updated, removed_idx, n_removed, false, tail_use_door(c), 0};
     // staged by eqf_stage_measurement and copied to HBM by the propagation kernel: same measurement, same landmark set?
     // (the pinned packet holds exactly this measurement, mapped and packed by stage_prepare: nothing to rewrite - and no wait for the propagation kernel's staging block,
     //  which may still be reading it - whichever route the frame takes)
-    const bool same_as_staged = c->staged_valid && c->staged_gen == c->lm_gen && c->staged_M == M && std::equal(ids, ids + M, c->staged_ids.begin()) &&
-                                std::memcmp(c->staged_y.data(), y, sizeof(double) * 2 * M) == 0;
-    const bool staged = speculate && same_as_staged;
+    s.same_as_staged = c->staged_valid && c->staged_gen == c->lm_gen && c->staged_M == M && std::equal(ids, ids + M, c->staged_ids.begin()) &&
+                       std::memcmp(c->staged_y.data(), y, sizeof(double) * 2 * M) == 0;
     c->staged_valid = c->stage_pending = c->stage_requested = false;
-    int* lmidx = c->h_lmidx;
-    int* measof = c->h_lmidx + c->Ncap;
-    int rc = 0;
-    if (!same_as_staged) {
-        if (c->busy_meas) {
-            int r = sync_ctx(c);
-            if (r)
-                return r;
+    if (!s.same_as_staged) {
+        bool all_known = false;
+        EQFCHK(measurement_into_packet(c, ids, y, M, UNKNOWN_STOPS, &all_known));
+        if (!all_known) { // a measurement without a landmark: the caller adds landmarks first (VIOFilter.cpp:217), nothing queued
+            *updated = -1;
+            return 0;
         }
-        rc = map_measurement(c, ids, M, false, lmidx, measof);
-        if (rc)
-            return rc;
-        for (int j = 0; j < M; ++j)
-            if (lmidx[j] < 0) { // a measurement without a landmark: the caller adds landmarks first (VIOFilter.cpp:217), nothing queued
-                *updated = -1;
-                return 0;
-            }
-        std::memcpy(c->h_y, y, sizeof(double) * 2 * M);
     }
     HP_SCOPE("stu.after_map");
-    const int seq = (int)(++c->door_seq);
-    auto copy_stats = [&]() {
-        if (absErr)
-            std::memcpy(absErr, c->h_res, sizeof(double) * N);
-        if (probErr)
-            std::memcpy(probErr, c->h_res + N, sizeof(double) * N);
-        if (depth2)
-            std::memcpy(depth2, c->h_res + 2 * N, sizeof(double) * N);
-    };
+    s.seq = (int)(++c->door_seq);
     c->meas_star = useEqv ? 1 : 0;
     c->meas_ids.assign(ids, ids + M);
     c->busy_meas = true;
-    if (!speculate && max_outliers >= 0 && N <= SEL_MAXN) {
-        // Outlier candidates frame after frame (speculation has backed off): statistics, the outlier decision (k_select_outliers: the discarded
-        // landmarks' measurements are masked out of C) and the whole update queued at once, ONE host wait. The discarded landmarks leave the
-        // state after the update (an unmeasured landmark can be marginalised before or after it).
-        // EQF_OPT_LIVE_COLUMNS_FIRST: up to 16 panels the look-ahead kernel ends with the last panel that holds a column of a landmark that stays (k_stats_select orders them)
-        const bool live_first = N <= SEL_ONE_WG && c->opt_sel_one && c->opt_live_first && blocks(2 * M, 32) <= 16 && blocks(2 * M, 32) >= 3;
-        if (N <= SEL_ONE_WG && c->opt_sel_one) { // statistics and decision as one launch of one workgroup
-            KTimer t(c, KN_STATS);
-            LAUNCH_TS(c, k_stats_select, dim3(1), dim3(512), c->stream, N, c->Ncap, c->ld, c->chart, make_cam(cam),
-                      same_as_staged ? (const double*)(c->d_meas + 2 * (size_t)c->Ncap) /* the staged copy in HBM: no PCIe round trip in front of the statistics */ : pack_by_landmark(c, measof, y), c->q0(), c->Qq(), c->Qa(),
-                      (const TS*)c->sigma(), c->h_res, useEqv ? 1 : 0, c->d_C, c->d_ytil, c->d_lmidx, c->d_flags, thrAbs, thrProb, max_outliers, M, c->h_sel, live_first ? c->d_spec + 2 : (int*)nullptr);
-            HIPCHK(hipGetLastError());
-        } else {
-            KTimer t(c, KN_STATS);
-            LAUNCH_TS(c, k_outlier_stats, dim3(blocks(N, 64)), dim3(64), c->stream, N, c->Ncap, c->ld, c->chart, make_cam(cam), same_as_staged ? (const double*)c->h_ylm : pack_by_landmark(c, measof, y), c->q0(), c->Qq(),
-                      c->Qa(), (const TS*)c->sigma(), c->h_res, useEqv ? 1 : 0, c->d_C, c->d_ytil, c->d_lmidx, c->d_flags, (int*)nullptr, c->h_door, seq, thrAbs, thrProb,
-                      (int*)nullptr, seq, c->d_stats);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_select_outliers, dim3(1), dim3(256), 0, c->stream, N, c->Ncap, M, c->d_stats, thrAbs, thrProb, max_outliers, c->d_lmidx, c->d_C, c->d_ytil, c->h_sel);
-            HIPCHK(hipGetLastError());
-        }
-        c->meas_valid = false;
-        c->early_allowed = c->opt_early_door != 0;
-        rc = launch_update_tail(c, ids, M, meas_var, discreteCorr, nullptr, 0, use_door, seq, nullptr, live_first);
-        if (rc)
-            return rc;
-        host_stamp(c, TH_TAIL_OUT);
-        bool early = false;
-        rc = use_door ? door_wait(c, 1, seq, &early) : sync_ctx(c);
-        if (rc)
-            return rc;
-        copy_stats();
-        ++c->sel_frames;
-        if (c->h_sel[c->Ncap] == 0) // a frame without an outlier candidate ends the back-off
-            c->spec_backoff = c->spec_backoff_len = 0;
-        rc = early ? finish_update_early(c, discreteCorr, seq) : finish_update(c, discreteCorr);
-        if (rc)
-            return rc;
-        *updated = 1;
-        std::vector<int> idx;
-        for (int i = 0; i < N; ++i)
-            if (c->h_sel[i])
-                idx.push_back(i);
-        if (n_removed)
-            *n_removed = (int)idx.size();
-        if (removed_idx)
-            std::copy(idx.begin(), idx.end(), removed_idx);
-        c->sel_discarded += (long)idx.size();
-        return idx.empty() ? 0 : eqf_remove_landmarks(c, idx.data(), (int)idx.size());
-    }
-    if (!speculate) { // plain statistics call: the caller decides and calls eqf_vision_update
-        {
-            KTimer t(c, KN_STATS);
-            LAUNCH_TS(c, k_outlier_stats, dim3(blocks(N, 64)), dim3(64), c->stream, N, c->Ncap, c->ld, c->chart, make_cam(cam), same_as_staged ? (const double*)c->h_ylm : pack_by_landmark(c, measof, y), c->q0(), c->Qq(),
-                      c->Qa(), (const TS*)c->sigma(), c->h_res, useEqv ? 1 : 0, c->d_C, c->d_ytil, c->d_lmidx, c->d_flags, use_door ? c->d_door : nullptr, c->h_door, seq, thrAbs,
-                      thrProb, (int*)nullptr, seq, (double*)nullptr);
-            HIPCHK(hipGetLastError());
-        }
-        c->meas_valid = true;
-        rc = use_door ? door_wait(c, 0, seq) : sync_ctx(c);
-        if (rc)
-            return rc;
-        copy_stats();
-        bool candidate = false; // a frame without an outlier candidate ends the back-off
-        for (int i = 0; i < N && !candidate; ++i)
-            candidate = c->h_res[i] > thrAbs || c->h_res[N + i] > thrProb;
-        if (!candidate)
-            c->spec_backoff = c->spec_backoff_len = 0;
-        return 0;
-    }
-    // Speculative tail: measurement, statistics and Z in ONE kernel (k_build_Z with measurement fusion), then the factorisation,
-    // the lift and the covariance update, all queued at once. An outlier candidate cancels everything behind the first kernel.
-    MeasFuse mf{};
-    mf.enabled = 1;
-    mf.N = N, mf.Ncap = c->Ncap, mf.chart = c->chart, mf.star = useEqv ? 1 : 0;
-    mf.cam = make_cam(cam);
-    if (staged)
-        mf.y = c->d_meas, mf.lmidx = c->d_meas_idx, mf.ylm = c->d_meas + 2 * (size_t)c->Ncap;
-    else
-        mf.y = c->h_y, mf.lmidx = lmidx, mf.ylm = pack_by_landmark(c, measof, y);
-    mf.q0 = c->q0(), mf.Qq = c->Qq(), mf.Qa = c->Qa();
-    mf.out = c->h_res;
-    mf.C = c->d_C, mf.ytil = c->d_ytil, mf.lmidx_dev = c->d_lmidx;
-    mf.thrAbs = thrAbs, mf.thrProb = thrProb;
-    mf.spec_w = c->d_spec, mf.spec_seq = seq;
-    c->meas_valid = false; // consumed by the tail below (restored if the tail is cancelled)
-    c->early_allowed = c->opt_early_door != 0;
-    rc = launch_update_tail(c, ids, M, meas_var, discreteCorr, c->d_spec, seq, use_door, seq, &mf);
-    if (rc)
-        return rc;
-    host_stamp(c, TH_TAIL_OUT);
-    bool early = false;
-    rc = use_door ? door_wait(c, 1, seq, &early) : sync_ctx(c);
-    if (rc)
-        return rc;
-    copy_stats();
-    ++c->spec_queued;
-    if (early) { // (the early doorbell does not ring for a cancelled tail)
-        c->spec_backoff = c->spec_backoff_len = 0;
-        rc = finish_update_early(c, discreteCorr, seq);
-        if (rc == 0)
-            *updated = 1;
-        return rc;
-    }
-    if (c->h_resflags[2]) { // cancelled on the device: nothing was modified, C / residuals of the statistics kernel are still valid
-        ++c->spec_cancelled;
-        // (up to 256 frames when the caller lets the device take the outlier decision: a frame with candidates then costs one round trip anyway, a cancelled tail two and a wasted
-        //  launch sequence - with candidates in nearly every frame, the shipped thresholds, the cap of 16 wasted a tail every 17th frame)
-        c->spec_backoff_len = std::min(max_outliers >= 0 ? 256 : 16, std::max(1, 2 * c->spec_backoff_len));
-        c->spec_backoff = c->spec_backoff_len;
-        c->meas_valid = true;
-        return 0;
-    }
-    c->spec_backoff = c->spec_backoff_len = 0;
-    rc = finish_update(c, discreteCorr);
-    if (rc == 0)
-        *updated = 1;
-    return rc;
+    if (!speculate)
+        return (max_outliers >= 0 && N <= SEL_MAXN) ? stats_select_route(c, s) : stats_only_route(c, s);
+    return stats_speculative_route(c, s);
 }
 
 int eqf_stats_then_update(eqf_ctx* c, const eqvio_camera* cam, const int* ids, const double* y, int M, double thrAbs, double thrProb, double meas_var, int useEqv,

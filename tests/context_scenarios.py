@@ -31,8 +31,8 @@ CU_COUNT = 256  # compute units of one MI355X: lookahead_eligible compares the l
 # Size thresholds of the context path, as read from the code (left value | right value take different forms). NJ = ceil(2 M / 32) panels of S.
 THRESHOLDS = {
     "NJ 2|3": "launch chain below the smallest look-ahead instantiation (lookahead_eligible: NJ >= 3)",
-    "NJ 8|9": "ZB = 2 (the look-ahead kernel evaluates the output blocks itself) in the speculative tail up to 8 panels (launch_update_tail)",
-    "NJ 16|17": "la_row2 / la_build_rows2, HOME placement, live_cols and live_first up to 16 panels (launch_lookahead, stats_then_update)",
+    "NJ 8|9": "ZB = 2 (the look-ahead kernel evaluates the output blocks itself) in the speculative tail up to 8 panels (plan_tail)",
+    "NJ 16|17": "la_row2 / la_build_rows2, HOME placement, live_cols and live_first up to 16 panels (launch_lookahead, plan_tail, stats_select_route)",
     "NJ 32|33": "look-ahead kernel up to 32 panels (la_njcap), one launch per panel above",
     "N 256|257": "propagation: nT = ceil(N / 16) > 16 takes the mirrored lower triangle with several tiles per workgroup (riccati_fast_impl)",
     "N 249|250": "k_syrk_lift walks the lower triangle row by row up to SYRK_ARITH_TILES = 24 tile rows of 32 (21 + 3 N <= 768)",
@@ -99,7 +99,7 @@ class Scenario:
         return settings_for(CHART_NAMES[self.chart], **kw)
 
     def expected(self):
-        """What the device's counters must read after the scenario (see launch_update_tail / stats_then_update): look-ahead launches, launches that built Z
+        """What the device's counters must read after the scenario (see plan_tail / stats_then_update and its three routes): look-ahead launches, launches that built Z
         inside, updates that used the propagation kernel's output blocks, speculative tails queued, frames with the device-side decision."""
         la = lookahead_fits(self.N, self.M)
         if self.route == "update":
@@ -350,6 +350,8 @@ def build_scenarios():
     s.append(_select("select_inv_N513_M257", 513, 257, 601, pins=("N 512|513", "NJ 16|17"), shuffled=True))
     s.append(_select("select_euc_N540_M530", 540, 530, 602, chart="euclid", pins=("NJ 32|33",)))
     s.append(_select("select_inv_N200_M190", 200, 190, 603, pins=()))
+    # the smallest look-ahead instantiation (3 panels) behind the device-side decision (tests/test_gpu_tail_routes.py crosses the options over it)
+    s.append(_select("select_inv_N40_M36", 40, 36, 604, pins=("NJ 2|3",)))
     return s
 
 
