@@ -1,7 +1,7 @@
 """ctypes binding of the filter batch: include/eqf_batch.h (device level, libeqf_hip.so) and include/eqvio_batch.h (filter level, libeqvio_filter.so).
 
-VIOFilterBatch holds B independent reference VIOFilters (fast Riccati, at most 64 landmarks each) whose frames go to the GPU together: one kernel launch per
-step, one workgroup per slot. .slot(k) is a view with the method names of capi.VIOFilter, so the per-filter test helpers work on a slot unchanged.
+VIOFilterBatch holds B independent reference VIOFilters (fast or, per slot, accurate Riccati; at most 64 landmarks each) whose frames go to the GPU together:
+one device call per step and mode, one workgroup per slot. BatchCore is the device level on its own. .slot(k) is a view with the method names of capi.VIOFilter, so the per-filter test helpers work on a slot unchanged.
 The prototypes are declared in lists of their own (_batch_declared), apart from the loaders' _declared lists of eqf_hip.h / eqvio_filter.h.
 """
 import ctypes as C
@@ -13,6 +13,7 @@ from eqvio_amd.capi import Camera, Settings, c_double_p, c_int_p, load_eqf_lib, 
 
 EQF_BATCH_MAX_LANDMARKS = 64
 BATCH_REMOVED_OLD, BATCH_REMOVED_OUTLIERS, BATCH_ADDED, BATCH_EMPTY, BATCH_UPDATED, BATCH_REMOVED_INVALID = 1, 2, 4, 8, 16, 32
+RICCATI_FAST, RICCATI_ACCURATE = 0, 1  # EQVIO_BATCH_RICCATI_* (include/eqvio_batch.h)
 
 
 class BatchFrame(C.Structure):
@@ -107,6 +108,8 @@ def load_batch_protos():
         "eqf_batch_state_estimate": (C.c_int, [vp, C.c_int, c_double_p, c_int_p, c_double_p, C.c_int]),
         "eqf_batch_sensor_estimate": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqf_batch_step": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
+        "eqf_batch_step_accurate": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
+        "eqf_batch_last_riccati": (C.c_int, [vp, C.c_int, c_int_p, c_int_p]),
         "eqf_batch_last_result": (C.c_int, [vp, C.c_int, c_int_p, c_double_p]),
         "eqf_batch_stream": (vp, [vp]),
         "eqf_batch_synchronize": (C.c_int, [vp]),
@@ -131,6 +134,8 @@ def load_batch_protos():
         "eqvio_batch_slots": (C.c_int, [vp]),
         "eqvio_batch_set_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
         "eqvio_batch_get_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
+        "eqvio_batch_set_slot_riccati": (C.c_int, [vp, C.c_int, C.c_int]),
+        "eqvio_batch_get_slot_riccati": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_process_imu": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqvio_batch_process_vision": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, P(Camera), c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
@@ -159,7 +164,8 @@ def load_batch_protos():
     }
     for lib, protos in ((elib, eprotos), (flib, fprotos)):
         for name, (res, args) in protos.items():
-            if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_batch_load_ctx", "eqf_batch_store_ctx", "eqvio_batch_load_filter", "eqvio_batch_store_filter") and not hasattr(lib, name):
+            if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_batch_load_ctx", "eqf_batch_store_ctx", "eqvio_batch_load_filter", "eqvio_batch_store_filter", "eqf_batch_step_accurate", "eqf_batch_last_riccati",
+                                                                   "eqvio_batch_set_slot_riccati", "eqvio_batch_get_slot_riccati") and not hasattr(lib, name):
                 continue  # same-box A/B against the libraries of an older commit (as capi.load_eqf_lib): entry points that commit did not have yet
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
@@ -189,6 +195,100 @@ class BatchError(RuntimeError):
     def __init__(self, msg, code):
         super().__init__(msg)
         self.code = code
+
+
+class BatchCore:
+    """The device level of the batch (include/eqf_batch.h) on its own: B slots without the host half of a VIOFilter. Either a batch of its own
+    (BatchCore(settings, slots)) or a view of the one behind a VIOFilterBatch (BatchCore.of(batch)), which stays the owner."""
+
+    def __init__(self, settings, slots, max_landmarks=EQF_BATCH_MAX_LANDMARKS, device=0):
+        self.elib, _ = load_batch_protos()
+        self.h = C.c_void_p()
+        self.owner = None
+        rc = self.elib.eqf_batch_create(C.byref(self.h), device, slots, max_landmarks, C.byref(settings))
+        if rc != 0:
+            raise BatchError(f"eqf_batch_create: {rc} ({self.elib.eqf_error_string(rc).decode()})", rc)
+
+    @classmethod
+    def of(cls, batch):
+        self = cls.__new__(cls)
+        self.elib, self.h, self.owner = batch.elib, C.c_void_p(batch.core_handle()), batch
+        return self
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise BatchError("eqf_batch: " + self.elib.eqf_error_string(rc).decode(), rc)
+
+    def close(self):
+        if self.h and self.owner is None:
+            self.elib.eqf_batch_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_state(self, k, xi0, Xs, ids, q0, Q):
+        xi0, Xs, ids, q0, Q = _f64(xi0), _f64(Xs), _i32(ids), _f64(q0), _f64(Q)
+        self._chk(self.elib.eqf_batch_set_state(self.h, k, _dp(xi0), _dp(Xs), _ip(ids), _dp(q0), _dp(Q), len(ids)))
+
+    def get_state(self, k):
+        cap = EQF_BATCH_MAX_LANDMARKS
+        xi0, Xs, ids, q0, Q = np.zeros(23), np.zeros(23), np.zeros(cap, np.int32), np.zeros(3 * cap), np.zeros(5 * cap)
+        N = self.elib.eqf_batch_get_state(self.h, k, _dp(xi0), _dp(Xs), _ip(ids), _dp(q0), _dp(Q), cap)
+        if N < 0:
+            self._chk(N)
+        return xi0, Xs, ids[:N].copy(), q0[: 3 * N].reshape(N, 3).copy(), Q[: 5 * N].reshape(N, 5).copy()
+
+    def set_sigma(self, k, Sigma):
+        S = np.asfortranarray(Sigma, dtype=np.float64)
+        self._chk(self.elib.eqf_batch_set_sigma(self.h, k, S.ctypes.data_as(c_double_p), S.shape[0]))
+
+    def get_sigma(self, k):
+        n = 21 + 3 * self.elib.eqf_batch_num_landmarks(self.h, k)
+        out = np.zeros((n, n), order="F")
+        self._chk(self.elib.eqf_batch_get_sigma(self.h, k, out.ctypes.data_as(c_double_p), n))
+        return out
+
+    def _step(self, fn, entries):
+        n = len(entries)
+        arr = (BatchFrame * max(n, 1))()
+        keep = []
+        for e, (slot, cam, imus, dts, ids, y, *rest) in enumerate(entries):
+            imus, dts, ids, y = _f64(imus).reshape(-1), _f64(dts).reshape(-1), _i32(ids), _f64(y).reshape(-1)
+            mean = _f64(rest[0]) if rest and rest[0] is not None else None
+            keep.append((imus, dts, ids, y, mean))
+            arr[e].slot, arr[e].cam, arr[e].k, arr[e].M = slot, cam, len(dts), len(ids)
+            arr[e].imu13_mean = _dp(mean) if mean is not None else None
+            arr[e].dt_total = float(rest[1]) if len(rest) > 1 else 0.0
+            arr[e].imu13_k = _dp(imus) if len(dts) else None
+            arr[e].dt_k = _dp(dts) if len(dts) else None
+            arr[e].ids = _ip(ids) if len(ids) else None
+            arr[e].y = _dp(y) if len(ids) else None
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(fn(self.h, n, arr, _ip(status)))
+        return status[:n].copy()
+
+    def step(self, entries):
+        """eqf_batch_step. entries: list of (slot, cam, imus[k, 13], dts[k], ids[M], y[2 M], imu13_mean, dt_total); returns the per-entry status codes."""
+        return self._step(self.elib.eqf_batch_step, entries)
+
+    def step_accurate(self, entries):
+        """eqf_batch_step_accurate: the frame with one accurate Riccati step per IMU sample. entries as step's; imu13_mean and dt_total may be left out."""
+        return self._step(self.elib.eqf_batch_step_accurate, entries)
+
+    def last_riccati(self, k):
+        """(samples with dt > 0, most squarings) of slot k's last accurate step (eqf_batch_last_riccati)."""
+        n, sq = C.c_int(), C.c_int()
+        self._chk(self.elib.eqf_batch_last_riccati(self.h, k, C.byref(n), C.byref(sq)))
+        return n.value, sq.value
+
+    def last_result(self, k):
+        flags, depth = C.c_int(), C.c_double()
+        self._chk(self.elib.eqf_batch_last_result(self.h, k, C.byref(flags), C.byref(depth)))
+        return flags.value, depth.value
 
 
 class VIOFilterBatch:
@@ -232,6 +332,27 @@ class VIOFilterBatch:
         out = Settings()
         self._chk(self.lib.eqvio_batch_get_slot_settings(self.h, k, C.byref(out)))
         return out
+
+    def set_slot_riccati(self, k, mode):
+        """The propagation slot k's frames take from its next frame on (eqvio_batch_set_slot_riccati): RICCATI_FAST (every slot starts with it) or
+        RICCATI_ACCURATE, the reference's default - one accurate Riccati step per IMU sample. k None: every slot. A bad mode or slot raises BatchError with
+        EQF_E_BAD_ARG and changes nothing."""
+        rc = self.lib.eqvio_batch_set_slot_riccati(self.h, -1 if k is None else k, mode)
+        if rc != 0:
+            raise BatchError(f"set_slot_riccati({k}, {mode}): " + self.elib.eqf_error_string(rc).decode(), rc)
+
+    def slot_riccati(self, k):
+        rc = self.lib.eqvio_batch_get_slot_riccati(self.h, k)
+        if rc < 0:
+            raise BatchError(f"slot_riccati({k}): " + self.elib.eqf_error_string(rc).decode(), rc)
+        return rc
+
+    def last_riccati(self, k):
+        """(samples, max_squarings) of slot k's last accurate step (eqf_batch_last_riccati): the samples that had dt > 0 and the most squarings one of its
+        exponentials took; 0, 0 after a fast step or a copy into the slot."""
+        n, sq = C.c_int(), C.c_int()
+        self._chk(self.elib.eqf_batch_last_riccati(self.core_handle(), k, C.byref(n), C.byref(sq)))
+        return n.value, sq.value
 
     def start_slot(self, k, sensor, ids, p, time):
         sensor, ids, p = _f64(sensor), _i32(ids), _f64(p)
@@ -464,6 +585,15 @@ class BatchSlot:
 
     def get_slot_settings(self):
         return self.b.get_slot_settings(self.k)
+
+    @property
+    def riccati(self):
+        """RICCATI_FAST or RICCATI_ACCURATE (VIOFilterBatch.set_slot_riccati)."""
+        return self.b.slot_riccati(self.k)
+
+    @riccati.setter
+    def riccati(self, mode):
+        self.b.set_slot_riccati(self.k, mode)
 
     def copy_to(self, dsts):
         """This slot into every slot of dsts (one slot or a list), one launch (VIOFilterBatch.copy_slots); returns the status codes."""

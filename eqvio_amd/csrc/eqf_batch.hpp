@@ -1,5 +1,5 @@
 // Filter batch (include/eqf_batch.h): B independent filters of at most 64 landmarks, one workgroup per slot, ONE launch per frame of all of them.
-// The device side: the packet structs and the eight kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
+// The device side: the packet structs and the ten kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
 // eqf_hip.hip includes both. Every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
 //
 // Per slot s, in HBM (fp64): two Sigma buffers (n x n column-major, leading dimension ld, n <= 21 + 3 * 64), two landmark buffers (35 SoA planes of stride
@@ -10,7 +10,9 @@
 // The filter settings a frame reads (chart, output, lifts, depth choice, thresholds, R, initial variance and depth, Q, P) are the SLOT's: BatchIn::ss, copied by
 // the host from the slot's settings into the packet entry of every step (eqf_batch_set_slot_settings), so one launch runs B different tunings.
 //
-// The phases of k_batch_frame (VIOFilter::processVisionData, fast Riccati, src/VIOFilter.cpp:194-241):
+// The phases of k_batch_frame (VIOFilter::processVisionData, fast Riccati, src/VIOFilter.cpp:194-241; its body is eqf_batch_frame_body.inc). With accurate
+// Riccati (eqf_batch_step_accurate) k_batch_riccati does what phases 0 and 1 do - one accurate Riccati step per IMU sample between the observer steps - and
+// k_batch_frame_tail, the same body from phase 2 on, the rest:
 //   0  rows of A and B of the surviving landmarks (assemble_landmark, sensor_Ass_entry / sensor_Bs_entry) into LDS; origin planes copied to the other
 //      buffer; the observer steps' landmark part (observer_chain) applied on the way. Landmarks the host found unmeasured (removeOldLandmarks) are not copied:
 //      the propagation is block triangular, so marginalising a landmark before or after it leaves every other entry the same.
@@ -74,6 +76,7 @@ struct BatchOut {
     double depth;                // depth the new landmarks got
     int dof;                     // rows m of the matched measurement (0: empty)
     double nis, logdet;          // yTilde^T S^-1 yTilde and log det S of the update (NaN when the update failed)
+    int ric_samples, ric_squarings; // k_batch_riccati's: samples with dt > 0, the most squarings an exponential took (eqf_batch_last_riccati)
 };
 // The slots' buffers, the same for every kernel: slot s has two Sigma buffers and two landmark buffers (which = 0 / 1; the host names the current one) and one
 // scratch area.
@@ -159,493 +162,359 @@ __device__ __forceinline__ V3 batch_point_estimate(const double* lm, int i) {
     return (1.0 / lm[BATCH_QA * L + i]) * q_rot(q_inv(ldq(lm + BATCH_QQ * L, L, i)), ld3(lm, L, i));
 }
 
+// Both kernels have one body, eqf_batch_frame_body.inc: k_batch_frame all of it, k_batch_frame_tail phases 2 - 5 (eqf_batch_step_accurate, below).
 __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame(const BatchArgs ba) {
-    __shared__ double sm[BATCH_SM];
+#define EQF_BATCH_FRAME_TAIL 0
+#include "eqf_batch_frame_body.inc"
+#undef EQF_BATCH_FRAME_TAIL
+}
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame_tail(const BatchArgs ba) {
+#define EQF_BATCH_FRAME_TAIL 1
+#include "eqf_batch_frame_body.inc"
+#undef EQF_BATCH_FRAME_TAIL
+}
+
+// ===================================================================================================
+// eqf_batch_step_accurate (include/eqf_batch.h): integrateUpToTime with fastRiccati == false (src/VIOFilter.cpp:160-178) - per IMU sample one
+// integrateRiccatiStateAccurate (VIO_eqf.cpp:74-91) at the X the samples before it have produced, then that sample's observer step - as a kernel of its own in
+// front of k_batch_frame_tail, on the same stream within the same round trip. It ends where phases 0 and 1 of k_batch_frame end: Sigma of the surviving
+// landmarks (n1 x n1) in the slot's other Sigma buffer, their planes in the other landmark buffer.
+//
+// Per sample with dt > 0, Sigma <- Phi Sigma Phi^T + Phi_B (Q / dt) Phi_B^T + dt P with [Phi Phi_B] the top n rows of exp(dt [[A, B], [0, 0]]), by the
+// structured scheme of k_expm_sensor / k_expm_landmarks (eqf_kernels.hpp), restated inside the slot's workgroup: the scaling 2^-s from the infinity norm of
+// dt [A B], a Taylor series of degree EXPM_K of the scaled generator - the sensor part E (21 x 33) by the whole workgroup, then [Y_i | F_i] (3 x 33, 3 x 3) a
+// wave per landmark -, then s squarings [[E, 0], [Y, F]]^2 = [[E^2, 0], [Y E + F Y, F^2]] with every landmark's Y, F and E in LDS, in lockstep. Phi's rows have
+// the shape of the rows of F = I + dt A in k_batch_frame's phase 1, except that a landmark row carries all 21 sensor columns: G = Phi Sigma goes to the
+// scratch area, Sigma' = G Phi^T + noise (lower half, mirrored) to the other Sigma buffer, which is also the next sample's source - the first sample gathers
+// from the current buffer through the surviving rows. Without a sample of dt > 0 the gathered Sigma is copied, bit for bit.
+// The LDS footprint (78 KB: E, the scaled generator, two Taylor temporaries, 64 x 108 doubles of Y / F) is why this is no instantiation of the frame body.
+struct RicStep {
+    double dt;
+    CommonK ck; // sensor-level terms of A and B at the X this sample starts from
+};
+struct RicArgs {
+    BatchBufs buf;
+    const BatchIn* in;
+    const ObsStep* steps;
+    const RicStep* rsteps;
+    BatchOut* out;
+};
+constexpr int RIC_EN = 21 * 33;                        // E, the scaled generator, a Taylor temporary
+constexpr int RIC_SLOT = 3 * 33 + 9;                   // a landmark's Y and F; before its Taylor series, its rows of A (45) and B (9)
+constexpr int RIC_SM = 4 * RIC_EN + 66 + BATCH_L * RIC_SLOT;
+static_assert(4 * (3 * 33) <= RIC_EN, "the waves' staging rows fit into the sensor series' temporary");
+
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_riccati(const RicArgs ra) {
+    __shared__ double sm[RIC_SM];
+    __shared__ double s_red[BATCH_T / 64];
+    __shared__ double s_qp[20]; // Q / dt and dt P of the sample
     __shared__ int s_gidx[BATCH_NMAX];
-    __shared__ int s_surv[BATCH_L], s_keep[BATCH_L], s_mlm[BATCH_L], s_mj[BATCH_L];
-    __shared__ int s_misc[8]; // 0 kept, 1 matched, 2 fail, 3 kept after the lift
-    __shared__ double s_depth;
-    __shared__ unsigned long long s_mask;
-    const BatchIn& in = ba.in[blockIdx.x];
-    BatchOut* out = ba.out + blockIdx.x;
-    const int tid = threadIdx.x;
-    const int L = BATCH_L, ld = ba.buf.ld;
-    // the slot's settings: read once, before the first store of the launch
-    const int chart = in.ss.chart, star = in.ss.star, discrete = in.ss.discrete, median = in.ss.median;
-    const double thrAbs = in.ss.thrAbs, thrProb = in.ss.thrProb, meas_var = in.ss.meas_var, init_var = in.ss.init_var, init_depth = in.ss.init_depth;
+    __shared__ int s_surv[BATCH_L];
+    const BatchIn& in = ra.in[blockIdx.x];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int L = BATCH_L, ld = ra.buf.ld;
+    const int chart = in.ss.chart;
     const bool ind = chart == EQVIO_COORD_INVDEPTH;
     const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
-    double* S0 = ba.buf.sig_of(slot, cur);
-    double* S1 = ba.buf.sig_of(slot, nxt);
-    double* L0 = ba.buf.lm_of(slot, cur);
-    double* L1 = ba.buf.lm_of(slot, nxt);
-    double* scr = ba.buf.scr_of(slot);
-    const int Ns = in.Ns, n1 = 21 + 3 * Ns, M = in.M;
-    const double dt = in.dt;
+    const double* S0 = ra.buf.sig_of(slot, cur);
+    double* S1 = ra.buf.sig_of(slot, nxt);
+    const double* L0 = ra.buf.lm_of(slot, cur);
+    double* L1 = ra.buf.lm_of(slot, nxt);
+    double* G = ra.buf.scr_of(slot);
+    const int Ns = in.Ns, n1 = 21 + 3 * Ns, K = in.k;
+    double* sP = sm;              // [A B] of the sensor rows (21 x 33, row-major), then scaled
+    double* sE = sP + RIC_EN;     // E
+    double* sT = sE + RIC_EN;     // the series' current term; afterwards the waves' staging rows (3 x 33 each)
+    double* sN = sT + RIC_EN;     // the next term, the next square
+    double* lm66 = sN + RIC_EN;
+    double* YF = lm66 + 66;       // per landmark: Y (3 x 33, row-major), F (3 x 3)
 
-    // ---- phase 0: A / B rows, landmark planes, observer steps
-    double* Ass = sm;
-    double* Bs = sm + 441;
-    double* lm66 = sm + 693;
-    double* Al = sm + 759;
-    double* Bl = Al + BATCH_L * 45;
-    double* Qd = sm + BATCH_SM_PROP; // the slot's input gains and process variances, behind the rows (the update's region is the larger one)
-    double* Pd = Qd + 12;
-    if (tid < 12)
-        Qd[tid] = in.ss.Qd[tid];
-    else if (tid < 20)
-        Pd[tid - 12] = in.ss.Pd[tid - 12];
-    for (int t = tid; t < 441; t += BATCH_T)
-        Ass[t] = sensor_Ass_entry(in.ck, t);
-    for (int t = tid; t < 252; t += BATCH_T)
-        Bs[t] = sensor_Bs_entry(in.ck, t);
-    for (int t = tid; t < 66; t += BATCH_T)
-        lm66[t] = in.ck.lm[t];
     for (int t = tid; t < Ns; t += BATCH_T)
         s_surv[t] = in.surv[t];
     __syncthreads();
     for (int r = tid; r < n1; r += BATCH_T)
         s_gidx[r] = r < 21 ? r : 21 + 3 * s_surv[(r - 21) / 3] + (r - 21) % 3;
-    {
-        // waves 0 / 1 / 2 assemble the three independent column parts of a landmark's rows of A and B (assemble_landmark<PART>), wave 3 copies its planes and
-        // runs the observer steps: one lane per landmark in each
-        const int wave = tid >> 6, i = tid & 63;
-        if (i < Ns) {
-            const int o = s_surv[i];
-            const V3 p0 = ld3(L0, L, o);
-            Qt q = ldq(L0 + BATCH_QQ * L, L, o);
-            double a = L0[BATCH_QA * L + o];
-            if (wave < 3) {
-                const M3 e2i = ind ? ld_cc(L0, L, o, CC_E2I) : M3{}, i2e = ind && wave == 2 ? ld_cc(L0, L, o, CC_I2E) : M3{};
+    // the surviving landmarks' planes into the other buffer; wave 3 keeps (q, a) of its landmark and takes it through the observer steps
+    V3 p0{};
+    Qt q{};
+    double a = 1.0;
+    if (wave == 3 && lane < Ns) {
+        const int o = s_surv[lane];
+        for (int pl = 0; pl < BATCH_PLANES; ++pl)
+            L1[pl * L + lane] = L0[pl * L + o];
+        p0 = ld3(L0, L, o);
+        q = ldq(L0 + BATCH_QQ * L, L, o);
+        a = L0[BATCH_QA * L + o];
+    }
+    __syncthreads();
+
+    bool first = true; // Sigma is still the current buffer's, to be gathered
+    int samples = 0, max_sq = 0;
+    for (int s = 0; s < K; ++s) {
+        const RicStep& rs = ra.rsteps[in.obs_off + s];
+        const double dt = rs.dt;
+        if (dt > 0.0) {
+            // ---- A and B at this sample's X: the sensor rows into sP, the landmarks' rows into their slots (assemble_landmark<PART>, a wave per column part)
+            for (int t = tid; t < RIC_EN; t += BATCH_T) {
+                const int r = t / 33, c = t % 33;
+                sP[t] = c < 21 ? sensor_Ass_entry(rs.ck, r * 21 + c) : sensor_Bs_entry(rs.ck, r * 12 + (c - 21));
+            }
+            for (int t = tid; t < 66; t += BATCH_T)
+                lm66[t] = rs.ck.lm[t];
+            if (tid < 12)
+                s_qp[tid] = in.ss.Qd[tid] / dt;
+            else if (tid < 20)
+                s_qp[tid] = dt * in.ss.Pd[tid - 12];
+            __syncthreads();
+            if (wave < 3 && lane < Ns) {
+                const int i = lane;
+                const V3 pi = ld3(L1, L, i);
+                const Qt qi = ldq(L1 + BATCH_QQ * L, L, i);
+                const double ai = L1[BATCH_QA * L + i];
+                const M3 e2i = ind ? ld_cc(L1, L, i, CC_E2I) : M3{}, i2e = ind && wave == 2 ? ld_cc(L1, L, i, CC_I2E) : M3{};
                 double al[45], bl[9];
+                double* Al = YF + i * RIC_SLOT;
                 if (wave == 0) {
-                    assemble_landmark<0>(lm66, chart, p0, q, a, e2i, i2e, al, bl);
+                    assemble_landmark<0>(lm66, chart, pi, qi, ai, e2i, i2e, al, bl);
                     for (int r = 0; r < 3; ++r)
                         for (int c = 0; c < 6; ++c)
-                            Al[i * 45 + r * 15 + c] = al[r * 15 + c];
+                            Al[r * 15 + c] = al[r * 15 + c];
                     for (int e = 0; e < 9; ++e)
-                        Bl[i * 9 + e] = bl[e];
+                        Al[45 + e] = bl[e];
                 } else if (wave == 1) {
-                    assemble_landmark<1>(lm66, chart, p0, q, a, e2i, i2e, al, bl);
+                    assemble_landmark<1>(lm66, chart, pi, qi, ai, e2i, i2e, al, bl);
                     for (int r = 0; r < 3; ++r)
                         for (int c = 6; c < 12; ++c)
-                            Al[i * 45 + r * 15 + c] = al[r * 15 + c];
+                            Al[r * 15 + c] = al[r * 15 + c];
                 } else {
-                    assemble_landmark<2>(lm66, chart, p0, q, a, e2i, i2e, al, bl);
+                    assemble_landmark<2>(lm66, chart, pi, qi, ai, e2i, i2e, al, bl);
                     for (int r = 0; r < 3; ++r)
                         for (int c = 12; c < 15; ++c)
-                            Al[i * 45 + r * 15 + c] = al[r * 15 + c];
-                }
-            } else {
-                for (int pl = 0; pl < BATCH_QQ; ++pl)
-                    L1[pl * L + i] = L0[pl * L + o];
-                if (in.k > 0)
-                    observer_chain(ba.steps + in.obs_off, in.k, p0, q, a);
-                L1[BATCH_QQ * L + i] = q.w;
-                L1[(BATCH_QQ + 1) * L + i] = q.x;
-                L1[(BATCH_QQ + 2) * L + i] = q.y;
-                L1[(BATCH_QQ + 3) * L + i] = q.z;
-                L1[BATCH_QA * L + i] = a;
-            }
-        }
-    }
-    __syncthreads();
-
-    // row r of F = I + dt A applied to a vector given entry by entry: sum_k F[r][k] v(k)
-    auto f_row = [&](int r, auto v) -> double {
-        double acc = 0.0;
-        if (r < 21) {
-            for (int k = 0; k < 21; ++k)
-                acc += Ass[r * 21 + k] * v(k);
-        } else {
-            const int i = (r - 21) / 3, a = (r - 21) % 3;
-            const double* row = Al + i * 45 + a * 15;
-            for (int e = 0; e < 12; ++e)
-                acc += row[e] * v(al_col(e));
-            for (int b = 0; b < 3; ++b)
-                acc += row[12 + b] * v(21 + 3 * i + b);
-        }
-        return v(r) + dt * acc;
-    };
-    auto b_entry = [&](int r, int e) -> double {
-        if (r < 21)
-            return Bs[r * 12 + e];
-        const int i = (r - 21) / 3, a = (r - 21) % 3;
-        return e < 3 ? Bl[i * 9 + a * 3 + e] : 0.0;
-    };
-
-    // ---- phase 1: Sigma' = F Sigma F^T + dt (B Q B^T + P)
-    double* G = scr;
-    for (int t = tid; t < n1 * n1; t += BATCH_T) {
-        const int r = t % n1, c = t / n1;
-        const double* col = S0 + (size_t)s_gidx[c] * ld;
-        G[r + (size_t)c * ld] = f_row(r, [&](int k) { return col[s_gidx[k]]; });
-    }
-    __syncthreads();
-    for (int t = tid; t < n1 * n1; t += BATCH_T) {
-        const int r = t % n1, c = t / n1;
-        if (r < c)
-            continue;
-        double v = f_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
-        double nz = 0.0;
-        for (int e = 0; e < 12; ++e)
-            nz += b_entry(r, e) * Qd[e] * b_entry(c, e);
-        if (r == c)
-            nz += Pd[r < 21 ? r / 3 : 7];
-        v += dt * nz;
-        S1[r + (size_t)c * ld] = v;
-        S1[c + (size_t)r * ld] = v;
-    }
-    __syncthreads();
-
-    // ---- phase 2: removeOutliers
-    double* ylm = scr + (size_t)ld * BATCH_NMAX; // planes u, v, feature index (-1: not measured)
-    double* stats = ylm + 3 * L;                 // absErr, probErr, |q_hat|^2 of the surviving landmarks
-    for (int i = tid; i < Ns; i += BATCH_T)
-        ylm[2 * L + i] = -1.0;
-    __syncthreads();
-    for (int j = tid; j < M; j += BATCH_T)
-        if (in.midx[j] >= 0) {
-            const int i = in.midx[j];
-            ylm[i] = in.y[2 * j];
-            ylm[L + i] = in.y[2 * j + 1];
-            ylm[2 * L + i] = (double)j;
-        }
-    __syncthreads();
-    if (tid < Ns) {
-        double ae, pe;
-        outlier_stats_body<double>(Ns, L, ld, chart, in.cam, ylm, L1, L1 + BATCH_QQ * L, L1 + BATCH_QA * L, S1, stats, 0, nullptr, nullptr, nullptr, nullptr, ae, pe,
-                                   false, tid);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        // candidates ranked as the reference's sort + reverse: absolute outliers first (largest error first), then probabilistic ones
-        unsigned long long cand = 0, drop = 0;
-        for (int i = 0; i < Ns; ++i) {
-            const double ae = stats[i], pe = stats[Ns + i];
-            if (ylm[2 * L + i] < 0.0)
-                continue;
-            if (ae > thrAbs || pe > thrProb)
-                cand |= 1ull << i;
-        }
-        for (int t = 0; t < in.max_outliers && cand; ++t) {
-            int best = -1;
-            bool best_abs = false;
-            double best_v = 0.0;
-            for (int i = 0; i < Ns; ++i) {
-                if (!((cand >> i) & 1ull))
-                    continue;
-                const bool isabs = stats[i] > thrAbs;
-                const double v = isabs ? stats[i] : stats[Ns + i];
-                if (best < 0 || (isabs && !best_abs) || (isabs == best_abs && v > best_v)) {
-                    best = i;
-                    best_abs = isabs;
-                    best_v = v;
+                            Al[r * 15 + c] = al[r * 15 + c];
                 }
             }
-            cand &= ~(1ull << best);
-            drop |= 1ull << best;
-        }
-        int nk = 0;
-        for (int i = 0; i < Ns; ++i)
-            if (!((drop >> i) & 1ull))
-                s_keep[nk++] = i;
-        // getMedianSceneDepth over the landmarks that stay: the element nth_element puts at position nk / 2
-        double depth = init_depth;
-        if (median && nk > 0) {
-            const int kth = nk / 2;
-            for (int a = 0; a < nk; ++a) {
-                const double va = stats[2 * Ns + s_keep[a]];
-                int less = 0, eq = 0;
-                for (int b = 0; b < nk; ++b) {
-                    const double vb = stats[2 * Ns + s_keep[b]];
-                    less += vb < va;
-                    eq += vb == va;
+            __syncthreads();
+            // ---- the scaling: s with |dt [A B]|_inf / 2^s <= 0.25 (k_expm_sensor's rule)
+            {
+                double mx = 0.0;
+                if (tid < 21) {
+                    for (int c = 0; c < 33; ++c)
+                        mx += fabs(sP[tid * 33 + c]);
+                } else if (tid >= 64 && tid - 64 < 3 * Ns) {
+                    const int i = (tid - 64) / 3, r = (tid - 64) % 3;
+                    const double* Al = YF + i * RIC_SLOT;
+                    for (int e = 0; e < 15; ++e)
+                        mx += fabs(Al[r * 15 + e]);
+                    for (int e = 0; e < 3; ++e)
+                        mx += fabs(Al[45 + r * 3 + e]);
                 }
-                if (less <= kth && kth < less + eq) {
-                    depth = sqrt(va);
-                    break;
-                }
+                for (int o = 32; o > 0; o >>= 1)
+                    mx = fmax(mx, __shfl_xor(mx, o, 64));
+                if (lane == 0)
+                    s_red[wave] = mx;
             }
-        }
-        // the matched measurement: features of kept or new landmarks, ascending id; their landmark index after addNewLandmarks
-        int m2 = 0;
-        for (int j = 0; j < M; ++j) {
-            const int mi = in.midx[j];
-            int li;
-            if (mi >= 0) {
-                if ((drop >> mi) & 1ull)
-                    continue;
-                li = 0;
-                for (int a = 0; a < mi; ++a)
-                    li += !((drop >> a) & 1ull);
-            } else {
-                li = nk + (-mi - 1);
+            __syncthreads();
+            int sc = 0;
+            {
+                const double nrm = dt * fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
+                while (sc < EXPM_SMAX && ldexp(nrm, -sc) > 0.25)
+                    ++sc;
             }
-            s_mlm[m2] = li;
-            s_mj[m2] = j;
-            ++m2;
-        }
-        s_misc[0] = nk;
-        s_misc[1] = m2;
-        s_misc[2] = 0;
-        s_depth = depth;
-        out->outliers = drop;
-        out->depth = depth;
-        out->did = (drop ? BATCH_DID_OUTLIERS : 0) | (in.nnew ? BATCH_DID_ADDED : 0);
-    }
-    __syncthreads();
-
-    // ---- phase 3: the kept landmarks and the new ones back to the first buffer pair
-    const int nk = s_misc[0], N2 = nk + in.nnew, n2 = 21 + 3 * N2, M2 = s_misc[1];
-    for (int r = tid; r < n2; r += BATCH_T)
-        s_gidx[r] = r < 21 ? r : ((r - 21) / 3 < nk ? 21 + 3 * s_keep[(r - 21) / 3] + (r - 21) % 3 : -1);
-    __syncthreads();
-    batch_gather_sigma(S0, S1, s_gidx, n2, ld, init_var);
-    if (tid < N2) {
-        const int i = tid;
-        if (i < nk) {
-            for (int pl = 0; pl < BATCH_PLANES; ++pl)
-                L0[pl * L + i] = L1[pl * L + s_keep[i]];
-        } else {
-            const int r = i - nk;
-            const double d = s_depth;
-            batch_new_landmark(L0, i, in.bear[3 * r] * d, in.bear[3 * r + 1] * d, in.bear[3 * r + 2] * d);
-        }
-    }
-    __syncthreads();
-    if (M2 == 0) { // performVisionUpdate returns at once on an empty measurement, and processVisionData before removeInvalidLandmarks
-        if (tid == 0) {
-            out->did |= BATCH_DID_EMPTY;
-            batch_finish(out, 0, N2, cur, 0, 0, 0.0, 0.0);
-        }
-        return;
-    }
-
-    // ---- phase 4: performVisionUpdate
-    const int m = 2 * M2;
-    double* Sp = sm;                  // S, then L: packed lower triangle
-    double* Cb = Sp + BATCH_SPACK;    // output blocks, 6 per matched feature
-    double* yt = Cb + BATCH_L * 6;    // yTilde
-    double* z = yt + BATCH_MAXM;      // L^-1 yTilde
-    double* gam = z + BATCH_MAXM;     // Gamma
-    double* inn = gam + BATCH_NMAX;   // NIS, log det S (the region's last three doubles are not Gamma's)
-    if (tid < M2) {
-        const int i = s_mlm[tid], j = s_mj[tid];
-        const MeasOut o = measure_one(chart, in.cam, ld3(L0, L, i), ldq(L0 + BATCH_QQ * L, L, i), L0[BATCH_QA * L + i], in.y[2 * j], in.y[2 * j + 1], star != 0,
-                                      ind ? ld_cc(L0, L, i, CC_R0) : M3{});
-        for (int e = 0; e < 6; ++e)
-            Cb[tid * 6 + e] = o.c[e];
-        yt[2 * tid] = o.yt[0];
-        yt[2 * tid + 1] = o.yt[1];
-    }
-    __syncthreads();
-    double* T = scr; // T = Sigma C^T (n2 x m), then W^T in place
-    for (int t = tid; t < n2 * M2; t += BATCH_T) {
-        const int r = t % n2, jj = t / n2;
-        const int l = 21 + 3 * s_mlm[jj];
-        double cj[6];
-        for (int e = 0; e < 6; ++e)
-            cj[e] = Cb[jj * 6 + e];
-        double o0, o1;
-        bz_T_pair(S0[r + (size_t)l * ld], S0[r + (size_t)(l + 1) * ld], S0[r + (size_t)(l + 2) * ld], cj, o0, o1);
-        T[r + (size_t)(2 * jj) * ld] = o0;
-        T[r + (size_t)(2 * jj + 1) * ld] = o1;
-    }
-    for (int t = tid; t < M2 * M2; t += BATCH_T) {
-        const int ii = t % M2, jj = t / M2;
-        if (ii < jj)
-            continue;
-        const int li = 21 + 3 * s_mlm[ii], lj = 21 + 3 * s_mlm[jj];
-        double ci[6], cj[6], sv[9], o[2][2];
-        for (int e = 0; e < 6; ++e) {
-            ci[e] = Cb[ii * 6 + e];
-            cj[e] = Cb[jj * 6 + e];
-        }
-        for (int c = 0; c < 3; ++c)
-            for (int r = 0; r < 3; ++r)
-                sv[3 * c + r] = S0[(li + r) + (size_t)(lj + c) * ld];
-        bz_S_block(ci, cj, sv, ii == jj, meas_var, o);
-        Sp[bt_tri(2 * ii, 2 * jj)] = o[0][0];
-        Sp[bt_tri(2 * ii + 1, 2 * jj)] = o[1][0];
-        Sp[bt_tri(2 * ii + 1, 2 * jj + 1)] = o[1][1];
-        if (ii != jj)
-            Sp[bt_tri(2 * ii, 2 * jj + 1)] = o[0][1];
-    }
-    __syncthreads();
-    // Cholesky S = L L^T, right-looking, in LDS
-    for (int k = 0; k < m; ++k) {
-        if (tid == 0) {
-            const double d = Sp[bt_tri(k, k)];
-            if (!(d > 0.0) || !(d - d == 0.0))
-                s_misc[2] = 1;
-            Sp[bt_tri(k, k)] = sqrt(d);
-        }
-        __syncthreads();
-        if (s_misc[2])
-            break;
-        const double lkk = Sp[bt_tri(k, k)];
-        for (int i = k + 1 + tid; i < m; i += BATCH_T)
-            Sp[bt_tri(i, k)] = Sp[bt_tri(i, k)] / lkk;
-        __syncthreads();
-        for (int i = k + 1 + tid; i < m; i += BATCH_T) {
-            const double lik = Sp[bt_tri(i, k)];
-            for (int j = k + 1; j <= i; ++j)
-                Sp[bt_tri(i, j)] -= lik * Sp[bt_tri(j, k)];
-        }
-        __syncthreads();
-    }
-    if (s_misc[2]) {
-        if (tid == 0)
-            batch_finish(out, EQF_E_NOT_SPD, N2, cur, 0, m, __builtin_nan(""), __builtin_nan(""));
-        return;
-    }
-    // W^T = T L^-T and z^T = yTilde^T L^-T, blocked by 16 columns on the matrix cores: row tiles of 16 rows of [T ; yTilde^T] (one wave each); per column block
-    // kb the product with the finished blocks (mfma16_nt, v_mfma_f64_16x16x4_f64) and then the 16 x 16 triangle, one lane per row. The columns are padded to
-    // m16 (zero columns of T, identity rows of L): the padding stays zero.
-    const int m16 = (m + 15) & ~15, rows = n2 + 1, nrt = (rows + 15) / 16;
-    double* Ld = scr + (size_t)ld * BATCH_MAXM; // L dense, column stride BATCH_MAXM
-    for (int t = tid; t < m16 * m16; t += BATCH_T) {
-        const int i = t % m16, p = t / m16;
-        Ld[i + (size_t)p * BATCH_MAXM] = (i < m && p < m) ? (p <= i ? Sp[bt_tri(i, p)] : 0.0) : (i == p ? 1.0 : 0.0);
-    }
-    for (int t = tid; t < nrt * 16 * m16; t += BATCH_T) {
-        const int r = t % (nrt * 16), k = t / (nrt * 16);
-        if (r == n2)
-            T[r + (size_t)k * ld] = k < m ? yt[k] : 0.0;
-        else if (r > n2 || k >= m)
-            T[r + (size_t)k * ld] = 0.0;
-    }
-    __syncthreads();
-    {
-        const int wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
-        for (int rt = wave; rt < nrt; rt += BATCH_T / 64) {
-            double* Tr = T + rt * 16;
-            for (int kb = 0; kb < m16 / 16; ++kb) {
-                d4 acc = {0, 0, 0, 0};
-                for (int pb = 0; pb < kb; ++pb) {
-                    const d4 a = mfma16_nt(Tr + (size_t)pb * 16 * ld, ld, Ld + kb * 16 + (size_t)pb * 16 * BATCH_MAXM, BATCH_MAXM);
-                    acc[0] += a[0], acc[1] += a[1], acc[2] += a[2], acc[3] += a[3];
+            const double scale = ldexp(dt, -sc);
+            ++samples;
+            max_sq = max(max_sq, sc);
+            // ---- sensor part: E = sum_k Ps^k / k! (rows 21 .. 32 of Ps are zero: the inner index runs over 21)
+            for (int t = tid; t < RIC_EN; t += BATCH_T) {
+                const double v = scale * sP[t];
+                sP[t] = v;
+                sT[t] = v;
+                sE[t] = v + (t / 33 == t % 33 ? 1.0 : 0.0);
+            }
+            __syncthreads();
+            for (int k = 2; k <= EXPM_K; ++k) {
+                for (int t = tid; t < RIC_EN; t += BATCH_T) {
+                    const int r = t / 33, c = t % 33;
+                    double acc = 0.0;
+                    for (int qq = 0; qq < 21; ++qq)
+                        acc += sT[r * 33 + qq] * sP[qq * 33 + c];
+                    sN[t] = acc / k;
                 }
-                for (int q = 0; q < 4; ++q) {
-                    double* e = Tr + lr + (size_t)(kb * 16 + lk + 4 * q) * ld;
-                    *e -= acc[q];
+                __syncthreads();
+                for (int t = tid; t < RIC_EN; t += BATCH_T) {
+                    sT[t] = sN[t];
+                    sE[t] += sN[t];
                 }
-                batch_wave_sync();
-                if (lane < 16) { // the diagonal block: row lr of the tile against L[kb block][kb block]
-                    double x[16];
-                    for (int c = 0; c < 16; ++c) {
-                        const double* lc = Ld + kb * 16 + c; // L[kb * 16 + c][kb * 16 + p] at lc[(kb * 16 + p) * BATCH_MAXM]
-                        double v = Tr[lane + (size_t)(kb * 16 + c) * ld];
-                        for (int p = 0; p < c; ++p)
-                            v -= lc[(size_t)(kb * 16 + p) * BATCH_MAXM] * x[p];
-                        x[c] = v / lc[(size_t)(kb * 16 + c) * BATCH_MAXM];
-                        Tr[lane + (size_t)(kb * 16 + c) * ld] = x[c];
+                __syncthreads();
+            }
+            // ---- landmark part, a wave per landmark and a lane per column: term_k = (term_{k-1} Ps + S^(k-1) / (k-1)! R) / k (k_expm_landmarks)
+            {
+                double* sR = sT + wave * 99;
+                const int c = lane;
+                for (int i = wave; i < Ns; i += BATCH_T / 64) {
+                    double* sl = YF + i * RIC_SLOT;
+                    double R[3] = {0, 0, 0};
+                    if (c < 33) {
+                        const int e = c < 3 ? c : (c >= 12 && c < 15) ? 3 + (c - 12) : (c >= 15 && c < 21) ? 6 + (c - 15) : -1;
+                        for (int r = 0; r < 3; ++r) {
+                            if (e >= 0)
+                                R[r] = scale * sl[r * 15 + e];
+                            else if (c >= 21 && c < 24)
+                                R[r] = scale * sl[45 + r * 3 + (c - 21)];
+                        }
                     }
-                }
-                batch_wave_sync();
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < m; k += BATCH_T)
-        z[k] = T[n2 + (size_t)k * ld];
-    __syncthreads();
-    for (int t = tid; t < n2; t += BATCH_T) {
-        double g = 0.0;
-        for (int k = 0; k < m; ++k)
-            g += T[t + (size_t)k * ld] * z[k];
-        gam[t] = g;
-        if (!(g - g == 0.0))
-            s_misc[2] = 2;
-    }
-    // The innovation statistics, from what the solve left in LDS: NIS = |z|^2 (wave 0) and log det S = 2 sum log L_kk (wave 1), over the true m rows. Lane l
-    // adds its entries l, l + 64 in ascending order, then the wave's butterfly: the order depends on m alone, not on the workgroup or the step's slot count.
-    if (tid < 128) {
-        const int lane = tid & 63;
-        double v = 0.0;
-        if (tid < 64) {
-            for (int k = lane; k < m; k += 64)
-                v += z[k] * z[k];
-        } else {
-            for (int k = lane; k < m; k += 64)
-                v += log(Sp[bt_tri(k, k)]);
-        }
-        v = batch_wave_sum(v);
-        if (lane == 0)
-            inn[tid >> 6] = tid < 64 ? v : 2.0 * v;
-    }
-    __syncthreads();
-    if (s_misc[2]) {
-        if (tid == 0)
-            batch_finish(out, EQF_E_NONFINITE, N2, cur, 0, m, __builtin_nan(""), __builtin_nan(""));
-        return;
-    }
-    // Sigma -= W^T W on the matrix cores: lower 16 x 16 tiles (one wave each), K = m16 (the padded columns of W are zero), mirrored into the upper half
-    {
-        const int wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
-        const int nt = (n2 + 15) / 16;
-        for (int t = wave; t < nt * (nt + 1) / 2; t += BATCH_T / 64) {
-            int bi, bj;
-            batch_tri_tile(t, bi, bj);
-            d4 acc = {0, 0, 0, 0};
-            for (int pb = 0; pb < m16 / 16; ++pb) {
-                const d4 a = mfma16_nt(T + bi * 16 + (size_t)pb * 16 * ld, ld, T + bj * 16 + (size_t)pb * 16 * ld, ld);
-                acc[0] += a[0], acc[1] += a[1], acc[2] += a[2], acc[3] += a[3];
-            }
-            const int r = bi * 16 + lr;
-            for (int q = 0; q < 4; ++q) {
-                const int c = bj * 16 + lk + 4 * q;
-                if (r < n2 && c < n2 && (bi > bj || r >= c)) {
-                    const double v = S0[r + (size_t)c * ld] - acc[q];
-                    S0[r + (size_t)c * ld] = v;
-                    S0[c + (size_t)r * ld] = v;
+                    double S[9], F[9], Spow[9];
+                    for (int r = 0; r < 3; ++r)
+                        for (int qq = 0; qq < 3; ++qq) {
+                            S[r * 3 + qq] = scale * sl[r * 15 + 12 + qq];
+                            Spow[r * 3 + qq] = S[r * 3 + qq];
+                            F[r * 3 + qq] = (r == qq ? 1.0 : 0.0) + S[r * 3 + qq];
+                        }
+                    double T[3] = {R[0], R[1], R[2]}, Y[3] = {R[0], R[1], R[2]};
+                    for (int k = 2; k <= EXPM_K; ++k) {
+                        batch_wave_sync(); // the staging rows' readers of the round before (and the slot's, before the first one) are done
+                        if (c < 33)
+                            for (int r = 0; r < 3; ++r)
+                                sR[r * 33 + c] = T[r];
+                        batch_wave_sync();
+                        double nt[3] = {0, 0, 0};
+                        if (c < 33) {
+                            for (int qq = 0; qq < 21; ++qq) {
+                                const double pv = sP[qq * 33 + c];
+                                nt[0] += sR[qq] * pv;
+                                nt[1] += sR[33 + qq] * pv;
+                                nt[2] += sR[66 + qq] * pv;
+                            }
+                            for (int r = 0; r < 3; ++r)
+                                nt[r] = (nt[r] + Spow[r * 3 + 0] * R[0] + Spow[r * 3 + 1] * R[1] + Spow[r * 3 + 2] * R[2]) / k;
+                        }
+                        double ns[9];
+                        for (int r = 0; r < 3; ++r)
+                            for (int qq = 0; qq < 3; ++qq)
+                                ns[r * 3 + qq] = (Spow[r * 3 + 0] * S[0 * 3 + qq] + Spow[r * 3 + 1] * S[1 * 3 + qq] + Spow[r * 3 + 2] * S[2 * 3 + qq]) / k;
+                        for (int r = 0; r < 3; ++r) {
+                            T[r] = nt[r];
+                            Y[r] += nt[r];
+                        }
+                        for (int e = 0; e < 9; ++e) {
+                            Spow[e] = ns[e];
+                            F[e] += ns[e];
+                        }
+                    }
+                    batch_wave_sync();
+                    if (c < 33)
+                        for (int r = 0; r < 3; ++r)
+                            sl[r * 33 + c] = Y[r];
+                    if (c < 9)
+                        sl[99 + c] = F[c];
                 }
             }
+            __syncthreads();
+            // ---- squarings, in lockstep: Y <- Y E + F Y and F <- F F of every landmark with this round's E, then E <- E E (rows 21 .. 32 of E are [0 I])
+            for (int j = 0; j < sc; ++j) {
+                const int c = lane;
+                for (int i = wave; i < Ns; i += BATCH_T / 64) {
+                    double* sl = YF + i * RIC_SLOT;
+                    double ny[3] = {0, 0, 0}, nf = 0.0;
+                    if (c < 33) {
+                        for (int r = 0; r < 3; ++r)
+                            ny[r] = c >= 21 ? sl[r * 33 + c] : 0.0;
+                        for (int qq = 0; qq < 21; ++qq) {
+                            const double pv = sE[qq * 33 + c];
+                            ny[0] += sl[qq] * pv;
+                            ny[1] += sl[33 + qq] * pv;
+                            ny[2] += sl[66 + qq] * pv;
+                        }
+                        const double y0 = sl[c], y1 = sl[33 + c], y2 = sl[66 + c];
+                        for (int r = 0; r < 3; ++r)
+                            ny[r] += sl[99 + r * 3 + 0] * y0 + sl[99 + r * 3 + 1] * y1 + sl[99 + r * 3 + 2] * y2;
+                    }
+                    if (c < 9) {
+                        const int r = c / 3, qq = c % 3;
+                        nf = sl[99 + r * 3 + 0] * sl[99 + 0 * 3 + qq] + sl[99 + r * 3 + 1] * sl[99 + 1 * 3 + qq] + sl[99 + r * 3 + 2] * sl[99 + 2 * 3 + qq];
+                    }
+                    batch_wave_sync();
+                    if (c < 33)
+                        for (int r = 0; r < 3; ++r)
+                            sl[r * 33 + c] = ny[r];
+                    if (c < 9)
+                        sl[99 + c] = nf;
+                }
+                for (int t = tid; t < RIC_EN; t += BATCH_T) {
+                    const int r = t / 33, cc = t % 33;
+                    double acc = cc >= 21 ? sE[r * 33 + cc] : 0.0;
+                    for (int qq = 0; qq < 21; ++qq)
+                        acc += sE[r * 33 + qq] * sE[qq * 33 + cc];
+                    sN[t] = acc;
+                }
+                __syncthreads();
+                for (int t = tid; t < RIC_EN; t += BATCH_T)
+                    sE[t] = sN[t];
+                __syncthreads();
+            }
+            // ---- Sigma' = Phi Sigma Phi^T + Phi_B (Q / dt) Phi_B^T + dt P
+            // row r of Phi applied to a vector given entry by entry (the shape of k_batch_frame's f_row; a landmark row carries all 21 sensor columns)
+            auto phi_row = [&](int r, auto v) -> double {
+                double acc = 0.0;
+                if (r < 21) {
+                    for (int k = 0; k < 21; ++k)
+                        acc += sE[r * 33 + k] * v(k);
+                } else {
+                    const int i = (r - 21) / 3, aa = (r - 21) % 3;
+                    const double* sl = YF + i * RIC_SLOT;
+                    for (int k = 0; k < 21; ++k)
+                        acc += sl[aa * 33 + k] * v(k);
+                    for (int b = 0; b < 3; ++b)
+                        acc += sl[99 + aa * 3 + b] * v(21 + 3 * i + b);
+                }
+                return acc;
+            };
+            auto phib = [&](int r, int e) -> double { return r < 21 ? sE[r * 33 + 21 + e] : YF[((r - 21) / 3) * RIC_SLOT + ((r - 21) % 3) * 33 + 21 + e]; };
+            const double* Ssrc = first ? S0 : S1;
+            for (int t = tid; t < n1 * n1; t += BATCH_T) {
+                const int r = t % n1, c = t / n1;
+                const double* col = Ssrc + (size_t)s_gidx[c] * ld;
+                G[r + (size_t)c * ld] = phi_row(r, [&](int k) { return col[s_gidx[k]]; });
+            }
+            __syncthreads();
+            for (int t = tid; t < n1 * n1; t += BATCH_T) {
+                const int r = t % n1, c = t / n1;
+                if (r < c)
+                    continue;
+                double v = phi_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
+                double nz = 0.0;
+                for (int e = 0; e < 12; ++e)
+                    nz += phib(r, e) * s_qp[e] * phib(c, e);
+                v += nz;
+                if (r == c)
+                    v += s_qp[12 + (r < 21 ? r / 3 : 7)];
+                S1[r + (size_t)c * ld] = v;
+                S1[c + (size_t)r * ld] = v;
+            }
+            if (first) { // the gathered rows' readers are behind the barrier above; the next reader is behind the sample's last one
+                for (int r = tid; r < n1; r += BATCH_T)
+                    s_gidx[r] = r;
+                first = false;
+            }
         }
-    }
-    // landmark lift; the sensor rows go to the host
-    double* est = ylm; // 4 planes of stride N2 (estimate, invalid flag)
-    if (tid < N2) {
-        const int i = tid;
-        const LiftIn li = lift_load(i, L, chart, discrete, L0, L0 + BATCH_QQ * L, L0 + BATCH_QA * L);
-        lift_landmark(i, V3{gam[21 + 3 * i], gam[22 + 3 * i], gam[23 + 3 * i]}, li, N2, L, chart, discrete, L0 + BATCH_QQ * L, L0 + BATCH_QA * L, est);
-    }
-    if (tid < 21)
-        out->gamma[tid] = gam[tid];
-    __syncthreads();
-
-    // ---- phase 5: removeInvalidLandmarks
-    if (tid == 0) {
-        unsigned long long bad = 0;
-        int nk2 = 0;
-        for (int i = 0; i < N2; ++i) {
-            if (est[3 * N2 + i] != 0.0)
-                bad |= 1ull << i;
-            else
-                s_keep[nk2++] = i;
+        // ---- this sample's observer step of the landmarks
+        if (wave == 3 && lane < Ns) {
+            observer_chain(ra.steps + in.obs_off + s, 1, p0, q, a);
+            L1[BATCH_QQ * L + lane] = q.w;
+            L1[(BATCH_QQ + 1) * L + lane] = q.x;
+            L1[(BATCH_QQ + 2) * L + lane] = q.y;
+            L1[(BATCH_QQ + 3) * L + lane] = q.z;
+            L1[BATCH_QA * L + lane] = a;
         }
-        s_misc[3] = nk2;
-        s_mask = bad;
-    }
-    __syncthreads();
-    const int N3 = s_misc[3];
-    if (N3 < N2) {
-        const int n3 = 21 + 3 * N3;
-        for (int r = tid; r < n3; r += BATCH_T)
-            s_gidx[r] = r < 21 ? r : 21 + 3 * s_keep[(r - 21) / 3] + (r - 21) % 3;
         __syncthreads();
-        for (int t = tid; t < n3 * n3; t += BATCH_T) {
-            const int r = t % n3, c = t / n3;
+    }
+    if (first) // no sample moved Sigma: the gathered Sigma as it is
+        for (int t = tid; t < n1 * n1; t += BATCH_T) {
+            const int r = t % n1, c = t / n1;
             S1[r + (size_t)c * ld] = S0[s_gidx[r] + (size_t)s_gidx[c] * ld];
         }
-        if (tid < N3)
-            for (int pl = 0; pl < BATCH_PLANES; ++pl)
-                L1[pl * L + tid] = L0[pl * L + s_keep[tid]];
-    }
     if (tid == 0) {
-        out->did |= BATCH_DID_UPDATE | (N3 < N2 ? BATCH_DID_INVALID : 0);
-        batch_finish(out, 0, N3, N3 < N2 ? nxt : cur, s_mask, m, inn[0], inn[1]);
+        ra.out[blockIdx.x].ric_samples = samples;
+        ra.out[blockIdx.x].ric_squarings = max_sq;
     }
 }
 

@@ -44,6 +44,7 @@ struct eqf_batch {
         double inn_nis = 0.0, inn_logdet = 0.0;
         long tot_updates = 0, tot_dof = 0; // their sums over the steps that carried EQF_BATCH_UPDATED, in step order (eqf_batch_innovation_totals)
         double tot_nis = 0.0, tot_logdet = 0.0;
+        int ric_samples = 0, ric_squarings = 0; // the last accurate step's counters (eqf_batch_last_riccati); 0 after a fast step or a copy into the slot
         eqvio_settings set{}; // the slot's own settings (eqf_batch_set_slot_settings; eqf_batch_create's until then)
         BatchSlotSet ss{};    // what the kernels read of them: copied into the slot's packet entry of every step
     };
@@ -53,6 +54,7 @@ struct eqf_batch {
     BatchPacket<BatchIn> in; // eqf_batch_step
     BatchPacket<BatchOut> out;
     BatchPacket<ObsStep> steps;
+    BatchPacket<RicStep> rsteps; // eqf_batch_step_accurate: the sensor terms of A and B per sample
     BatchPacket<NeesIn> nin; // eqf_batch_nees, eqf_batch_consistency
     BatchPacket<NeesOut> nout;
     BatchPacket<eqf_batch_consistency_record> rec;
@@ -220,6 +222,7 @@ void eqf_batch_destroy(eqf_batch* b) {
     b->in.release();
     b->out.release();
     b->steps.release();
+    b->rsteps.release();
     b->nin.release();
     b->nout.release();
     b->rec.release();
@@ -378,7 +381,11 @@ int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* dept
     return 0;
 }
 
-int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
+namespace {
+// eqf_batch_step and eqf_batch_step_accurate: one screening, one packet, one round trip, one host half of the results. accurate: the frame's propagation is
+// integrateUpToTime's with fastRiccati == false - the sensor terms of A and B at every sample's X ride along with the observer steps, and k_batch_riccati runs
+// in front of k_batch_frame_tail on the same stream; imu13_mean and dt_total are not read. (A template parameter: the fast instance is the function it was.)
+template <bool accurate> int batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
     if (!b || count < 0 || (count > 0 && (!frames || !status)))
         return EQF_E_BAD_ARG;
     if (count == 0)
@@ -393,6 +400,9 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         return rc;
     if (int rc = b->steps.grow(std::max(total_steps, 64)))
         return rc;
+    if (accurate)
+        if (int rc = b->rsteps.grow(std::max(total_steps, 64)))
+            return rc;
     // host half: validation, the landmark bookkeeping the ids decide, the sensor-level terms and the observer steps' sensor part
     BatchScreen scr(b, count);
     std::vector<GroupSensor> X_after(count);
@@ -402,15 +412,17 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
     for (int e = 0; e < count; ++e) {
         const eqf_batch_frame& f = frames[e];
         status[e] = 0;
-        if (!scr.fresh(b, f.slot) || f.M < 0 || f.k < 0 || (f.M > 0 && (!f.ids || !f.y)) || !f.imu13_mean || (f.k > 0 && (!f.imu13_k || !f.dt_k)) ||
-            !camera_ok(&f.cam)) {
+        if (!scr.fresh(b, f.slot) || f.M < 0 || f.k < 0 || (f.M > 0 && (!f.ids || !f.y)) || (!accurate && !f.imu13_mean) ||
+            (f.k > 0 && (!f.imu13_k || !f.dt_k)) || !camera_ok(&f.cam)) {
             status[e] = EQF_E_BAD_ARG;
             continue;
         }
-        bool asc = true;
+        bool asc = true, dts_ok = true;
+        for (int s = 0; accurate && s < f.k; ++s) // a Riccati step per sample: its noise term is Q / dt
+            dts_ok = dts_ok && std::isfinite(f.dt_k[s]) && f.dt_k[s] >= 0.0;
         for (int j = 1; j < f.M; ++j)
             asc = asc && f.ids[j] > f.ids[j - 1];
-        if (!asc) {
+        if (!asc || !dts_ok) {
             status[e] = EQF_E_BAD_ARG;
             continue;
         }
@@ -452,7 +464,7 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         in.ss = sl.ss;
         Cam cam = make_cam(&f.cam);
         in.cam = cam;
-        in.dt = f.dt_total;
+        in.dt = accurate ? 0.0 : f.dt_total;
         for (size_t t = 0; t < surv.size(); ++t)
             in.surv[t] = (int)surv[t];
         for (int j = 0; j < f.M; ++j) {
@@ -467,10 +479,19 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
             }
         }
         Common cm;
-        compute_common_at(sl.X, sl.xi0, f.imu13_mean, cm, in.ck); // integrateRiccatiStateFast at the current X
+        if (!accurate)
+            compute_common_at(sl.X, sl.xi0, f.imu13_mean, cm, in.ck); // integrateRiccatiStateFast at the current X
+        else
+            std::memset(&in.ck, 0, sizeof(in.ck));
         GroupSensor X = sl.X;
-        for (int s = 0; s < f.k; ++s)
+        for (int s = 0; s < f.k; ++s) {
+            if (accurate) { // integrateRiccatiStateAccurate at the X the samples before this one have produced
+                RicStep& rs = b->rsteps.h[nsteps + s];
+                rs.dt = f.dt_k[s];
+                compute_common_at(X, sl.xi0, f.imu13_k + 13 * s, cm, rs.ck);
+            }
             observer_host_step(X, sl.xi0, f.imu13_k + 13 * s, f.dt_k[s], sl.set.useDiscreteVelocityLift, b->steps.h[nsteps + s]);
+        }
         nsteps += f.k;
         X_after[e] = X;
         for (int i : surv)
@@ -485,7 +506,17 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
     const BatchArgs ba{b->buf, b->in.d, b->steps.d, b->out.d};
     if (nsteps) // the observer steps ride along, in front of the launch on the same stream
         HIPCHK(hipMemcpyAsync(b->steps.d, b->steps.h, sizeof(ObsStep) * nsteps, hipMemcpyHostToDevice, b->stream));
-    const auto launch = [&] { hipLaunchKernelGGL(k_batch_frame, dim3(nin), dim3(BATCH_T), 0, b->stream, ba); };
+    if (accurate && nsteps)
+        HIPCHK(hipMemcpyAsync(b->rsteps.d, b->rsteps.h, sizeof(RicStep) * nsteps, hipMemcpyHostToDevice, b->stream));
+    const RicArgs ra{b->buf, b->in.d, b->steps.d, b->rsteps.d, b->out.d};
+    const auto launch = [&] {
+        if (accurate) {
+            hipLaunchKernelGGL(k_batch_riccati, dim3(nin), dim3(BATCH_T), 0, b->stream, ra);
+            hipLaunchKernelGGL(k_batch_frame_tail, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
+        } else {
+            hipLaunchKernelGGL(k_batch_frame, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
+        }
+    };
     if (int rc = batch_round_trip(b, b->in, nin, launch, &b->out))
         return rc;
     // host half of the results: landmark ids, the sensor lift
@@ -523,6 +554,8 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         sl.inn_dof = o.dof;
         sl.inn_nis = o.nis;
         sl.inn_logdet = o.logdet;
+        sl.ric_samples = accurate ? o.ric_samples : 0;
+        sl.ric_squarings = accurate ? o.ric_squarings : 0;
         if (flags & EQF_BATCH_UPDATED) {
             sl.tot_updates += 1;
             sl.tot_dof += o.dof;
@@ -532,6 +565,19 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
         if ((int)sl.ids.size() != o.N)
             status[e] = EQF_E_BAD_ARG; // bookkeeping disagreement: cannot happen
     }
+    return 0;
+}
+} // namespace
+
+int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<false>(b, count, frames, status); }
+int eqf_batch_step_accurate(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<true>(b, count, frames, status); }
+int eqf_batch_last_riccati(const eqf_batch* b, int slot, int* samples, int* max_squarings) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    if (samples)
+        *samples = b->s[slot].ric_samples;
+    if (max_squarings)
+        *max_squarings = b->s[slot].ric_squarings;
     return 0;
 }
 
@@ -983,6 +1029,7 @@ int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst
         to.depth = 0.0;
         to.inn_dof = 0;
         to.inn_nis = to.inn_logdet = 0.0;
+        to.ric_samples = to.ric_squarings = 0;
     }
     return 0;
 }
@@ -1060,6 +1107,7 @@ int eqf_batch_load_ctx(eqf_batch* b, eqf_ctx* src, int count, const int* slots, 
         to.depth = 0.0;
         to.inn_dof = 0;
         to.inn_nis = to.inn_logdet = 0.0;
+        to.ric_samples = to.ric_squarings = 0;
     }
     return 0;
 }

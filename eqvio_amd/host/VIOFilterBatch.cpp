@@ -115,6 +115,7 @@ void check(int rc, const char* what) {
 VIOFilterBatch::VIOFilterBatch(eqf_batch* b) : batch(b) {
     const int slots = eqf_batch_slots(b);
     slotv.resize(slots);
+    riccati_.assign(slots, EQVIO_BATCH_RICCATI_FAST);
     for (int k = 0; k < slots; ++k) {
         try {
             resetSlot(k);
@@ -132,6 +133,16 @@ eqvio_settings VIOFilterBatch::slotSettings(int k) const {
     check(eqf_batch_get_slot_settings(batch, k, &s), "eqf_batch_get_slot_settings");
     return s;
 }
+int VIOFilterBatch::setRiccatiMode(int k, int mode) {
+    if ((mode != EQVIO_BATCH_RICCATI_FAST && mode != EQVIO_BATCH_RICCATI_ACCURATE) || k >= (int)slotv.size())
+        return EQF_E_BAD_ARG;
+    if (k < 0)
+        riccati_.assign(slotv.size(), mode);
+    else
+        riccati_[k] = mode;
+    return 0;
+}
+int VIOFilterBatch::riccatiMode(int k) const { return k >= 0 && k < (int)slotv.size() ? riccati_[k] : EQF_E_BAD_ARG; }
 VIOFilterBatch::InnovationTotals VIOFilterBatch::innovationTotals(int k) const {
     InnovationTotals t;
     check(eqf_batch_innovation_totals(batch, k, &t.updates, &t.dof, &t.nis, &t.logdet), "eqf_batch_innovation_totals");
@@ -279,7 +290,33 @@ void VIOFilterBatch::stepPrepared(const int* slots, const double* stamps, int* s
         frames_[t].dt_k = dts_[t].data();
     }
     st_.resize(frames_.size());
-    check(eqf_batch_step(batch, (int)frames_.size(), frames_.data(), st_.data()), "eqf_batch_step");
+    // every listed slot to the call of its mode: a step whose slots are all of one mode is one device call, a mixed step two
+    bool mixed = false;
+    for (size_t t = 1; t < frames_.size(); ++t)
+        mixed = mixed || riccati_[frames_[t].slot] != riccati_[frames_[0].slot];
+    if (!mixed) {
+        if (riccati_[frames_[0].slot] == EQVIO_BATCH_RICCATI_ACCURATE)
+            check(eqf_batch_step_accurate(batch, (int)frames_.size(), frames_.data(), st_.data()), "eqf_batch_step_accurate");
+        else
+            check(eqf_batch_step(batch, (int)frames_.size(), frames_.data(), st_.data()), "eqf_batch_step");
+    } else {
+        std::vector<int> pst;
+        for (const int mode : {EQVIO_BATCH_RICCATI_FAST, EQVIO_BATCH_RICCATI_ACCURATE}) {
+            part_.clear(), partOf_.clear();
+            for (size_t t = 0; t < frames_.size(); ++t)
+                if (riccati_[frames_[t].slot] == mode) {
+                    part_.push_back(frames_[t]);
+                    partOf_.push_back(t);
+                }
+            pst.assign(part_.size(), 0);
+            if (mode == EQVIO_BATCH_RICCATI_ACCURATE)
+                check(eqf_batch_step_accurate(batch, (int)part_.size(), part_.data(), pst.data()), "eqf_batch_step_accurate");
+            else
+                check(eqf_batch_step(batch, (int)part_.size(), part_.data(), pst.data()), "eqf_batch_step");
+            for (size_t t = 0; t < part_.size(); ++t)
+                st_[partOf_[t]] = pst[t];
+        }
+    }
     for (size_t t = 0; t < frames_.size(); ++t) {
         const int e = entry_[t];
         status[e] = st_[t];
@@ -458,6 +495,8 @@ int eqvio_batch_set_slot_settings(eqvio_batch* b, int slot, const eqvio_settings
     const int rc = guarded(b, [&] { code = b->f->setSlotSettings(slot, *s); }); // the checks are eqf_batch_set_slot_settings's
     return rc ? rc : code;
 }
+int eqvio_batch_set_slot_riccati(eqvio_batch* b, int slot, int mode) { return b ? b->f->setRiccatiMode(slot, mode) : EQF_E_BAD_ARG; }
+int eqvio_batch_get_slot_riccati(const eqvio_batch* b, int slot) { return b ? b->f->riccatiMode(slot) : EQF_E_BAD_ARG; }
 int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out) {
     return b ? eqf_batch_get_slot_settings(b->f->core(), slot, out) : EQF_E_BAD_ARG;
 }

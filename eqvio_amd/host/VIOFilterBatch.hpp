@@ -52,6 +52,11 @@ class VIOFilterBatch {
     // call throws and the slot has its former settings again.
     int setSlotSettings(int slot, const eqvio_settings& s);
     eqvio_settings slotSettings(int slot) const;
+    // The propagation a slot's frames take (include/eqvio_batch.h): EQVIO_BATCH_RICCATI_FAST (eqf_batch_step; every slot starts with it) or _ACCURATE
+    // (eqf_batch_step_accurate). slot < 0: every slot. Kept like the settings: copySlots and loadFilter leave the destination's mode alone. Returns 0 or
+    // EQF_E_BAD_ARG (bad mode or slot; nothing changes); riccatiMode returns the mode or EQF_E_BAD_ARG.
+    int setRiccatiMode(int slot, int mode);
+    int riccatiMode(int slot) const;
     // Entry e: slot dst[e] becomes slot src[e] as it was before the call - the EqF state on the device (eqf_batch_copy_slots: one launch, same status codes)
     // and the host half: IMU buffer, current time, initialised flag. The destination keeps its settings and innovation totals. A refused entry changes nothing.
     void copySlots(int count, const int* src, const int* dst, int* status);
@@ -99,6 +104,9 @@ class VIOFilterBatch {
     void resetSlot(int slot);
     eqf_batch* batch = nullptr;
     std::vector<Slot> slotv;
+    std::vector<int> riccati_; // per slot: EQVIO_BATCH_RICCATI_*
+    std::vector<eqf_batch_frame> part_; // stepPrepared: the frames of one mode
+    std::vector<size_t> partOf_;
 };
 
 } // namespace eqvio_amd

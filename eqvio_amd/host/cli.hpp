@@ -3,6 +3,7 @@
 #pragma once
 #include "VIOFilter.hpp"
 #include "eqf_batch.h"
+#include "eqvio_batch.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -169,6 +170,29 @@ inline std::string warmupSweepRefusal(const Sweep& sw) {
             return "--warmup with --sweep " + sw.name + ": it is read only when a filter starts, so it has no effect behind a warm-up";
     return "";
 }
+
+// --batchRiccati M[,M...] with --batch B: the slots' propagation (eqvio_batch_set_slot_riccati), M = fast | accurate; one value for every slot, or B values,
+// one per slot. Returns what the flag is refused for, before any file or device is opened (empty: nothing); modes then holds B entries.
+inline std::string batchRiccatiRefusal(const std::string& text, int B, std::vector<int>& modes) {
+    if (B == 0)
+        return "--batchRiccati needs --batch B (the mode is the filter batch's, per slot)";
+    std::vector<int> given;
+    for (size_t p = 0; p <= text.size();) {
+        const size_t c = std::min(text.find(',', p), text.size());
+        const std::string w = text.substr(p, c - p);
+        if (w != "fast" && w != "accurate")
+            return "--batchRiccati: '" + w + "' is neither fast nor accurate";
+        given.push_back(w == "accurate" ? EQVIO_BATCH_RICCATI_ACCURATE : EQVIO_BATCH_RICCATI_FAST);
+        p = c + 1;
+    }
+    if (given.size() != 1 && (int)given.size() != B)
+        return "--batchRiccati has " + std::to_string(given.size()) + " values for --batch " + std::to_string(B) + ": one value, or one per slot";
+    modes.assign(std::max(B, 0), given[0]);
+    for (int k = 0; k < B && given.size() > 1; ++k)
+        modes[k] = given[k];
+    return "";
+}
+inline const char* batchRiccatiName(int mode) { return mode == EQVIO_BATCH_RICCATI_ACCURATE ? "accurate" : "fast"; }
 
 // the filter settings as the C-ABI's eqvio_settings
 inline eqvio_settings batchSettings(const VIOFilter::Settings& fs) {

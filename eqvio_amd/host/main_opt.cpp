@@ -32,7 +32,8 @@ static void usage() {
               "                 [--cameraFile sensor.yaml | camchain.yaml]   (intrinsics, distortion and camera offset from the dataset's own file, main_opt.cpp:114-147)\n"
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
-              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]]\n"
+              "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]\n"
+              "                            [--batchRiccati fast|accurate[,...]]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
@@ -53,12 +54,15 @@ static void usage() {
               "              when a filter starts) is refused.\n"
               "  --warmupOnFilter   with --warmup F (F > 0): the F warm-up frames run on ONE single filter (the low-latency context path) with the command line's\n"
               "              settings instead of in slot 0; the filter is then loaded into all B slots on the device in one call, the sweep's values are applied and\n"
-              "              scoring starts. With --record DIR every slot starts its files at the branch.");
+              "              scoring starts. With --record DIR every slot starts its files at the branch.\n"
+              "  --batchRiccati M[,M...]   with --batch B: the slots' propagation, M = fast (one fast Riccati step per frame) or accurate (the reference's default,\n"
+              "              fastRiccati: false: one accurate Riccati step per IMU sample); one value for every slot, or B values, one per slot. With this flag\n"
+              "              --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each slot's lines name its mode.");
 }
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
 static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime,
-                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions, bool warmupOnFilter) {
+                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions, bool warmupOnFilter, const std::vector<int>& riccati) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -67,6 +71,11 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         return 1;
     }
     VIOFilterBatch filters(core); // every slot as VIOFilter(fs): it initialises itself from its first IMU sample
+    for (int k = 0; k < B && !riccati.empty(); ++k) // kept through the warm-up's copies, like the settings
+        check_rc(filters.setRiccatiMode(k, riccati[k]), "--batchRiccati");
+    auto label = [&](int k) {
+        return (swept ? " " + sweep.name + "=" + sweep.values[k] : std::string()) + (riccati.empty() ? std::string() : std::string(" riccati ") + batchRiccatiName(riccati[k]));
+    };
     // --warmupOnFilter: the warm-up's frames run here, on the context path, and no slot runs before the branch
     std::unique_ptr<VIOFilter> warm;
     if (warmupOnFilter) {
@@ -214,17 +223,17 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     }
     for (int k = 0; k < B; ++k) {
         const VIOFilterBatch::InnovationTotals t = filters.innovationTotals(k);
-        const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
+        const std::string what = label(k);
         std::printf("slot %d%s: frames updated %ld  failed %d  mean NIS/dof %.9g  log-likelihood %.9g\n", k, what.c_str(), t.updates, failed[k], t.meanNisPerDof(),
                     t.logLikelihood());
     }
     for (int k = 0; k < B && groundtruth; ++k) {
         const TrajectoryScore t = trajectoryPositionRMSE(trajectories[k], *groundtruth);
-        const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
+        const std::string what = label(k);
         std::printf("slot %d%s: position RMSE %.9g over %d frames\n", k, what.c_str(), t.rmse, t.frames);
     }
     for (int k = 0; k < B && predictions; ++k) {
-        const std::string what = swept ? " " + sweep.name + "=" + sweep.values[k] : "";
+        const std::string what = label(k);
         std::printf("slot %d%s: prediction RMSE %.9g px over %ld features\n", k, what.c_str(), std::sqrt(predSq[k] / (double)predCount[k]), predCount[k]);
     }
     std::printf("batch of %d slots: slots x vision updates/s %.1f\n", B, (double)B * visionDataCounter / elapsed);
@@ -245,7 +254,9 @@ int main(int argc, char** argv) {
     double cameraLag = 0, startTime = -1, stopTime = -1;
     bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false;
     int batch = 0;
-    std::string warmupText;
+    std::string warmupText, riccatiText;
+    bool haveRiccati = false;
+    std::vector<int> riccati;
     Sweep sweep;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -301,6 +312,10 @@ int main(int argc, char** argv) {
             else if (a == "--record") recordDir = val();
             else if (a == "--predictions") predictions = true;
             else if (a == "--warmupOnFilter") warmupOnFilter = true;
+            else if (a == "--batchRiccati") {
+                riccatiText = val();
+                haveRiccati = true;
+            }
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
                 haveSweep = true;
@@ -327,6 +342,14 @@ int main(int argc, char** argv) {
         }
         if (predictions)
             fs.useFeaturePredictions = true;
+        if (haveRiccati) { // before any file or device is opened
+            const std::string refusal = batchRiccatiRefusal(riccatiText, batch < 0 ? 0 : batch, riccati);
+            if (!refusal.empty()) {
+                std::fprintf(stderr, "eqvio_opt: %s\n", refusal.c_str());
+                return 2;
+            }
+            fs.fastRiccati = true; // the batch's settings describe eqf_batch_step; the modes go to the slots
+        }
         int warmup = 0;
         if (haveWarmup) { // before any file or device is opened, as the refusals of --batch
             char* end = nullptr;
@@ -406,7 +429,7 @@ int main(int argc, char** argv) {
             std::vector<StampedPose> gt;
             if (!gtName.empty())
                 gt = TrackReplayServer::groundtruth(gtName, format);
-            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter, riccati);
         }
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150

@@ -22,7 +22,7 @@ static void usage() {
     std::puts("usage: eqvio_sim [--duration S] [--trajectory wave|square|sine|line] [--numPoints N] [--numWalls W] [--wallDistance D]\n"
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
               "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
-              "                 [--sweep NAME=v0,v1,...] [--innovation] [--record DIR]\n"
+              "                 [--sweep NAME=v0,v1,...] [--innovation] [--record DIR] [--batchRiccati fast|accurate[,...]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
               "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
@@ -36,11 +36,15 @@ static void usage() {
               "              (eqvio_batch_innovation_totals). Needs no true state, unlike NEES.\n"
               "  --record DIR   with --batch B: writes every run's consistency record to DIR/run_<k>/ - nees.csv (NEES, PoseNEES, AttitudeNEES),\n"
               "              poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv and landmarkError.csv, in the formats of --output - from one\n"
-              "              launch per frame for all runs (eqvio_batch_run_sim_recorded).");
+              "              launch per frame for all runs (eqvio_batch_run_sim_recorded).\n"
+              "  --batchRiccati M[,M...]   with --batch B: the runs' propagation, M = fast (one fast Riccati step per frame) or accurate (the reference's\n"
+              "              default, fastRiccati: false: one accurate Riccati step per IMU sample); one value for every run, or B values, one per run.\n"
+              "              With this flag --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each run's line names its mode.");
 }
 
 // --batch B: the default-mode loop of main() for B seeds in lockstep, through eqvio_batch_run_sim (augment, vision step and NEES: one launch each per frame)
-static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep, bool innovation, const std::string& recordDir) {
+static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep, bool innovation, const std::string& recordDir,
+                    const std::vector<int>& riccati) {
     const bool swept = !sweep.name.empty();
     eqvio_sim_settings ss;
     eqvio_sim_default_settings(&ss);
@@ -89,6 +93,13 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
             return 1;
         }
     }
+    for (int k = 0; k < B && !riccati.empty(); ++k)
+        if ((rc = eqvio_batch_set_slot_riccati(b, k, riccati[k]))) {
+            std::fprintf(stderr, "eqvio_sim: --batchRiccati: slot %d: %s\n", k, eqf_error_string(rc));
+            eqvio_batch_destroy(b);
+            release();
+            return 1;
+        }
     const int maxFrames = (int)std::ceil(sim.duration * sim.imageFreq) + 2;
     std::vector<double> nees((size_t)maxFrames * B);
     int frames = 0;
@@ -113,10 +124,11 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
         }
         const double mean = s / std::max(n, 1);
         sumOfMeans += mean;
+        const std::string mode = riccati.empty() ? "" : std::string(" riccati ") + batchRiccatiName(riccati[k]);
         if (swept)
-            std::printf("run %d seed %u %s=%s: mean NEES %.9g over %d frames\n", k, sim.randomSeed, sweep.name.c_str(), sweep.values[k].c_str(), mean, n);
+            std::printf("run %d seed %u %s=%s%s: mean NEES %.9g over %d frames\n", k, sim.randomSeed, sweep.name.c_str(), sweep.values[k].c_str(), mode.c_str(), mean, n);
         else
-            std::printf("run %d seed %u: mean NEES %.9g over %d frames\n", k, sim.randomSeed + (unsigned)k, mean, n);
+            std::printf("run %d seed %u%s: mean NEES %.9g over %d frames\n", k, sim.randomSeed + (unsigned)k, mode.c_str(), mean, n);
     }
     std::printf("batch of %d runs: mean of the runs' mean NEES %.9g  frames %d  runs x frames/s %.1f\n", B, sumOfMeans / B, frames, (double)B * frames / elapsed);
     for (int k = 0; k < B && innovation; ++k) { // the slot's totals over the whole run: every slot starts with none
@@ -140,7 +152,9 @@ int main(int argc, char** argv) {
     int batch = 0;
     Sweep sweep;
     bool haveSweep = false;
-    std::string outputDir, datasetDir, recordDir;
+    std::string outputDir, datasetDir, recordDir, riccatiText;
+    bool haveRiccati = false;
+    std::vector<int> riccati;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         std::function<const char*()> val = [&]() -> const char* {
@@ -171,6 +185,10 @@ int main(int argc, char** argv) {
         else if (a == "--batch") batch = std::atoi(val());
         else if (a == "--innovation") innovation = true;
         else if (a == "--record") recordDir = val();
+        else if (a == "--batchRiccati") {
+            riccatiText = val();
+            haveRiccati = true;
+        }
         else if (a == "--sweep") {
             sweep = parseSweep(val());
             haveSweep = true;
@@ -192,6 +210,14 @@ int main(int argc, char** argv) {
     if (!recordDir.empty() && batch == 0) {
         std::fprintf(stderr, "eqvio_sim: --record needs --batch B (the records are the filter batch's; a single run writes them with --output)\n");
         return 2;
+    }
+    if (haveRiccati) { // before any device is opened
+        const std::string refusal = batchRiccatiRefusal(riccatiText, batch < 0 ? 0 : batch, riccati);
+        if (!refusal.empty()) {
+            std::fprintf(stderr, "eqvio_sim: %s\n", refusal.c_str());
+            return 2;
+        }
+        fs.fastRiccati = true; // the batch's settings describe eqf_batch_step; the modes go to the slots
     }
     if (batch != 0) { // what the filter batch refuses, before any device is opened
         const char* why = batch < 1 ? "--batch needs B >= 1"
@@ -215,7 +241,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        return runBatch(sim, fs, batch, quiet, sweep, innovation, recordDir);
+        return runBatch(sim, fs, batch, quiet, sweep, innovation, recordDir, riccati);
     }
     double lastLandmarkReset = landmarkResetTime > 0 ? 0.0 : std::nan("");
 

@@ -1,11 +1,13 @@
 /* eqf_batch.h — C-ABI of the filter batch: B independent EqF filters ("slots") of at most 64 landmarks each on one MI355X (gfx950),
  * advanced by one frame with ONE kernel launch (one workgroup per slot) and one host synchronisation per step.
  *
- * A slot is what one reference VIOFilter does in processVisionData with fast Riccati (src/VIOFilter.cpp:194-241): integrateRiccatiStateFast with the
- * frame's mean IMU sample, the k observer steps, removeOldLandmarks (settings.removeLostLandmarks), removeOutliers, addNewLandmarks (median or fixed depth),
+ * A slot is what one reference VIOFilter does in processVisionData (src/VIOFilter.cpp:194-241): the propagation - with fast Riccati (eqf_batch_step)
+ * integrateRiccatiStateFast with the frame's mean IMU sample and the k observer steps, with the reference's default (eqf_batch_step_accurate) one
+ * integrateRiccatiStateAccurate per sample between the observer steps -, removeOldLandmarks (settings.removeLostLandmarks), removeOutliers, addNewLandmarks (median or fixed depth),
  * performVisionUpdate and removeInvalidLandmarks. Its state is the one eqf_hip.h's context holds (xi0, X, Sigma; same flat layouts, eqvio_types.h).
  * The sensor-level work (the 46 doubles of xi0 / X, the terms of A and B, the observer steps' sensor part, the sensor lift) is done on the host, the
- * rest by the slot's workgroup. Only the accurate / discrete Riccati modes and the Normal chart are not available (EQF_E_UNSUPPORTED at creation).
+ * rest by the slot's workgroup. Only the discrete state matrix (useDiscreteStateMatrix) and the Normal chart are not available; settings with
+ * fastRiccati == 0 are still refused (EQF_E_UNSUPPORTED at creation): the accurate mode is a call of its own, not a setting.
  *
  * Return codes are eqf_hip.h's. Argument and settings checks come BEFORE the device is looked at: a call with bad arguments returns EQF_E_BAD_ARG /
  * EQF_E_UNSUPPORTED on a machine without a GPU as well; with valid arguments and no gfx950 device, eqf_batch_create returns EQF_E_NO_DEVICE.
@@ -97,6 +99,20 @@ int eqf_batch_sensor_estimate(const eqf_batch* b, int slot, double* sensor);
  *                      removeOutliers, addNewLandmarks) without the vision update; the other slots are not affected.
  * The call itself returns 0 when the step ran (whatever the per-slot codes), EQF_E_BAD_ARG for null arguments, or a HIP error. */
 int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status);
+/* eqf_batch_step with the reference's default propagation, fastRiccati == false (integrateUpToTime, src/VIOFilter.cpp:160-178): for sample i = 0 .. k-1, when
+ * dt_i > 0, Sigma <- Phi Sigma Phi^T + Phi_B (Q / dt_i) Phi_B^T + dt_i P with [Phi Phi_B] the top n rows of exp(dt_i [[A, B], [0, 0]])
+ * (integrateRiccatiStateAccurate, VIO_eqf.cpp:74-91), A and B at the X that samples 0 .. i-1 have produced, Q and P the slot's own gains; then the observer
+ * step with sample i. A sample with dt_i == 0 skips its Riccati step and still runs its observer step. The rest of the frame is eqf_batch_step's, by the same
+ * code. The frame struct, the screening, the status codes, the result flags, the innovation statistics and the totals are eqf_batch_step's; imu13_mean and
+ * dt_total are not read and may be null / 0. In addition a dt_k that is negative or not finite gives EQF_E_BAD_ARG, the slot untouched bit for bit.
+ * One packet to the device, one copy back and one synchronisation; two launches on the batch's stream between them (the per-sample propagation, then the frame's
+ * remaining phases). The settings of a batch keep saying fastRiccati = 1: that field describes eqf_batch_step. Any slot may be advanced by either call in any
+ * frame. */
+int eqf_batch_step_accurate(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status);
+/* Two counters of the slot's last eqf_batch_step_accurate, written by its kernel into the result record: how many samples had dt > 0, and the largest number
+ * of squarings an exponential of the step took (0: |dt [A B]|_inf <= 0.25 for every sample). After eqf_batch_step, or a copy into the slot
+ * (eqf_batch_copy_slots, eqf_batch_load_ctx), both read 0. Null output pointers are skipped; a null batch or a bad slot gives EQF_E_BAD_ARG; no device is looked at. */
+int eqf_batch_last_riccati(const eqf_batch* b, int slot, int* samples, int* max_squarings);
 /* flags (EQF_BATCH_*) of the slot's last step, and the depth its new landmarks got */
 int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* depth);
 

@@ -1,5 +1,5 @@
-/* eqvio_batch.h — C-ABI of the filter-level batch (eqvio_amd/host/VIOFilterBatch.hpp): B reference VIOFilters (fast Riccati, <= 64 landmarks each) whose
- * frames go to the device together, one kernel launch per step (include/eqf_batch.h). Each slot keeps what the reference's VIOFilter keeps on the host:
+/* eqvio_batch.h — C-ABI of the filter-level batch (eqvio_amd/host/VIOFilterBatch.hpp): B reference VIOFilters (fast or, per slot, accurate Riccati; <= 64
+ * landmarks each) whose frames go to the device together, one device call per step and mode (include/eqf_batch.h). Each slot keeps what the reference's VIOFilter keeps on the host:
  * its IMU buffer, current time, initialised flag and landmark ids.
  *
  * Return values: 0 / a count on success, -1 when the C++ layer threw (message via eqvio_batch_last_error), an EQF_E_* code for refused arguments
@@ -31,6 +31,17 @@ int eqvio_batch_create(eqvio_batch** out, const eqvio_settings* settings, int de
  * every slot, after per-slot settings were set, is a settings sweep. get returns the slot's settings. */
 int eqvio_batch_set_slot_settings(eqvio_batch* b, int slot, const eqvio_settings* settings);
 int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out);
+/* The propagation a slot's frames take: EQVIO_BATCH_RICCATI_FAST - eqf_batch_step, one integrateRiccatiStateFast per frame; every slot starts with it - or
+ * EQVIO_BATCH_RICCATI_ACCURATE - eqf_batch_step_accurate, the reference's default (fastRiccati: false): one integrateRiccatiStateAccurate per IMU sample,
+ * between the observer steps. As in the reference's layering (VIO_eqf offers both integrations, the filter above picks one) the mode is not a setting: a batch's
+ * settings keep saying fastRiccati = 1, which describes eqf_batch_step. eqvio_batch_process_vision, _run_prepared(_recorded) and _run_sim(_recorded) send every
+ * step's listed slots to the call of their mode; a step that lists slots of both modes makes two device calls, the fast slots first. set: slot < 0 means every
+ * slot; a mode outside the enum, a slot index past the last slot or a null batch gives EQF_E_BAD_ARG, nothing changed, no device looked at. get returns the mode,
+ * or EQF_E_BAD_ARG. The mode is kept like the settings: eqvio_batch_copy_slots and _load_filter leave the destination's mode alone, _store_filter leaves the
+ * filter's settings alone. */
+enum { EQVIO_BATCH_RICCATI_FAST = 0, EQVIO_BATCH_RICCATI_ACCURATE = 1 };
+int eqvio_batch_set_slot_riccati(eqvio_batch* b, int slot, int mode); /* slot < 0: every slot */
+int eqvio_batch_get_slot_riccati(const eqvio_batch* b, int slot);     /* mode, or EQF_E_BAD_ARG */
 /* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56), with the slot's settings */
 int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time);
 void eqvio_batch_destroy(eqvio_batch* b);
