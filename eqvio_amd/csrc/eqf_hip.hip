@@ -11,6 +11,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include <optional>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -287,7 +288,6 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     Cam pred_cam{}, me_cam{};
     int pred_star = 0, me_star = 0, me_M = 0;
     unsigned long me_gen = 0;
-    bool obs_one_chunk = false;              // the propagation launch in progress carries ALL observer steps of the call (more than kMaxSteps: further k_observer launches follow)
     // The plan of the update tail in flight (queue_tail; finish_update's retry replaces it with its own). Scratch like the buffers it describes: a tail is never in
     // flight across grow_capacity, eqf_destroy or the batch bridge's entry into a context - every one of them passes enter() (or sync_ctx), which settles first - so none
     // of them mentions it.
@@ -635,7 +635,7 @@ int sync_ctx(eqf_ctx* c) {
 }
 // Wait for the doorbell `which` to show `seq` (written by the last workgroup of the kernel launched with it, after every
 // result store has been fenced at system scope). The stream is polled now and then so that a kernel fault is reported
-// instead of spinning forever; if the stream completes without the bell (cannot happen) the call fails loudly.
+// instead of spinning forever; if the stream completes without the bell (a kernel's last workgroup always rings it) the call fails loudly.
 int door_wait(eqf_ctx* c, int which, int seq, bool* early = nullptr) {
     HP_SCOPE("abi.door_wait");
     volatile int* bell = reinterpret_cast<volatile int*>(c->h_door) + which;
@@ -1682,8 +1682,12 @@ int eqf_add_landmarks(eqf_ctx* c, const int* ids, const double* p, int k, double
 }
 
 // eqf_hip.h: landmarks that belong to the time BEHIND the next eqf_propagate_fast
-int eqf_hold_supported(const eqf_ctx* c) {
-    return (c && c->opt_hold && c->opt_gather && c->opt_fuse_asm && !c->opt_dense && c->chart != EQVIO_COORD_NORMAL && !c->sig32 && !c->opt_check && c->h_held) ? 1 : 0;
+// "The fused kernel is available", as far as the context's options and chart decide it: k_propagate_main with fused assembly in the form that can also apply a removal
+// record and create held landmarks (its GH instantiation: fp64 Sigma, and not between the normal chart's congruences). A call adds its own part: observer steps to
+// ride along and N > 0 (plan_propagation).
+static bool fused_kernel_available(const eqf_ctx* c) { return c->opt_fuse_asm && !c->opt_dense && c->chart != EQVIO_COORD_NORMAL && !c->sig32; }
+int eqf_hold_supported(const eqf_ctx* c) { // ... and on top of it: both options, the pinned packet of the held points, no finite check behind the propagation
+    return (c && c->opt_hold && c->opt_gather && fused_kernel_available(c) && !c->opt_check && c->h_held) ? 1 : 0;
 }
 int eqf_add_landmarks_held(eqf_ctx* c, const int* ids, const double* p, int k, double var) {
     HP_SCOPE("abi.add_landmarks_held");
@@ -1962,24 +1966,6 @@ static int ensure_dense(eqf_ctx* c) {
         EQFCHK(alloc_device(c, c->d_F, (size_t)c->ld * c->ncap));
     return c->d_tmp ? 0 : alloc_device(c, c->d_tmp, (size_t)c->ld * c->ncap);
 }
-static int riccati_after_assemble(eqf_ctx* c, double dt, const double* Qdiag12, const double* Pdiag8, const ObsSteps* obs = nullptr, int obs_k = 0, bool fused = false,
-                                  const GatherArgs* gather = nullptr);
-int eqf_integrate_riccati_fast(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
-    if (c && c->n_held > 0)
-        return EQF_E_UNSUPPORTED; // landmarks held for eqf_propagate_fast (eqf_add_landmarks_held): only that call knows to leave them alone
-    if (!c || !imu13 || !Qdiag12 || !Pdiag8)
-        return EQF_E_BAD_ARG;
-    EQFCHK(enter(c));
-    int rc = upload_common(c, imu13);
-    if (rc)
-        return rc;
-    rc = launch_assemble(c);
-    if (rc)
-        return rc;
-    return riccati_after_assemble(c, dt, Qdiag12, Pdiag8);
-}
-// Sigma' = F Sigma F^T + dt (B Q B^T + P) once A_l / B_l are assembled (arrow form, or the dense GEMM pair)
-// obs != nullptr (arrow form only): obs_k observer steps for the landmarks ride along as extra blocks of k_propagate_main
 // Normal chart (coordinateSuite/normal.cpp:37-45): Sigma <- T Sigma T^T with T = M (dir > 0, plus dt P on the diagonal) or M^-1 (dir < 0),
 // out of place into the other Sigma buffer. See k_congruence_normal.
 static int normal_congruence(eqf_ctx* c, int dir, double dt, const double* Pdiag8) {
@@ -1999,219 +1985,302 @@ static int normal_congruence(eqf_ctx* c, int dir, double dt, const double* Pdiag
     c->cur = 1 - c->cur;
     return 0;
 }
-static int riccati_after_assemble(eqf_ctx* c, double dt, const double* Qdiag12, const double* Pdiag8, const ObsSteps* obs, int obs_k, bool fused, const GatherArgs* gather) {
-    int rc = 0;
-    c->me_valid = false; // whatever propagates Sigma (any mode) leaves output blocks of an earlier propagation behind
-    static const ObsSteps kNoSteps{};
-    const bool normal = c->chart == EQVIO_COORD_NORMAL;
+// Every mode propagates Sigma in Euclidean coordinates. In the normal chart that is the Euclidean propagation of M^-1 Sigma M^-T without process noise, between two
+// congruences: riccati_open transforms and fills the kernels' arguments (P zeroed under the normal chart), riccati_close applies M ( . ) M^T + dt P and the
+// rounding of EQF_OPT_SIGMA_FP32 = 1. What lies between them leaves the propagated Sigma as the current buffer.
+static int riccati_open(eqf_ctx* c, bool normal, double dt, const double* Qdiag12, const double* Pdiag8, RiccatiArgs& ra) {
     static const double kZero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const double* Pfull = Pdiag8;
-    if (normal) { // Euclidean propagation of M^-1 Sigma M^-T without process noise; M ( . ) M^T + dt P follows below
-        rc = normal_congruence(c, -1, dt, nullptr);
-        if (rc)
-            return rc;
-        Pdiag8 = kZero8;
-    }
-    RiccatiArgs ra;
+    if (normal)
+        EQFCHK(normal_congruence(c, -1, dt, nullptr));
     ra.dt = dt;
     std::memcpy(ra.Qd, Qdiag12, sizeof(ra.Qd));
-    std::memcpy(ra.Pd, Pdiag8, sizeof(ra.Pd));
-    const int N = c->N, n = c->n();
+    std::memcpy(ra.Pd, normal ? kZero8 : Pdiag8, sizeof(ra.Pd));
+    return 0;
+}
+static int riccati_close(eqf_ctx* c, bool normal, double dt, const double* Pdiag8) {
+    if (normal)
+        EQFCHK(normal_congruence(c, +1, dt, Pdiag8));
+    return round_sigma(c);
+}
+// The dense modes: Sigma' = F Sigma F^T + noise with F materialised, tmp = F Sigma (= (Sigma F^T)^T, Sigma symmetric), Sigma' = tmp F^T. A mode supplies how F gets
+// into d_F (build_F(normal): the chart its kernels work in is Euclidean under the normal chart) and the noise kernel that follows (add_noise(ra, Sout)) - and where the
+// span of its per-kernel timing (option 100) begins and ends, which differs between the three for no reason other than where each had its KTimer:
+struct DenseTiming {
+    bool covers_F;     // the span begins in front of the kernels that build F (fast, accurate), not behind them (discrete)
+    bool covers_close; // ... and ends behind riccati_close (accurate, discrete), not in front of it (fast)
+};
+extern "C++" { // (a template inside this file's extern "C" block)
+template <class BuildF, class AddNoise>
+static int dense_sandwich(eqf_ctx* c, double dt, const double* Qdiag12, const double* Pdiag8, DenseTiming timing, BuildF build_F, AddNoise add_noise) {
+    EQFCHK(ensure_dense(c));
+    const bool normal = c->chart == EQVIO_COORD_NORMAL;
+    RiccatiArgs ra;
+    EQFCHK(riccati_open(c, normal, dt, Qdiag12, Pdiag8, ra));
+    const int n = c->n();
     double* Sin = c->d_sigma[c->cur];
     double* Sout = c->d_sigma[1 - c->cur];
-    if (!c->opt_dense) {
-        const int nT = blocks(N, PT);
-        const bool sym = nT > 16;           // more tiles than fit the chip in one round: lower triangle only, mirrored (k_propagate_main)
-        const int nObs = (obs && obs_k > 0) ? blocks(N, PROP_T) : 0;
-        // Lower triangle: tpw consecutive tiles of a block row per workgroup, the smallest tpw with which every workgroup of the launch is resident at once (one of
-        // these workgroups per compute unit: a second ROUND costs a whole tile chain, a second tile of the same block row about a third of one; k_propagate_main)
-        int tpw = 1, nTiles = sym ? nT * (nT + 1) / 2 : nT * nT;
-        if (sym && c->opt_prop_tpw) {
-            auto wgs = [&](int t) {
-                int w = 0;
-                for (int r = 0; r < nT; ++r)
-                    w += (r + t) / t;
-                return w;
-            };
-            while (tpw < 8 && wgs(tpw) + 2 + nObs > c->cu_count)
-                ++tpw;
-            if (c->opt_prop_tpw > 1)
-                tpw = c->opt_prop_tpw; // forced (A/B)
-            nTiles = wgs(tpw);
-        }
-        StageArgs sg{};
-        if (c->stage_pending) { // one more block copies the staged measurement from the pinned packet to HBM
-            sg.M = c->staged_M;
-            sg.y_h = c->h_y, sg.ylm_h = c->h_ylm, sg.idx_h = c->h_lmidx;
-            sg.y_d = c->d_meas, sg.ylm_d = c->d_meas + 2 * (size_t)c->Ncap, sg.idx_d = c->d_meas_idx;
-            c->stage_pending = false;
-            c->staged_valid = true;
-            c->busy_meas = true;
-        }
-        // fused assembly (eqf_propagate_fast): every workgroup assembles the rows of A / B it needs from the current Q and c->ck; the
-        // observer blocks then write the other landmark buffer, which becomes the current one
-        FuseArgs fa{};
-        if (fused) {
-            fa.on = 1;
-            fa.chart = c->chart;
-            double* other = c->d_lm[1 - c->lmcur];
-            fa.Qqo = other, fa.Qao = other + 4 * (size_t)c->Ncap;
-            fa.ck = c->ck;
-        }
-        // EQF_OPT_MEASURE_IN_PROPAGATE: the observer blocks evaluate the output blocks of the staged measurement with the camera / output choice of the last update call
-        MeasEval me{};
-        if (c->opt_measure_prop && fused && nObs && c->obs_one_chunk && sg.M > 0 && c->pred_valid && !c->sig32 && !c->opt_f32 && c->opt_zb && !c->opt_check) {
-            me.on = 1, me.star = c->pred_star, me.Mcap = c->Ncap, me.cam = c->pred_cam;
-            me.ylm = c->h_ylm, me.C = c->d_C, me.ytil = c->d_ytil, me.lmidx_dev = c->d_lmidx;
-            c->me_valid = true, c->me_cam = c->pred_cam, c->me_star = c->pred_star, c->me_M = sg.M, c->me_gen = c->staged_gen;
-        }
-        // EQF_OPT_GATHER_IN_PROPAGATE: the landmarks removed since the last kernel leave inside this launch (eqf_propagate_fast decided; fused assembly + observer blocks)
-        GatherArgs ga{};
-        if (gather) {
-            if (!(fused && nObs))
-                return EQF_E_UNSUPPORTED; // (eqf_propagate_fast checks the same conditions before it asks for this)
-            ga = *gather;
-            ga.st_in = c->d_st[c->stcur], ga.st_out = ga.n ? c->d_st[1 - c->stcur] : c->d_st[c->stcur]; // (nothing removed: the planes stay where they are, only held landmarks are written)
-        }
-        ga.nprop = N - c->n_held; // (held landmarks that an ordinary pass appended: read from memory, passed through untouched)
-        if (c->n_held > 0 && !(fused && nObs))
-            return EQF_E_UNSUPPORTED;
-        KTimer t(c, KN_PROP_MAIN);
-        auto launch = [&](auto kern, auto* sin, auto* sout) {
-            hipLaunchKernelGGL(kern, dim3(nTiles + 1 + nObs + (sg.M ? 1 : 0)), dim3(PROP_T), 0, c->stream, N, c->Ncap, c->ld, ra, c->d_common, sin, sout, c->d_Al, c->d_Bl, nT, tpw,
-                               nObs ? *obs : kNoSteps, nObs ? obs_k : 0, c->q0(), c->Qq(), c->Qa(), nObs, sg, trace_slot(c, TR_PROPAGATE), fa, me, ga);
-        };
-#define PROP_LAUNCH(TS_, F_) \
-    do { \
-        if (sym) \
-            launch(k_propagate_main<TS_, F_, true>, (const TS_*)Sin, (TS_*)Sout); \
-        else \
-            launch(k_propagate_main<TS_, F_, false>, (const TS_*)Sin, (TS_*)Sout); \
-    } while (0)
-        if (c->sig32) {
-            if (fused)
-                PROP_LAUNCH(float, true);
-            else
-                PROP_LAUNCH(float, false);
-        } else if (fused && (ga.n > 0 || ga.nprop < N)) { // landmarks leave / are created / pass through inside this launch: the instantiation that knows how
-            if (sym)
-                launch(k_propagate_main<double, true, true, true>, (const double*)Sin, (double*)Sout);
-            else
-                launch(k_propagate_main<double, true, false, true>, (const double*)Sin, (double*)Sout);
-        } else {
-            if (fused)
-                PROP_LAUNCH(double, true);
-            else
-                PROP_LAUNCH(double, false);
-        }
-#undef PROP_LAUNCH
-        HIPCHK(hipGetLastError());
-        if (fused && nObs)
-            c->lmcur = 1 - c->lmcur;
-        if (gather) { // what flush_reshape does behind its pass
-            if (gather->n) {
-                c->stcur = 1 - c->stcur;
-                ++c->gather_launches;
-            }
-            if (gather->held) {
-                ++c->held_launches;
-                c->held_busy = true;
-            }
-            c->dev_N = N;
-            c->reshape_pending = false;
-        }
-        c->n_held = 0, c->held_in_memory = false; // they are ordinary landmarks from here on
-    } else {
-        // dense: F materialised, tmp = F Sigma (= (Sigma F^T)^T, Sigma symmetric), Sigma' = tmp F^T + noise
-        EQFCHK(ensure_dense(c));
-        KTimer t(c, KN_DENSE_GEMM);
-        hipLaunchKernelGGL(k_build_F, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, dt, c->d_common, c->d_Al, c->d_F);
-        HIPCHK(hipGetLastError());
-        // tmp[i][j] = sum_k F[i][k] Sigma[j][k]
-        hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_F, c->ld, Sin, c->ld, c->d_tmp, c->ld);
-        HIPCHK(hipGetLastError());
-        // Sout[i][j] = sum_k tmp[i][k] F[j][k]
-        hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_tmp, c->ld, c->d_F, c->ld, Sout, c->ld);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_add_noise, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, ra, c->d_common, c->d_Bl, Sout);
-        HIPCHK(hipGetLastError());
-    }
+    std::optional<KTimer> t;
+    if (timing.covers_F)
+        t.emplace(c, KN_DENSE_GEMM);
+    EQFCHK(build_F(normal));
+    if (!t)
+        t.emplace(c, KN_DENSE_GEMM);
+    // tmp[i][j] = sum_k F[i][k] Sigma[j][k]
+    hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_F, c->ld, Sin, c->ld, c->d_tmp, c->ld);
+    HIPCHK(hipGetLastError());
+    // Sout[i][j] = sum_k tmp[i][k] F[j][k]
+    hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_tmp, c->ld, c->d_F, c->ld, Sout, c->ld);
+    HIPCHK(hipGetLastError());
+    add_noise(ra, Sout);
+    HIPCHK(hipGetLastError());
     c->cur = 1 - c->cur;
-    if (normal) {
-        rc = normal_congruence(c, +1, dt, Pfull);
-        if (rc)
-            return rc;
+    if (!timing.covers_close)
+        t.reset();
+    return riccati_close(c, normal, dt, Pdiag8);
+}
+} // extern "C++"
+
+// landmarks held for eqf_propagate_fast (eqf_add_landmarks_held): only that call knows to leave them alone
+static bool holds_landmarks(const eqf_ctx* c) { return c && c->n_held > 0; }
+// What the Riccati entry points do in front of their mode: the refusals in this order, the pending bookkeeping (enter), the sensor terms at the current X and
+// the assembly of A_l / B_l. record_early: see launch_assemble.
+struct RiccatiEntry {
+    bool dt_positive, refuse_float_store, record_early;
+};
+static int riccati_entry(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8, RiccatiEntry e) {
+    if (holds_landmarks(c))
+        return EQF_E_UNSUPPORTED;
+    if (!c || !imu13 || !Qdiag12 || !Pdiag8 || (e.dt_positive && !(dt > 0.0)))
+        return EQF_E_BAD_ARG;
+    if (e.refuse_float_store && c->sig32)
+        return EQF_E_UNSUPPORTED; // the float store exists for the structured fast path only
+    EQFCHK(enter(c));
+    EQFCHK(upload_common(c, imu13));
+    return launch_assemble(c, e.record_early);
+}
+
+// The fast mode's launch - Sigma' = F Sigma F^T + dt (B Q B^T + P) once the sensor terms are fixed - is decided ONCE (plan_propagation), from the context as it is BEFORE
+// enter(): c->N, n_held, the pending record (pend_*, reshape_pending) and dev_N. The gather route exists precisely to skip enter()'s compaction pass, so the decision
+// cannot come behind it; nothing enter() does changes what the plan has read otherwise (N and n_held are the host's, the flush only moves the device to them). The
+// two fields that depend on the staged measurement are filled behind stage_prepare, which maps it behind the frame's first launch (plan_stage). launch_propagation
+// launches from the plan alone and commits the context's state behind the launch; a refused call has written nothing.
+struct PropCall {
+    bool frame; // eqf_propagate_fast asks (fused assembly, observer steps, the removal record and held landmarks are its alone), not eqf_integrate_riccati_fast
+    int k;      // observer steps of the call
+};
+struct PropPlan {
+    bool dense = false;    // EQF_OPT_RICCATI_DENSE: dense_sandwich. Otherwise the arrow form, ONE k_propagate_main launch, which the fields below describe
+    bool sig32 = false;    // Sigma stored as float
+    bool normal = false;   // the normal chart's congruences wrap the launch
+    bool fused = false;    // fused assembly: every workgroup assembles the rows of A / B it needs from the current Q and c->ck; no k_assemble_AB in front
+    bool sym = false;      // more tiles than fit the chip in one round (nT > 16): lower triangle only, mirrored
+    int nT = 0, tpw = 1, nTiles = 0; // 16-landmark tiles a side; consecutive tiles of a block row per workgroup; tile workgroups
+    int nObs = 0;          // observer blocks
+    bool ride = false;     // the first chunk of observer steps rides along as those blocks (further chunks are k_observer launches behind this one) ...
+    int ride_k = 0;        // ... with this many steps
+    bool one_chunk = false; // ... which are ALL steps of the call: the group elements are final when the observer blocks are done
+    int stage_M = 0;       // one more block copies the staged measurement (so many points) from the pinned packet to HBM
+    bool meas_eval = false; // EQF_OPT_MEASURE_IN_PROPAGATE: the observer blocks evaluate its output blocks with the camera / output choice of the last update call (MeasEval::on)
+    bool use_gather = false; // EQF_OPT_GATHER_IN_PROPAGATE / eqf_add_landmarks_held: the removal record is applied, the held landmarks are created, inside this launch
+    GatherArgs gather{};   // ... the record without its buffer pointers. nprop (always set): the landmarks that are propagated; the others are held and pass through
+    bool gh = false;       // landmarks leave / are created / pass through inside this launch: the instantiation that knows how
+    int grid = 0;
+};
+static int plan_propagation(const eqf_ctx* c, const PropCall& call, PropPlan& p) {
+    p = PropPlan{};
+    const int N = c->N, Nprop = N - c->n_held;
+    const bool steps = call.frame && call.k > 0 && N > 0;
+    const bool fused_kernel = fused_kernel_available(c) && steps; // the fused kernel WITH observer blocks: what a removal record and held landmarks need
+    if (c->n_held > 0 && !fused_kernel)
+        return EQF_E_UNSUPPORTED; // (eqf_add_landmarks_held checked the options: one was changed in between, or there are no observer steps to ride along)
+    p.dense = c->opt_dense != 0, p.sig32 = c->sig32, p.normal = c->chart == EQVIO_COORD_NORMAL;
+    p.gather.nprop = Nprop;
+    if (p.dense)
+        return 0;
+    p.fused = call.frame && c->opt_fuse_asm;
+    p.ride = steps, p.ride_k = steps ? std::min(call.k, eqf_ctx::kMaxSteps) : 0, p.one_chunk = steps && call.k <= eqf_ctx::kMaxSteps;
+    p.nObs = p.ride ? blocks(N, PROP_T) : 0;
+    p.nT = blocks(N, PT), p.sym = p.nT > 16;
+    // Lower triangle: tpw consecutive tiles of a block row per workgroup, the smallest tpw with which every workgroup of the launch is resident at once (one of
+    // these workgroups per compute unit: a second ROUND costs a whole tile chain, a second tile of the same block row about a third of one; k_propagate_main)
+    p.nTiles = p.sym ? p.nT * (p.nT + 1) / 2 : p.nT * p.nT;
+    if (p.sym && c->opt_prop_tpw) {
+        auto wgs = [&](int t) {
+            int w = 0;
+            for (int r = 0; r < p.nT; ++r)
+                w += (r + t) / t;
+            return w;
+        };
+        while (p.tpw < 8 && wgs(p.tpw) + 2 + p.nObs > c->cu_count)
+            ++p.tpw;
+        if (c->opt_prop_tpw > 1)
+            p.tpw = c->opt_prop_tpw; // forced (A/B)
+        p.nTiles = wgs(p.tpw);
     }
-    EQFCHK(round_sigma(c));
+    // EQF_OPT_GATHER_IN_PROPAGATE: a pending record of removals only (the frame's lost landmarks, the last frame's discarded outliers) is applied by the propagation kernel
+    // itself instead of a compaction pass in front of it - when nothing was appended. eqf_add_landmarks_held: the held landmarks (the last n_held of the state) are
+    // created by the same kernel (GatherArgs::held) unless an ordinary pass has appended them.
+    const bool hold_here = c->n_held > 0 && !c->held_in_memory;
+    if (fused_kernel && c->opt_gather && (c->reshape_pending || hold_here) && c->pend_var.empty() && c->dev_N <= GATHER_MAXN &&
+        (!c->reshape_pending || ((int)c->pend_map.size() == Nprop && c->dev_N >= Nprop))) {
+        GatherArgs g = p.gather;
+        bool ok = true;
+        if (c->reshape_pending) {
+            int prev = -1;
+            for (int i = 0; i < Nprop && ok; ++i) {
+                const int o = c->pend_map[i];
+                ok = o > prev && o < c->dev_N; // survivors keep their order
+                if (ok)
+                    g.surv[o >> 6] |= 1ull << (o & 63);
+                prev = o;
+            }
+            g.n = c->dev_N - Nprop;
+        } else
+            ok = c->dev_N == Nprop;
+        if (ok && (g.n > 0 || hold_here)) {
+            g.held = hold_here ? c->h_held : nullptr;
+            p.use_gather = true, p.gather = g;
+        }
+    }
+    p.gh = !p.sig32 && p.fused && (p.gather.n > 0 || Nprop < N);
+    return 0;
+}
+static void plan_stage(const eqf_ctx* c, PropPlan& p) {
+    if (p.dense)
+        return;
+    p.stage_M = c->stage_pending ? c->staged_M : 0;
+    p.meas_eval = c->opt_measure_prop && p.fused && p.nObs && p.one_chunk && p.stage_M > 0 && c->pred_valid && !p.sig32 && !c->opt_f32 && c->opt_zb && !c->opt_check;
+    p.grid = p.nTiles + 1 + p.nObs + (p.stage_M ? 1 : 0);
+}
+static int launch_propagation(eqf_ctx* c, const PropPlan& p, RiccatiArgs ra, const ObsSteps* obs) {
+    static const ObsSteps kNoSteps{};
+    int N = c->N;
+    StageArgs sg{};
+    if (p.stage_M) {
+        sg.M = p.stage_M;
+        sg.y_h = c->h_y, sg.ylm_h = c->h_ylm, sg.idx_h = c->h_lmidx;
+        sg.y_d = c->d_meas, sg.ylm_d = c->d_meas + 2 * (size_t)c->Ncap, sg.idx_d = c->d_meas_idx;
+    }
+    FuseArgs fa{};
+    if (p.fused) { // the observer blocks write the other landmark buffer, which becomes the current one
+        fa.on = 1;
+        fa.chart = c->chart;
+        double* other = c->d_lm[1 - c->lmcur];
+        fa.Qqo = other, fa.Qao = other + 4 * (size_t)c->Ncap;
+        fa.ck = c->ck;
+    }
+    MeasEval me{};
+    if (p.meas_eval) {
+        me.on = 1, me.star = c->pred_star, me.Mcap = c->Ncap, me.cam = c->pred_cam;
+        me.ylm = c->h_ylm, me.C = c->d_C, me.ytil = c->d_ytil, me.lmidx_dev = c->d_lmidx;
+    }
+    GatherArgs ga = p.gather;
+    if (p.use_gather) // (nothing removed: the planes stay where they are, only held landmarks are written)
+        ga.st_in = c->d_st[c->stcur], ga.st_out = ga.n ? c->d_st[1 - c->stcur] : c->d_st[c->stcur];
+    // The instantiations, by (TS = double | float, FUSED, SYM, GH). nullptr: there is no such kernel, and the plan never asks for one (a removal record and held
+    // landmarks need the fused kernel: fused assembly, fp64 Sigma). The arguments are the same for all of them, the two pointers to Sigma but for their type.
+    static const void* const kernels[2][2][2][2] = {
+        {{{(const void*)k_propagate_main<double, false, false>, nullptr}, {(const void*)k_propagate_main<double, false, true>, nullptr}},
+         {{(const void*)k_propagate_main<double, true, false>, (const void*)k_propagate_main<double, true, false, true>},
+          {(const void*)k_propagate_main<double, true, true>, (const void*)k_propagate_main<double, true, true, true>}}},
+        {{{(const void*)k_propagate_main<float, false, false>, nullptr}, {(const void*)k_propagate_main<float, false, true>, nullptr}},
+         {{(const void*)k_propagate_main<float, true, false>, nullptr}, {(const void*)k_propagate_main<float, true, true>, nullptr}}}};
+    const void* kernel = kernels[p.sig32][p.fused][p.sym][p.gh];
+    if (!kernel)
+        return EQF_E_UNSUPPORTED;
+    int Ncap = c->Ncap, ld = c->ld, nT = p.nT, tpw = p.tpw, nObs = p.nObs, obs_k = p.ride_k;
+    const Common* cm = c->d_common;
+    const void* Sin = c->d_sigma[c->cur];
+    void* Sout = c->d_sigma[1 - c->cur];
+    const double *Al = c->d_Al, *Bl = c->d_Bl, *q0 = c->q0();
+    double *Qq = c->Qq(), *Qa = c->Qa();
+    trace_t* tr = trace_slot(c, TR_PROPAGATE);
+    void* args[] = {&N, &Ncap, &ld, &ra, &cm, &Sin, &Sout, &Al, &Bl, &nT, &tpw, const_cast<ObsSteps*>(p.ride ? obs : &kNoSteps), &obs_k, &q0, &Qq, &Qa, &nObs, &sg, &tr, &fa, &me, &ga};
+    {
+        KTimer t(c, KN_PROP_MAIN);
+        HIPCHK(hipLaunchKernel(kernel, dim3(p.grid), dim3(PROP_T), args, 0, c->stream));
+    }
+    // the launch is out: what it leaves behind
+    if (p.stage_M)
+        c->stage_pending = false, c->staged_valid = true, c->busy_meas = true;
+    if (p.meas_eval)
+        c->me_valid = true, c->me_cam = c->pred_cam, c->me_star = c->pred_star, c->me_M = p.stage_M, c->me_gen = c->staged_gen;
+    if (p.fused && p.nObs)
+        c->lmcur = 1 - c->lmcur;
+    if (p.use_gather) { // what flush_reshape does behind its pass
+        if (p.gather.n) {
+            c->stcur = 1 - c->stcur;
+            ++c->gather_launches;
+        }
+        if (p.gather.held) {
+            ++c->held_launches;
+            c->held_busy = true;
+        }
+        c->dev_N = N;
+        c->reshape_pending = false;
+    }
+    c->n_held = 0, c->held_in_memory = false; // they are ordinary landmarks from here on
+    c->cur = 1 - c->cur;
+    return 0;
+}
+// The fast mode behind its sensor terms and assembly, for both its entry points: the arrow form from the plan or the dense sandwich. Around it, what the fast mode
+// alone does (the accurate and the discrete mode do neither): output blocks of an earlier propagation are dropped, EQF_OPT_CHECK_FINITE is honoured behind it.
+static int propagate_sigma_fast(eqf_ctx* c, const PropPlan& p, double dt, const double* Qdiag12, const double* Pdiag8, const ObsSteps* obs) {
+    c->me_valid = false;
+    if (p.dense) {
+        const int N = c->N, n = c->n();
+        EQFCHK(dense_sandwich(
+            c, dt, Qdiag12, Pdiag8, DenseTiming{true, false},
+            [&](bool) {
+                hipLaunchKernelGGL(k_build_F, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, dt, c->d_common, c->d_Al, c->d_F);
+                return (int)hipGetLastError();
+            },
+            [&](const RiccatiArgs& ra, double* Sout) { hipLaunchKernelGGL(k_add_noise, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, ra, c->d_common, c->d_Bl, Sout); }));
+    } else {
+        RiccatiArgs ra;
+        EQFCHK(riccati_open(c, p.normal, dt, Qdiag12, Pdiag8, ra));
+        EQFCHK(launch_propagation(c, p, ra, obs));
+        EQFCHK(riccati_close(c, p.normal, dt, Pdiag8));
+    }
     if (c->opt_check) {
         EQFCHK(launch_check_finite(c));
-        rc = read_flags(c);
-        if (rc)
-            return rc;
+        EQFCHK(read_flags(c));
         if (c->h_flags[1])
             return EQF_E_NONFINITE;
     }
     return 0;
 }
+int eqf_integrate_riccati_fast(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
+    EQFCHK(riccati_entry(c, imu13, dt, Qdiag12, Pdiag8, RiccatiEntry{false, false, true}));
+    PropPlan plan;
+    EQFCHK(plan_propagation(c, PropCall{false, 0}, plan)); // (behind enter(): no removal record or held landmark is this call's to handle)
+    plan_stage(c, plan);
+    return propagate_sigma_fast(c, plan, dt, Qdiag12, Pdiag8, nullptr);
+}
 
 int eqf_integrate_riccati_accurate(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
-    if (c && c->n_held > 0)
-        return EQF_E_UNSUPPORTED; // landmarks held for eqf_propagate_fast (eqf_add_landmarks_held): only that call knows to leave them alone
-    if (!c || !imu13 || !Qdiag12 || !Pdiag8 || !(dt > 0.0))
-        return EQF_E_BAD_ARG;
-    if (c->sig32)
-        return EQF_E_UNSUPPORTED; // the float store exists for the structured fast path only
-    EQFCHK(enter(c));
-    if (!c->d_Ebuf) {
+    EQFCHK(riccati_entry(c, imu13, dt, Qdiag12, Pdiag8, RiccatiEntry{true, true, true}));
+    if (!c->d_Ebuf) { // the exponential's buffers, on first use (this mode alone has buffers of its own)
         EQFCHK(alloc_device(c, c->d_Ebuf, (size_t)(EXPM_SMAX + 2) * 21 * 33));
         EQFCHK(alloc_device(c, c->d_Yl, 99 * (size_t)c->Ncap));
         EQFCHK(alloc_device(c, c->d_Fl, 9 * (size_t)c->Ncap));
         EQFCHK(alloc_device(c, c->d_PhiB, (size_t)c->ld * 12));
         EQFCHK(alloc_device(c, c->d_expinfo, 4));
     }
-    EQFCHK(ensure_dense(c));
-    int rc = upload_common(c, imu13);
-    if (rc)
-        return rc;
-    rc = launch_assemble(c);
-    if (rc)
-        return rc;
-    const bool normal = c->chart == EQVIO_COORD_NORMAL;
-    static const double kZero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (normal) { // expm(dt [[A_n, B_n],[0,0]]) = blkdiag(M, I) expm(dt [[A_e, B_e],[0,0]]) blkdiag(M^-1, I): the same two congruences
-        rc = normal_congruence(c, -1, dt, nullptr);
-        if (rc)
-            return rc;
-    }
-    RiccatiArgs ra;
-    ra.dt = dt;
-    std::memcpy(ra.Qd, Qdiag12, sizeof(ra.Qd));
-    std::memcpy(ra.Pd, normal ? kZero8 : Pdiag8, sizeof(ra.Pd));
     const int N = c->N, n = c->n();
-    double* Sin = c->d_sigma[c->cur];
-    double* Sout = c->d_sigma[1 - c->cur];
-    KTimer t(c, KN_DENSE_GEMM);
-    hipLaunchKernelGGL(k_expm_sensor, dim3(1), dim3(256), 0, c->stream, N, c->Ncap, dt, c->d_common, c->d_Al, c->d_Bl, c->d_Ebuf, c->d_expinfo);
-    HIPCHK(hipGetLastError());
-    if (N > 0) {
-        hipLaunchKernelGGL(k_expm_landmarks, dim3(blocks(N, 4)), dim3(256), 0, c->stream, N, c->Ncap, dt, c->d_Al, c->d_Bl, c->d_Ebuf, c->d_expinfo, c->d_Yl, c->d_Fl);
-        HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_build_phi, dim3(blocks(n, 256), n + 12), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, c->d_Ebuf, c->d_expinfo, c->d_Yl, c->d_Fl, c->d_F, c->d_PhiB);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_F, c->ld, Sin, c->ld, c->d_tmp, c->ld);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_tmp, c->ld, c->d_F, c->ld, Sout, c->ld);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_add_noise_dense, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, n, c->ld, c->ld, ra, c->d_PhiB, Sout);
-    HIPCHK(hipGetLastError());
-    c->cur = 1 - c->cur;
-    if (normal) {
-        rc = normal_congruence(c, +1, dt, Pdiag8);
-        if (rc)
-            return rc;
-    }
-    return round_sigma(c);
+    return dense_sandwich(
+        c, dt, Qdiag12, Pdiag8, DenseTiming{true, true},
+        [&](bool) { // expm(dt [[A_n, B_n],[0,0]]) = blkdiag(M, I) expm(dt [[A_e, B_e],[0,0]]) blkdiag(M^-1, I): the normal chart's two congruences serve this mode as well
+            hipLaunchKernelGGL(k_expm_sensor, dim3(1), dim3(256), 0, c->stream, N, c->Ncap, dt, c->d_common, c->d_Al, c->d_Bl, c->d_Ebuf, c->d_expinfo);
+            HIPCHK(hipGetLastError());
+            if (N > 0) {
+                hipLaunchKernelGGL(k_expm_landmarks, dim3(blocks(N, 4)), dim3(256), 0, c->stream, N, c->Ncap, dt, c->d_Al, c->d_Bl, c->d_Ebuf, c->d_expinfo, c->d_Yl, c->d_Fl);
+                HIPCHK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_build_phi, dim3(blocks(n, 256), n + 12), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, c->d_Ebuf, c->d_expinfo, c->d_Yl, c->d_Fl, c->d_F, c->d_PhiB);
+            return (int)hipGetLastError();
+        },
+        [&](const RiccatiArgs& ra, double* Sout) { hipLaunchKernelGGL(k_add_noise_dense, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, n, c->ld, c->ld, ra, c->d_PhiB, Sout); });
 }
 
 // ---- integrateRiccatiStateDiscrete (VIO_eqf.cpp:93-103, EqFMatrices.cpp:24-41) -----------------------------------------------------------
@@ -2239,97 +2308,63 @@ static GroupSensor group_inv(const GroupSensor& X) { // VIOGroup::inverse, senso
     return r;
 }
 int eqf_integrate_riccati_discrete(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
-    if (c && c->n_held > 0)
-        return EQF_E_UNSUPPORTED; // landmarks held for eqf_propagate_fast (eqf_add_landmarks_held): only that call knows to leave them alone
-    if (!c || !imu13 || !Qdiag12 || !Pdiag8 || !(dt > 0.0))
-        return EQF_E_BAD_ARG;
-    if (c->sig32)
-        return EQF_E_UNSUPPORTED; // float store: structured fast path only
-    EQFCHK(enter(c));
-    const size_t bytes = sizeof(double) * (size_t)c->ld * c->ncap;
-    EQFCHK(ensure_dense(c));
-    int rc = upload_common(c, imu13); // B_t at the current X (inputMatrixB), for dt (B Q B^T + P)
-    if (rc)
-        return rc;
-    rc = launch_assemble(c, false); // "the last reader of Q" is k_discrete_A below, not k_assemble_AB: the event is recorded there
-    if (rc)
-        return rc;
+    // (B_t at the current X (inputMatrixB), for dt (B Q B^T + P). "The last reader of Q" is k_discrete_A below, not k_assemble_AB: the event is recorded there)
+    EQFCHK(riccati_entry(c, imu13, dt, Qdiag12, Pdiag8, RiccatiEntry{true, true, false}));
     // Normal chart: A_d,n = M A_d,e M^-1 and B_n = M B_e at the origin (chain rule through the change of coordinates), so the Euclidean
-    // discrete propagation sits between the same two congruences as the continuous ones (riccati_after_assemble); the reference differentiates
+    // discrete propagation sits between the same two congruences as the continuous ones (riccati_open / riccati_close); the reference differentiates
     // a0Discrete numerically in normal coordinates, which agrees to the differencing's own 1e-9
-    const bool normal = c->chart == EQVIO_COORD_NORMAL;
-    static const double kZero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (normal) {
-        rc = normal_congruence(c, -1, dt, nullptr);
-        if (rc)
-            return rc;
-    }
-    // sensor-level part of a0Discrete: nominal + 21 x (+h, -h)
-    const double h = std::cbrt(2.220446049250313e-16);
-    const SensorState xhat = sensor_action(c->X, c->xi0);
-    const GroupSensor Lh = lift_discrete_sensor(xhat, imu13, dt), Lh_inv = group_inv(Lh), Xinv = group_inv(c->X);
-    DiscreteAArgs da;
-    da.h = h;
-    da.cpc[0] = pose_mul(pose_mul(pose_inv(xhat.cam), pose_inv(Lh.A)), xhat.cam);
-    double Ass[21 * 21]; // column-major
-    double col[2][21];
-    for (int j = 0; j < 21; ++j) {
-        for (int sgn = 0; sgn < 2; ++sgn) {
-            double e[21] = {0};
-            e[j] = sgn == 0 ? h : -h;
-            // xi_e = sensorChart_std.inv(e, xi0) (VIOState.cpp:114-121)
-            SensorState se;
-            se.bgyr = c->xi0.bgyr + v3(e[0], e[1], e[2]);
-            se.bacc = c->xi0.bacc + v3(e[3], e[4], e[5]);
-            se.pose = pose_mul(c->xi0.pose, se3_exp(v3(e[6], e[7], e[8]), v3(e[9], e[10], e[11])));
-            se.vel = c->xi0.vel + v3(e[12], e[13], e[14]);
-            se.cam = pose_mul(c->xi0.cam, se3_exp(v3(e[15], e[16], e[17]), v3(e[18], e[19], e[20])));
-            const SensorState xs = sensor_action(c->X, se);
-            const GroupSensor L = lift_discrete_sensor(xs, imu13, dt);
-            da.cpc[1 + 2 * j + sgn] = pose_mul(pose_mul(pose_inv(xs.cam), pose_inv(L.A)), xs.cam);
-            const GroupSensor G = group_mul(group_mul(c->X, group_mul(L, Lh_inv)), Xinv);
-            const SensorState s1 = sensor_action(G, se);
-            V3 om, tr, omc, trc;
-            se3_log(pose_mul(pose_inv(c->xi0.pose), s1.pose), om, tr);
-            se3_log(pose_mul(pose_inv(c->xi0.cam), s1.cam), omc, trc);
-            const V3 parts[7] = {s1.bgyr - c->xi0.bgyr, s1.bacc - c->xi0.bacc, om, tr, s1.vel - c->xi0.vel, omc, trc};
-            for (int b = 0; b < 7; ++b)
-                pack_v3(parts[b], col[sgn] + 3 * b);
-        }
-        for (int r = 0; r < 21; ++r)
-            Ass[r + 21 * j] = (col[0][r] - col[1][r]) / (2.0 * h);
-    }
     const int N = c->N, n = c->n();
-    EQFCHK(sync_ctx(c)); // h_buf staging
-    std::memcpy(c->h_buf, Ass, sizeof(Ass));
-    HIPCHK(hipMemsetAsync(c->d_F, 0, bytes, c->stream));
-    HIPCHK(hipMemcpy2DAsync(c->d_F, sizeof(double) * c->ld, c->h_buf, sizeof(double) * 21, sizeof(double) * 21, 21, hipMemcpyHostToDevice, c->stream));
-    if (N > 0) {
-        hipLaunchKernelGGL(k_discrete_A, dim3(blocks(N, 64)), dim3(64), 0, c->stream, N, c->Ncap, c->ld, normal ? (int)EQVIO_COORD_EUCLIDEAN : c->chart, da, c->q0(), c->Qq(), c->Qa(), c->d_F);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(c->ev_early, c->stream)); // an observer call that follows may overwrite Q from here on (observer_launch)
-    c->ev_assembled_early = true;
-    RiccatiArgs ra;
-    ra.dt = dt;
-    std::memcpy(ra.Qd, Qdiag12, sizeof(ra.Qd));
-    std::memcpy(ra.Pd, normal ? kZero8 : Pdiag8, sizeof(ra.Pd));
-    double* Sin = c->d_sigma[c->cur];
-    double* Sout = c->d_sigma[1 - c->cur];
-    KTimer t(c, KN_DENSE_GEMM);
-    hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_F, c->ld, Sin, c->ld, c->d_tmp, c->ld);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_gemm_nt, dim3(blocks(n, 32), blocks(n, 32)), dim3(256), 0, c->stream, n, n, n, c->d_tmp, c->ld, c->d_F, c->ld, Sout, c->ld);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_add_noise, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, ra, c->d_common, c->d_Bl, Sout);
-    HIPCHK(hipGetLastError());
-    c->cur = 1 - c->cur;
-    if (normal) {
-        rc = normal_congruence(c, +1, dt, Pdiag8);
-        if (rc)
-            return rc;
-    }
-    return round_sigma(c);
+    auto discrete_A = [&](bool normal) {
+        // sensor-level part of a0Discrete: nominal + 21 x (+h, -h)
+        const double h = std::cbrt(2.220446049250313e-16);
+        const SensorState xhat = sensor_action(c->X, c->xi0);
+        const GroupSensor Lh = lift_discrete_sensor(xhat, imu13, dt), Lh_inv = group_inv(Lh), Xinv = group_inv(c->X);
+        DiscreteAArgs da;
+        da.h = h;
+        da.cpc[0] = pose_mul(pose_mul(pose_inv(xhat.cam), pose_inv(Lh.A)), xhat.cam);
+        double Ass[21 * 21]; // column-major
+        double col[2][21];
+        for (int j = 0; j < 21; ++j) {
+            for (int sgn = 0; sgn < 2; ++sgn) {
+                double e[21] = {0};
+                e[j] = sgn == 0 ? h : -h;
+                // xi_e = sensorChart_std.inv(e, xi0) (VIOState.cpp:114-121)
+                SensorState se;
+                se.bgyr = c->xi0.bgyr + v3(e[0], e[1], e[2]);
+                se.bacc = c->xi0.bacc + v3(e[3], e[4], e[5]);
+                se.pose = pose_mul(c->xi0.pose, se3_exp(v3(e[6], e[7], e[8]), v3(e[9], e[10], e[11])));
+                se.vel = c->xi0.vel + v3(e[12], e[13], e[14]);
+                se.cam = pose_mul(c->xi0.cam, se3_exp(v3(e[15], e[16], e[17]), v3(e[18], e[19], e[20])));
+                const SensorState xs = sensor_action(c->X, se);
+                const GroupSensor L = lift_discrete_sensor(xs, imu13, dt);
+                da.cpc[1 + 2 * j + sgn] = pose_mul(pose_mul(pose_inv(xs.cam), pose_inv(L.A)), xs.cam);
+                const GroupSensor G = group_mul(group_mul(c->X, group_mul(L, Lh_inv)), Xinv);
+                const SensorState s1 = sensor_action(G, se);
+                V3 om, tr, omc, trc;
+                se3_log(pose_mul(pose_inv(c->xi0.pose), s1.pose), om, tr);
+                se3_log(pose_mul(pose_inv(c->xi0.cam), s1.cam), omc, trc);
+                const V3 parts[7] = {s1.bgyr - c->xi0.bgyr, s1.bacc - c->xi0.bacc, om, tr, s1.vel - c->xi0.vel, omc, trc};
+                for (int b = 0; b < 7; ++b)
+                    pack_v3(parts[b], col[sgn] + 3 * b);
+            }
+            for (int r = 0; r < 21; ++r)
+                Ass[r + 21 * j] = (col[0][r] - col[1][r]) / (2.0 * h);
+        }
+        EQFCHK(sync_ctx(c)); // h_buf staging
+        std::memcpy(c->h_buf, Ass, sizeof(Ass));
+        HIPCHK(hipMemsetAsync(c->d_F, 0, sizeof(double) * (size_t)c->ld * c->ncap, c->stream));
+        HIPCHK(hipMemcpy2DAsync(c->d_F, sizeof(double) * c->ld, c->h_buf, sizeof(double) * 21, sizeof(double) * 21, 21, hipMemcpyHostToDevice, c->stream));
+        if (N > 0) {
+            hipLaunchKernelGGL(k_discrete_A, dim3(blocks(N, 64)), dim3(64), 0, c->stream, N, c->Ncap, c->ld, normal ? (int)EQVIO_COORD_EUCLIDEAN : c->chart, da, c->q0(), c->Qq(), c->Qa(), c->d_F);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(c->ev_early, c->stream)); // an observer call that follows may overwrite Q from here on (observer_launch)
+        c->ev_assembled_early = true;
+        return 0;
+    };
+    return dense_sandwich(c, dt, Qdiag12, Pdiag8, DenseTiming{false, true}, discrete_A, [&](const RiccatiArgs& ra, double* Sout) {
+        hipLaunchKernelGGL(k_add_noise, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, ra, c->d_common, c->d_Bl, Sout);
+    });
 }
 
 // Host half of integrateObserverState for `chunk` consecutive IMU samples: the sensor-level group element Lambda of every
@@ -2347,14 +2382,7 @@ static void observer_host_step(GroupSensor& X, const SensorState& xi0, const dou
         st.discrete = discreteLift ? 1 : 0;
         st.dt = dt;
         if (discreteLift) {
-            L.bgyr = dt * gbv;
-            L.bacc = dt * abv;
-            L.A.R = so3_exp(dt * gyr);
-            V3 x = dt * q_rot(xh.pose.R, xh.vel) + (0.5 * dt * dt) * (q_rot(xh.pose.R, acc) + v3(0, 0, -kGravity));
-            L.A.x = q_rot(q_inv(xh.pose.R), x);
-            L.B = pose_mul(pose_mul(pose_inv(xh.cam), L.A), xh.cam);
-            const V3 bodyVelDiff = acc - kGravity * gdir;
-            L.w = xh.vel - (xh.vel + dt * bodyVelDiff);
+            L = lift_discrete_sensor(xh, imu, dt);
             st.Tinv = pose_mul(pose_mul(pose_inv(xh.cam), pose_inv(L.A)), xh.cam);
             st.omC = v3(0, 0, 0);
             st.vC = v3(0, 0, 0);
@@ -2401,8 +2429,8 @@ static int observer_launch(eqf_ctx* c, const ObsSteps& steps_arg, int chunk) {
     return 0;
 }
 int eqf_integrate_observer(eqf_ctx* c, const double* imu13_k, const double* dt_k, int k, int discreteLift) {
-    if (c && c->n_held > 0)
-        return EQF_E_UNSUPPORTED; // landmarks held for eqf_propagate_fast (eqf_add_landmarks_held): only that call knows to leave them alone
+    if (holds_landmarks(c))
+        return EQF_E_UNSUPPORTED;
     if (!c || k < 0 || (k > 0 && (!imu13_k || !dt_k)))
         return EQF_E_BAD_ARG;
     if (k == 0)
@@ -2431,38 +2459,9 @@ int eqf_propagate_fast(eqf_ctx* c, const double* imu13_mean, double dt_total, co
     HP_SCOPE("abi.propagate_fast");
     if (!c || !imu13_mean || !Qdiag12 || !Pdiag8 || k < 0 || (k > 0 && (!imu13_k || !dt_k)))
         return EQF_E_BAD_ARG;
-    // EQF_OPT_GATHER_IN_PROPAGATE: a pending record of removals only (the frame's lost landmarks, the last frame's discarded outliers) is applied by the propagation kernel
-    // itself instead of a compaction pass in front of it - when this call takes the fused kernel with observer blocks and nothing was appended.
-    // eqf_add_landmarks_held: the held landmarks (the last n_held of the state) are created by the same kernel (GatherArgs::held) unless an ordinary pass has appended them.
-    GatherArgs gather{};
-    bool use_gather = false;
-    const bool fused_kernel = c->opt_fuse_asm && !c->opt_dense && !c->sig32 && c->chart != EQVIO_COORD_NORMAL && k > 0 && c->N > 0; // (more steps than one chunk holds: the further chunks are k_observer launches on the new buffers, for the propagated landmarks only)
-    if (c->n_held > 0 && !fused_kernel)
-        return EQF_E_UNSUPPORTED; // (eqf_add_landmarks_held checked the options: one was changed in between, or there are no observer steps to ride along)
-    const int Nprop = c->N - c->n_held;
-    const bool hold_here = c->n_held > 0 && !c->held_in_memory;
-    if (fused_kernel && c->opt_gather && (c->reshape_pending || hold_here) && c->pend_var.empty() && c->dev_N <= GATHER_MAXN &&
-        (!c->reshape_pending || ((int)c->pend_map.size() == Nprop && c->dev_N >= Nprop))) {
-        bool ok = true;
-        if (c->reshape_pending) {
-            int prev = -1;
-            for (int i = 0; i < Nprop && ok; ++i) {
-                const int o = c->pend_map[i];
-                ok = o > prev && o < c->dev_N; // survivors keep their order
-                if (ok)
-                    gather.surv[o >> 6] |= 1ull << (o & 63);
-                prev = o;
-            }
-            gather.n = c->dev_N - Nprop;
-        } else
-            ok = c->dev_N == Nprop;
-        if (ok && (gather.n > 0 || hold_here)) {
-            use_gather = true;
-            if (hold_here)
-                gather.held = c->h_held;
-        }
-    }
-    if (use_gather) { // enter() without the flush
+    PropPlan plan;
+    EQFCHK(plan_propagation(c, PropCall{true, k}, plan)); // from the context as it is in front of enter(): see PropPlan
+    if (plan.use_gather) { // enter() without the flush: the launch applies the record
         HIPCHK(hipSetDevice(c->device));
         c->ocov_valid = false;
     } else {
@@ -2481,10 +2480,7 @@ int eqf_propagate_fast(eqf_ctx* c, const double* imu13_mean, double dt_total, co
     // 2. the assembly kernel goes out first (its terms, c->ck, are fixed now): the host part of the observer steps below then
     //    overlaps it instead of delaying it
     // (with fused assembly there is no such launch: the propagation kernel assembles what it needs itself)
-    const bool fuse = c->opt_fuse_asm && !c->opt_dense;
-    rc = fuse ? join_observer(c) : launch_assemble(c, false);
-    if (rc)
-        return rc;
+    EQFCHK(plan.fused ? join_observer(c) : launch_assemble(c, false));
     host_stamp(c, TH_ASSEMBLE_OUT);
     {
         HP_SCOPE("pf.stage_prepare");
@@ -2509,24 +2505,17 @@ int eqf_propagate_fast(eqf_ctx* c, const double* imu13_mean, double dt_total, co
     }
     // 4. Arrow form: the first chunk of observer steps rides along as extra blocks of the Sigma propagation kernel (it does
     //    not touch Q; the assembly before it has read Q, the statistics after it want the new Q): two launches on ONE stream.
-    //    Further chunks (k > 24) and the dense mode use the observer kernel, in stream order.
-    const bool ride = !c->opt_dense && !chunks.empty() && c->N > 0;
-    c->obs_one_chunk = chunks.size() == 1; // (the group elements are final when the propagation kernel's observer blocks are done)
+    //    Further chunks (k > kMaxSteps) and the dense mode use the observer kernel, in stream order.
     {
         HP_SCOPE("pf.launch");
-        if (use_gather && !(ride && fuse)) { // (cannot happen: the conditions above are the ones of `ride` and `fuse`) - apply the record the ordinary way
-            materialise_held(c);
-            rc = flush_reshape(c);
-            if (rc)
-                return rc;
-            use_gather = false;
-        }
-        rc = riccati_after_assemble(c, dt_total, Qdiag12, Pdiag8, ride ? &chunks[0] : nullptr, ride ? counts[0] : 0, fuse, use_gather ? &gather : nullptr);
+        plan_stage(c, plan);
+        rc = propagate_sigma_fast(c, plan, dt_total, Qdiag12, Pdiag8, plan.ride ? &chunks[0] : nullptr);
     }
     if (rc)
         return rc;
     host_stamp(c, TH_PROP_OUT);
-    for (size_t q = ride ? 1 : 0; q < chunks.size() && Nprop > 0; ++q) { // (held landmarks are the last ones: the observer kernel does not reach them)
+    const int Nprop = plan.gather.nprop; // (held landmarks are the last ones: the observer kernel does not reach them)
+    for (size_t q = plan.ride ? 1 : 0; q < chunks.size() && Nprop > 0; ++q) {
         c->ev_assembled_early = false;
         hipLaunchKernelGGL(k_observer, dim3(blocks(Nprop, 64)), dim3(64), 0, c->stream, chunks[q], Nprop, c->Ncap, counts[q], c->q0(), c->Qq(), c->Qa());
         HIPCHK(hipGetLastError());
@@ -2910,7 +2899,7 @@ static int lookahead_selftest_pass(eqf_ctx* c, bool& placement_refused) {
                 return fail(0);
             }
             if (rep < 0) {
-                if (fl[0]) { // (cannot happen: the problem is positive definite)
+                if (fl[0]) { // (not expected: the problem is positive definite)
                     c->la_selftest = -1;
                     return fail(0);
                 }
@@ -3205,7 +3194,7 @@ static int settle_update(eqf_ctx* c) {
     c->unsettled_wait = false;
     if (rc)
         return rc;
-    if (c->h_resflags[0] || c->h_resflags[2] || c->h_resflags[3]) { // (cannot happen: the early doorbell rings only when none of these can be raised any more)
+    if (c->h_resflags[0] || c->h_resflags[2] || c->h_resflags[3]) { // (not expected: the early doorbell rings only when none of these can be raised any more)
         std::fprintf(stderr, "[eqf_hip] an update announced by the early doorbell was not applied (flags %d %d %d)\n", c->h_resflags[0], c->h_resflags[2], c->h_resflags[3]);
         return EQF_E_STALLED;
     }

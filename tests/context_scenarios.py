@@ -34,7 +34,7 @@ THRESHOLDS = {
     "NJ 8|9": "ZB = 2 (the look-ahead kernel evaluates the output blocks itself) in the speculative tail up to 8 panels (plan_tail)",
     "NJ 16|17": "la_row2 / la_build_rows2, HOME placement, live_cols and live_first up to 16 panels (launch_lookahead, plan_tail, stats_select_route)",
     "NJ 32|33": "look-ahead kernel up to 32 panels (la_njcap), one launch per panel above",
-    "N 256|257": "propagation: nT = ceil(N / 16) > 16 takes the mirrored lower triangle with several tiles per workgroup (riccati_fast_impl)",
+    "N 256|257": "propagation: nT = ceil(N / 16) > 16 takes the mirrored lower triangle with several tiles per workgroup (plan_propagation)",
     "N 249|250": "k_syrk_lift walks the lower triangle row by row up to SYRK_ARITH_TILES = 24 tile rows of 32 (21 + 3 N <= 768)",
     "N 512|513": "SEL_ONE_WG = 512: k_stats_select up to it, k_outlier_stats -> k_select_outliers above",
     "N 16k": "16-landmark tiles of the propagation kernel (PT): 255, 257, 271, 273, 511, 513",

@@ -74,7 +74,7 @@ PLAIN32 = dict(me=0, queued=0, upd=[0, 0])
 PLAIN33 = dict(me=0, queued=0, early=0, upd=[0, 0])
 CHANGES = {
     "lookahead=0": {"update33": dict(la=0, zb=0), "staged33": dict(la=0, zb=0, early=0), "select40": dict(la=0, zb=0, live=0, early=0)},
-    # (the propagation kernel evaluates output blocks for the update only where the look-ahead kernel may build Z from them: riccati_after_assemble asks for
+    # (the propagation kernel evaluates output blocks for the update only where the look-ahead kernel may build Z from them: plan_stage (behind plan_propagation) asks for
     #  EQF_OPT_Z_IN_LOOKAHEAD, fp64 Sigma and no finite check as well - no me without them, whatever factorises)
     "z_in_lookahead=0": {"update33": dict(zb=0), "staged32": dict(me=0), "staged33": dict(zb=0, me=0), "select40": dict(zb=0)},
     "early_lift=0": {"staged32": dict(me=0), "staged33": dict(zb=0, me=0, early=0), "select40": dict(early=0)},
