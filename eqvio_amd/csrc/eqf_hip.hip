@@ -1156,8 +1156,12 @@ static int round_sigma(eqf_ctx* c, const int* spec, int spec_seq) {
     HIPCHK(hipGetLastError());
     return 0;
 }
-static int launch_check_finite(eqf_ctx* c) { // EQF_OPT_CHECK_FINITE: behind a propagation, behind an update tail
+// EQF_OPT_CHECK_FINITE: behind a propagation, behind an update tail. k_check_finite only ever raises its word, and not every launch sequence in front of it holds one
+// of the kernels that clear the status words (the dense sandwich and the unfused arrow form hold none): every scan starts from a cleared word, so a verdict is this
+// call's and never an earlier one's. Contexts with the option off never come here.
+static int launch_check_finite(eqf_ctx* c) {
     const int n = c->n();
+    HIPCHK(hipMemsetAsync(c->d_flags + 1, 0, sizeof(int), c->stream));
     LAUNCH_TS(c, k_check_finite, dim3(blocks(n, 256), n), dim3(256), c->stream, n, c->ld, (const TS*)c->sigma(), c->d_flags);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2223,8 +2227,17 @@ static int launch_propagation(eqf_ctx* c, const PropPlan& p, RiccatiArgs ra, con
     c->cur = 1 - c->cur;
     return 0;
 }
+// assert(!Sigma.hasNaN()) behind integrateRiccatiStateFast / Accurate / Discrete (VIO_eqf.cpp:71, 90, 102): what every propagation mode returns through, with its
+// own status in front. EQF_OPT_CHECK_FINITE off: nothing is launched.
+static int check_propagated(eqf_ctx* c, int rc) {
+    if (rc || !c->opt_check)
+        return rc;
+    EQFCHK(launch_check_finite(c));
+    EQFCHK(read_flags(c));
+    return c->h_flags[1] ? EQF_E_NONFINITE : 0;
+}
 // The fast mode behind its sensor terms and assembly, for both its entry points: the arrow form from the plan or the dense sandwich. Around it, what the fast mode
-// alone does (the accurate and the discrete mode do neither): output blocks of an earlier propagation are dropped, EQF_OPT_CHECK_FINITE is honoured behind it.
+// alone does (the accurate and the discrete mode do not): output blocks of an earlier propagation are dropped.
 static int propagate_sigma_fast(eqf_ctx* c, const PropPlan& p, double dt, const double* Qdiag12, const double* Pdiag8, const ObsSteps* obs) {
     c->me_valid = false;
     if (p.dense) {
@@ -2242,13 +2255,7 @@ static int propagate_sigma_fast(eqf_ctx* c, const PropPlan& p, double dt, const 
         EQFCHK(launch_propagation(c, p, ra, obs));
         EQFCHK(riccati_close(c, p.normal, dt, Pdiag8));
     }
-    if (c->opt_check) {
-        EQFCHK(launch_check_finite(c));
-        EQFCHK(read_flags(c));
-        if (c->h_flags[1])
-            return EQF_E_NONFINITE;
-    }
-    return 0;
+    return check_propagated(c, 0);
 }
 int eqf_integrate_riccati_fast(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
     EQFCHK(riccati_entry(c, imu13, dt, Qdiag12, Pdiag8, RiccatiEntry{false, false, true}));
@@ -2268,7 +2275,7 @@ int eqf_integrate_riccati_accurate(eqf_ctx* c, const double* imu13, double dt, c
         EQFCHK(alloc_device(c, c->d_expinfo, 4));
     }
     const int N = c->N, n = c->n();
-    return dense_sandwich(
+    return check_propagated(c, dense_sandwich(
         c, dt, Qdiag12, Pdiag8, DenseTiming{true, true},
         [&](bool) { // expm(dt [[A_n, B_n],[0,0]]) = blkdiag(M, I) expm(dt [[A_e, B_e],[0,0]]) blkdiag(M^-1, I): the normal chart's two congruences serve this mode as well
             hipLaunchKernelGGL(k_expm_sensor, dim3(1), dim3(256), 0, c->stream, N, c->Ncap, dt, c->d_common, c->d_Al, c->d_Bl, c->d_Ebuf, c->d_expinfo);
@@ -2280,7 +2287,7 @@ int eqf_integrate_riccati_accurate(eqf_ctx* c, const double* imu13, double dt, c
             hipLaunchKernelGGL(k_build_phi, dim3(blocks(n, 256), n + 12), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, c->d_Ebuf, c->d_expinfo, c->d_Yl, c->d_Fl, c->d_F, c->d_PhiB);
             return (int)hipGetLastError();
         },
-        [&](const RiccatiArgs& ra, double* Sout) { hipLaunchKernelGGL(k_add_noise_dense, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, n, c->ld, c->ld, ra, c->d_PhiB, Sout); });
+        [&](const RiccatiArgs& ra, double* Sout) { hipLaunchKernelGGL(k_add_noise_dense, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, n, c->ld, c->ld, ra, c->d_PhiB, Sout); }));
 }
 
 // ---- integrateRiccatiStateDiscrete (VIO_eqf.cpp:93-103, EqFMatrices.cpp:24-41) -----------------------------------------------------------
@@ -2362,9 +2369,9 @@ int eqf_integrate_riccati_discrete(eqf_ctx* c, const double* imu13, double dt, c
         c->ev_assembled_early = true;
         return 0;
     };
-    return dense_sandwich(c, dt, Qdiag12, Pdiag8, DenseTiming{false, true}, discrete_A, [&](const RiccatiArgs& ra, double* Sout) {
+    return check_propagated(c, dense_sandwich(c, dt, Qdiag12, Pdiag8, DenseTiming{false, true}, discrete_A, [&](const RiccatiArgs& ra, double* Sout) {
         hipLaunchKernelGGL(k_add_noise, dim3(blocks(n, 256), n), dim3(256), 0, c->stream, N, c->Ncap, n, c->ld, ra, c->d_common, c->d_Bl, Sout);
-    });
+    }));
 }
 
 // Host half of integrateObserverState for `chunk` consecutive IMU samples: the sensor-level group element Lambda of every

@@ -24,7 +24,11 @@ typedef struct eqf_ctx eqf_ctx;
 
 enum {
     EQF_OK = 0,
-    EQF_E_NONFINITE = -1,  /* NaN/Inf detected in Sigma or X (the reference's assert(!hasNaN())) */
+    EQF_E_NONFINITE = -1,  /* EQF_OPT_CHECK_FINITE found NaN/Inf in Sigma, or an update's Gamma has a non-finite sensor entry (the reference's
+                              assert(!Sigma.hasNaN()) / assert(!X.hasNaN())). The step was NOT undone: Sigma and X are as the failed step left them
+                              (a propagation has written the propagated Sigma, eqf_propagate_fast has applied its observer steps, an update has
+                              subtracted W W^T and applied the lift). The context is good again after eqf_set_state + eqf_set_sigma, and equal to one
+                              that never saw the bad values */
     EQF_E_NOT_SPD = -2,    /* Cholesky pivot <= 0 in S = C Sigma C^T + R */
     EQF_E_BAD_ARG = -3,
     EQF_E_CAPACITY = -4,   /* an output array of the caller is too small; or the device buffers could not be grown (allocation failed) */
@@ -40,7 +44,13 @@ enum {
 enum {
     EQF_OPT_RICCATI_DENSE = 1, /* 1: propagate with two dense fp64 MFMA GEMMs (F Sigma F^T, F materialised);
                                   0 (default): structure-exploiting arrow-form kernel */
-    EQF_OPT_CHECK_FINITE = 2,  /* 1: scan Sigma/X for non-finite values after propagate/update */
+    EQF_OPT_CHECK_FINITE = 2,  /* 1: every propagation (eqf_integrate_riccati_fast / _accurate / _discrete, eqf_propagate_fast, in any of their modes) and every
+                                  update (eqf_vision_update, eqf_stats_then_update, eqf_stats_select_update) scans the n x n Sigma it leaves behind - the
+                                  live rows and columns, not the capacity beyond them - and returns EQF_E_NONFINITE from THAT call if an entry is NaN or
+                                  +-Inf. Every scan starts from a cleared verdict: an earlier call's is never reported again. X is not scanned; an update
+                                  looks at the 21 sensor entries of Gamma instead, with the option on or off. What the context holds afterwards: see
+                                  EQF_E_NONFINITE. One more launch and a host wait per call; the doorbell waits and the speculative tail are not used.
+                                  0 (default): no scan, no launch */
     EQF_OPT_SPECULATIVE = 7,   /* 1 (default): eqf_stats_then_update queues the update behind the statistics kernel, and backs off where that does not
                                   pay: after a tail the device had to cancel, the next 1, 2, 4 .. 16 calls only compute the statistics (*updated = 0),
                                   until a frame shows no outlier candidate; 2: always queue the tail; 0: never (statistics only) */
