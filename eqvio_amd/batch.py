@@ -1,6 +1,6 @@
 """ctypes binding of the filter batch: include/eqf_batch.h (device level, libeqf_hip.so) and include/eqvio_batch.h (filter level, libeqvio_filter.so).
 
-VIOFilterBatch holds B independent reference VIOFilters (fast or, per slot, accurate Riccati; at most 64 landmarks each) whose frames go to the GPU together:
+VIOFilterBatch holds B independent reference VIOFilters (fast or, per slot, accurate Riccati with the continuous or the discrete state matrix; at most 64 landmarks each) whose frames go to the GPU together:
 one device call per step and mode, one workgroup per slot. BatchCore is the device level on its own. .slot(k) is a view with the method names of capi.VIOFilter, so the per-filter test helpers work on a slot unchanged.
 The prototypes are declared in lists of their own (_batch_declared), apart from the loaders' _declared lists of eqf_hip.h / eqvio_filter.h.
 """
@@ -14,6 +14,7 @@ from eqvio_amd.capi import Camera, Settings, c_double_p, c_int_p, load_eqf_lib, 
 EQF_BATCH_MAX_LANDMARKS = 64
 BATCH_REMOVED_OLD, BATCH_REMOVED_OUTLIERS, BATCH_ADDED, BATCH_EMPTY, BATCH_UPDATED, BATCH_REMOVED_INVALID = 1, 2, 4, 8, 16, 32
 RICCATI_FAST, RICCATI_ACCURATE = 0, 1  # EQVIO_BATCH_RICCATI_* (include/eqvio_batch.h)
+STATE_MATRIX_CONTINUOUS, STATE_MATRIX_DISCRETE = 0, 1  # EQVIO_BATCH_STATE_MATRIX_*
 
 
 class BatchFrame(C.Structure):
@@ -109,6 +110,7 @@ def load_batch_protos():
         "eqf_batch_sensor_estimate": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqf_batch_step": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
         "eqf_batch_step_accurate": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
+        "eqf_batch_step_discrete": (C.c_int, [vp, C.c_int, P(BatchFrame), c_int_p]),
         "eqf_batch_last_riccati": (C.c_int, [vp, C.c_int, c_int_p, c_int_p]),
         "eqf_batch_last_result": (C.c_int, [vp, C.c_int, c_int_p, c_double_p]),
         "eqf_batch_stream": (vp, [vp]),
@@ -136,6 +138,8 @@ def load_batch_protos():
         "eqvio_batch_get_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
         "eqvio_batch_set_slot_riccati": (C.c_int, [vp, C.c_int, C.c_int]),
         "eqvio_batch_get_slot_riccati": (C.c_int, [vp, C.c_int]),
+        "eqvio_batch_set_slot_state_matrix": (C.c_int, [vp, C.c_int, C.c_int]),
+        "eqvio_batch_get_slot_state_matrix": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_process_imu": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqvio_batch_process_vision": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, P(Camera), c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
@@ -165,7 +169,8 @@ def load_batch_protos():
     for lib, protos in ((elib, eprotos), (flib, fprotos)):
         for name, (res, args) in protos.items():
             if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_batch_load_ctx", "eqf_batch_store_ctx", "eqvio_batch_load_filter", "eqvio_batch_store_filter", "eqf_batch_step_accurate", "eqf_batch_last_riccati",
-                                                                   "eqvio_batch_set_slot_riccati", "eqvio_batch_get_slot_riccati") and not hasattr(lib, name):
+                                                                   "eqvio_batch_set_slot_riccati", "eqvio_batch_get_slot_riccati", "eqf_batch_step_discrete",
+                                                                   "eqvio_batch_set_slot_state_matrix", "eqvio_batch_get_slot_state_matrix") and not hasattr(lib, name):
                 continue  # same-box A/B against the libraries of an older commit (as capi.load_eqf_lib): entry points that commit did not have yet
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
@@ -279,8 +284,12 @@ class BatchCore:
         """eqf_batch_step_accurate: the frame with one accurate Riccati step per IMU sample. entries as step's; imu13_mean and dt_total may be left out."""
         return self._step(self.elib.eqf_batch_step_accurate, entries)
 
+    def step_discrete(self, entries):
+        """eqf_batch_step_discrete: the frame with one discrete-state-matrix Riccati step per IMU sample. entries as step_accurate's."""
+        return self._step(self.elib.eqf_batch_step_discrete, entries)
+
     def last_riccati(self, k):
-        """(samples with dt > 0, most squarings) of slot k's last accurate step (eqf_batch_last_riccati)."""
+        """(samples with dt > 0, most squarings) of slot k's last accurate or discrete step (eqf_batch_last_riccati)."""
         n, sq = C.c_int(), C.c_int()
         self._chk(self.elib.eqf_batch_last_riccati(self.h, k, C.byref(n), C.byref(sq)))
         return n.value, sq.value
@@ -347,9 +356,23 @@ class VIOFilterBatch:
             raise BatchError(f"slot_riccati({k}): " + self.elib.eqf_error_string(rc).decode(), rc)
         return rc
 
+    def set_slot_state_matrix(self, k, kind):
+        """The state matrix slot k's accurate Riccati steps use from its next frame on (eqvio_batch_set_slot_state_matrix): STATE_MATRIX_CONTINUOUS (every
+        slot starts with it) or STATE_MATRIX_DISCRETE, the reference's useDiscreteStateMatrix. It matters only while the slot's Riccati mode is
+        RICCATI_ACCURATE. k None: every slot. A bad kind or slot raises BatchError with EQF_E_BAD_ARG and changes nothing."""
+        rc = self.lib.eqvio_batch_set_slot_state_matrix(self.h, -1 if k is None else k, kind)
+        if rc != 0:
+            raise BatchError(f"set_slot_state_matrix({k}, {kind}): " + self.elib.eqf_error_string(rc).decode(), rc)
+
+    def slot_state_matrix(self, k):
+        rc = self.lib.eqvio_batch_get_slot_state_matrix(self.h, k)
+        if rc < 0:
+            raise BatchError(f"slot_state_matrix({k}): " + self.elib.eqf_error_string(rc).decode(), rc)
+        return rc
+
     def last_riccati(self, k):
-        """(samples, max_squarings) of slot k's last accurate step (eqf_batch_last_riccati): the samples that had dt > 0 and the most squarings one of its
-        exponentials took; 0, 0 after a fast step or a copy into the slot."""
+        """(samples, max_squarings) of slot k's last accurate or discrete step (eqf_batch_last_riccati): the samples that had dt > 0 and the most squarings
+        one of its exponentials took (0 in the discrete mode); 0, 0 after a fast step or a copy into the slot."""
         n, sq = C.c_int(), C.c_int()
         self._chk(self.elib.eqf_batch_last_riccati(self.core_handle(), k, C.byref(n), C.byref(sq)))
         return n.value, sq.value
@@ -594,6 +617,15 @@ class BatchSlot:
     @riccati.setter
     def riccati(self, mode):
         self.b.set_slot_riccati(self.k, mode)
+
+    @property
+    def state_matrix(self):
+        """STATE_MATRIX_CONTINUOUS or STATE_MATRIX_DISCRETE (VIOFilterBatch.set_slot_state_matrix)."""
+        return self.b.slot_state_matrix(self.k)
+
+    @state_matrix.setter
+    def state_matrix(self, kind):
+        self.b.set_slot_state_matrix(self.k, kind)
 
     def copy_to(self, dsts):
         """This slot into every slot of dsts (one slot or a list), one launch (VIOFilterBatch.copy_slots); returns the status codes."""

@@ -1,5 +1,5 @@
 // Filter batch (include/eqf_batch.h): B independent filters of at most 64 landmarks, one workgroup per slot, ONE launch per frame of all of them.
-// The device side: the packet structs and the ten kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
+// The device side: the packet structs and the eleven kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
 // eqf_hip.hip includes both. Every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
 //
 // Per slot s, in HBM (fp64): two Sigma buffers (n x n column-major, leading dimension ld, n <= 21 + 3 * 64), two landmark buffers (35 SoA planes of stride
@@ -12,7 +12,7 @@
 //
 // The phases of k_batch_frame (VIOFilter::processVisionData, fast Riccati, src/VIOFilter.cpp:194-241; its body is eqf_batch_frame_body.inc). With accurate
 // Riccati (eqf_batch_step_accurate) k_batch_riccati does what phases 0 and 1 do - one accurate Riccati step per IMU sample between the observer steps - and
-// k_batch_frame_tail, the same body from phase 2 on, the rest:
+// k_batch_frame_tail, the same body from phase 2 on, the rest; with the discrete state matrix (eqf_batch_step_discrete) k_batch_discrete stands in k_batch_riccati's place:
 //   0  rows of A and B of the surviving landmarks (assemble_landmark, sensor_Ass_entry / sensor_Bs_entry) into LDS; origin planes copied to the other
 //      buffer; the observer steps' landmark part (observer_chain) applied on the way. Landmarks the host found unmeasured (removeOldLandmarks) are not copied:
 //      the propagation is block triangular, so marginalising a landmark before or after it leaves every other entry the same.
@@ -76,7 +76,7 @@ struct BatchOut {
     double depth;                // depth the new landmarks got
     int dof;                     // rows m of the matched measurement (0: empty)
     double nis, logdet;          // yTilde^T S^-1 yTilde and log det S of the update (NaN when the update failed)
-    int ric_samples, ric_squarings; // k_batch_riccati's: samples with dt > 0, the most squarings an exponential took (eqf_batch_last_riccati)
+    int ric_samples, ric_squarings; // k_batch_riccati's / k_batch_discrete's: samples with dt > 0, the most squarings an exponential took (eqf_batch_last_riccati)
 };
 // The slots' buffers, the same for every kernel: slot s has two Sigma buffers and two landmark buffers (which = 0 / 1; the host names the current one) and one
 // scratch area.
@@ -515,6 +515,275 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_riccati(const RicArgs ra) 
     if (tid == 0) {
         ra.out[blockIdx.x].ric_samples = samples;
         ra.out[blockIdx.x].ric_squarings = max_sq;
+    }
+}
+
+// ===================================================================================================
+// eqf_batch_step_discrete (include/eqf_batch.h): integrateUpToTime with fastRiccati == false and useDiscreteStateMatrix == true (src/VIOFilter.cpp:165-170) - per
+// IMU sample one integrateRiccatiStateDiscrete (VIO_eqf.cpp:93-103) at the X the samples before it have produced, then that sample's observer step. The sibling of
+// k_batch_riccati: launched in its place in front of k_batch_frame_tail, it ends where that kernel ends and moves Sigma the same way (the first sample gathers
+// from the current buffer through the surviving rows, every later one reads the other buffer; without a sample of dt > 0 the gathered Sigma is copied).
+//
+// Per sample with dt > 0, Sigma <- A_d Sigma A_d^T + dt (B Q B^T + P). A_d = stateMatrixADiscrete (EqFMatrices.cpp:24-41) is the central difference, h = cbrt(eps),
+// of a0Discrete over the 21 sensor coordinates and the 3 coordinates of every landmark, and has the arrow shape of the accurate mode's Phi: a dense 21 x 21 sensor
+// block, per landmark a 3 x 21 strip and a 3 x 3 block. All of it is formed here:
+//   sensor part   lanes 0 .. 41 of wave 0 evaluate one perturbation each (coordinate lane / 2, +h for even lanes, -h for odd ones) by the chain of
+//                 eqf_integrate_riccati_discrete's discrete_A (eqf_hip.hip), with the helpers that function calls: sensorChart^-1, sensor_action,
+//                 lift_discrete_sensor, the group products, two se3_log. Each leaves its 21-vector and the camera-frame pose change cpc of its lift in LDS; lane 42
+//                 leaves the nominal cpc. The pairs are then differenced into the sensor block.
+//   landmark rows a lane per landmark, by k_discrete_A's device functions (a0_discrete_landmark, lift_q, chart_fwd / chart_bwd), from the 43 cpc and the landmark's
+//                 current Q, which wave 3 carries through the observer steps as in k_batch_riccati. The 24 central differences of a landmark (21 sensor coordinates,
+//                 its own 3) are split over the four waves, six each.
+//   noise         B's sensor rows from sensor_Bs_entry, the landmarks' 3 x 3 from assemble_landmark<0>, as phase 1 of the fast frame forms dt (B Q B^T + P).
+// The packet carries per sample dt and CommonK (for B) as RicStep does, the sample's 13 IMU doubles, and the sensor parts of xi0 and of the X the sample starts
+// from: 1.6 KB, not the 6 KB of A_d pieces a host-side chain would send - and no 42 lift-and-log chains per sample and slot on the host's one thread.
+// G = A_d Sigma goes to the scratch area and Sigma' = G A_d^T + noise (lower half, mirrored) to the other buffer on the VALU, as step (5) of k_batch_riccati does.
+struct DiscStep {
+    double dt;
+    CommonK ck;       // sensor-level terms of B at the X this sample starts from
+    double imu[13];   // the sample
+    GroupSensor X;    // sensor part of X at the sample's start
+    SensorState xi0;  // the slot's origin (the same in every sample of a frame: it rides here so that the frame packet BatchIn stays what the other kernels read)
+};
+struct DiscArgs {
+    BatchBufs buf;
+    const BatchIn* in;
+    const ObsStep* steps;
+    const DiscStep* dsteps;
+    BatchOut* out;
+};
+// Measurement switch, 0 in every build that ships: -DEQF_DISC_MEASURE_SKIP=1 builds k_batch_discrete without the two passes over Sigma (G = A_d Sigma and
+// Sigma' = G A_d^T + noise), so that a kernel trace of that build shows what forming A_d and B costs on its own. For attributing the kernel's time only
+// (profiles/r21_batch_discrete_kernel_stats.txt): the build's results mean nothing.
+#ifndef EQF_DISC_MEASURE_SKIP
+#define EQF_DISC_MEASURE_SKIP 0
+#endif
+constexpr int DISC_ROW = 24;                 // a landmark row of A_d: 21 sensor columns, its own 3
+constexpr int DISC_SLOT = 3 * DISC_ROW + 9;  // a landmark's rows of A_d and its 3 x 3 of B
+constexpr int DISC_NPERT = 42;               // perturbed evaluations of the sensor chain
+constexpr int DISC_SM = 441 + 252 + 66 + DISC_NPERT * 21 + BATCH_L * DISC_SLOT;
+
+// One evaluation of a0Discrete's sensor part (EqFMatrices.cpp:24-41) by one lane of k_batch_discrete: lane 42 the nominal one - it leaves cpc[0], the camera-frame
+// pose change of liftVelocityDiscrete(xi_hat) -, lane 2 j + s < 42 the one with sensor coordinate j moved by +h (s = 0) or -h (s = 1), which leaves its cpc and its
+// 21-vector epsilon_1. The chain is eqf_integrate_riccati_discrete's discrete_A (eqf_hip.hip), term for term. A function of its own (noinline): its 46-double
+// states are live only here, not across the kernel. The order keeps few of them live at once: Lambda_hat^-1, then xi_e and its lift, then the products.
+__device__ __attribute__((noinline)) void disc_sensor_eval(const DiscStep& ds, int lane, double h, double* sCol, Pose* cpc) {
+    const double dt = ds.dt;
+    const SensorState xhat = sensor_action(ds.X, ds.xi0);
+    const GroupSensor Lh = lift_discrete_sensor(xhat, ds.imu, dt);
+    if (lane == DISC_NPERT) {
+        cpc[0] = pose_mul(pose_mul(pose_inv(xhat.cam), pose_inv(Lh.A)), xhat.cam);
+        return;
+    }
+    const GroupSensor Lh_inv = group_inv(Lh);
+    const int j = lane >> 1;
+    const double hh = (lane & 1) ? -h : h;
+    // block b of the perturbation e = +-h e_j (named scalars: no array indexed at run time)
+    const auto eb = [&](int b) { return v3(j == 3 * b ? hh : 0.0, j == 3 * b + 1 ? hh : 0.0, j == 3 * b + 2 ? hh : 0.0); };
+    // xi_e = sensorChart_std.inv(e, xi0) (VIOState.cpp:114-121)
+    SensorState se;
+    se.bgyr = ds.xi0.bgyr + eb(0);
+    se.bacc = ds.xi0.bacc + eb(1);
+    se.pose = pose_mul(ds.xi0.pose, se3_exp(eb(2), eb(3)));
+    se.vel = ds.xi0.vel + eb(4);
+    se.cam = pose_mul(ds.xi0.cam, se3_exp(eb(5), eb(6)));
+    GroupSensor T;
+    {
+        const SensorState xs = sensor_action(ds.X, se);
+        const GroupSensor Lp = lift_discrete_sensor(xs, ds.imu, dt);
+        cpc[1 + lane] = pose_mul(pose_mul(pose_inv(xs.cam), pose_inv(Lp.A)), xs.cam);
+        T = group_mul(Lp, Lh_inv);
+    }
+    const GroupSensor Gp = group_mul(group_mul(ds.X, T), group_inv(ds.X));
+    const SensorState s1 = sensor_action(Gp, se);
+    V3 om, tr, omc, trc;
+    se3_log(pose_mul(pose_inv(ds.xi0.pose), s1.pose), om, tr);
+    se3_log(pose_mul(pose_inv(ds.xi0.cam), s1.cam), omc, trc);
+    double* col = sCol + lane * 21;
+    const V3 parts[7] = {s1.bgyr - ds.xi0.bgyr, s1.bacc - ds.xi0.bacc, om, tr, s1.vel - ds.xi0.vel, omc, trc};
+    for (int b = 0; b < 7; ++b) {
+        col[3 * b] = parts[b].x;
+        col[3 * b + 1] = parts[b].y;
+        col[3 * b + 2] = parts[b].z;
+    }
+}
+
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_discrete(const DiscArgs da) {
+    __shared__ double sm[DISC_SM];
+    __shared__ Pose s_cpc[1 + DISC_NPERT]; // [0] nominal, [1 + 2 j + s]: DiscreteAArgs::cpc's order
+    __shared__ double s_qp[20];            // Q and P of the slot
+    __shared__ int s_gidx[BATCH_NMAX];
+    __shared__ int s_surv[BATCH_L];
+    const BatchIn& in = da.in[blockIdx.x];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int L = BATCH_L, ld = da.buf.ld;
+    const int chart = in.ss.chart;
+    const bool ind = chart == EQVIO_COORD_INVDEPTH;
+    const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
+    const double* S0 = da.buf.sig_of(slot, cur);
+    double* S1 = da.buf.sig_of(slot, nxt);
+    const double* L0 = da.buf.lm_of(slot, cur);
+    double* L1 = da.buf.lm_of(slot, nxt);
+    double* G = da.buf.scr_of(slot);
+    const int Ns = in.Ns, n1 = 21 + 3 * Ns, K = in.k;
+    double* sA = sm;              // sensor block of A_d, row-major 21 x 21
+    double* sB = sA + 441;        // sensor rows of B, row-major 21 x 12
+    double* lm66 = sB + 252;
+    double* sCol = lm66 + 66;     // the 42 perturbed evaluations' 21-vectors
+    double* AL = sCol + DISC_NPERT * 21; // per landmark: rows of A_d (3 x 24, row-major), then B (3 x 3)
+    const double h = cbrt(2.220446049250313e-16), ih2 = 1.0 / (2.0 * h);
+
+    for (int t = tid; t < Ns; t += BATCH_T)
+        s_surv[t] = in.surv[t];
+    if (tid < 12)
+        s_qp[tid] = in.ss.Qd[tid];
+    else if (tid < 20)
+        s_qp[tid] = in.ss.Pd[tid - 12];
+    __syncthreads();
+    for (int r = tid; r < n1; r += BATCH_T)
+        s_gidx[r] = r < 21 ? r : 21 + 3 * s_surv[(r - 21) / 3] + (r - 21) % 3;
+    // the surviving landmarks' planes into the other buffer; wave 3 keeps (q, a) of its landmark and takes it through the observer steps
+    V3 p0{};
+    Qt q{};
+    double a = 1.0;
+    if (wave == 3 && lane < Ns) {
+        const int o = s_surv[lane];
+        for (int pl = 0; pl < BATCH_PLANES; ++pl)
+            L1[pl * L + lane] = L0[pl * L + o];
+        p0 = ld3(L0, L, o);
+        q = ldq(L0 + BATCH_QQ * L, L, o);
+        a = L0[BATCH_QA * L + o];
+    }
+    __syncthreads();
+
+    bool first = true; // Sigma is still the current buffer's, to be gathered
+    int samples = 0;
+    for (int s = 0; s < K; ++s) {
+        const DiscStep& ds = da.dsteps[in.obs_off + s];
+        const double dt = ds.dt;
+        if (dt > 0.0) {
+            ++samples;
+            // ---- a0Discrete's sensor part: the nominal evaluation and the 42 perturbed ones (wave 0); B's sensor rows and the landmark factors (the other waves)
+            if (wave == 0) {
+                if (lane <= DISC_NPERT)
+                    disc_sensor_eval(ds, lane, h, sCol, s_cpc);
+            } else {
+                for (int t = tid - 64; t < 252; t += BATCH_T - 64)
+                    sB[t] = sensor_Bs_entry(ds.ck, t);
+                for (int t = tid - 64; t < 66; t += BATCH_T - 64)
+                    lm66[t] = ds.ck.lm[t];
+            }
+            __syncthreads();
+            // ---- the sensor block: the pairs differenced
+            for (int t = tid; t < 441; t += BATCH_T) {
+                const int r = t / 21, j = t % 21;
+                sA[t] = (sCol[(2 * j) * 21 + r] - sCol[(2 * j + 1) * 21 + r]) * ih2;
+            }
+            // ---- the landmarks' rows: a lane per landmark, six of its 24 central differences per wave; wave 0 also its 3 x 3 of B
+            if (lane < Ns) {
+                const int i = lane;
+                const V3 q0 = ld3(L1, L, i);
+                const Sot3 Qi{ldq(L1 + BATCH_QQ * L, L, i), L1[BATCH_QA * L + i]};
+                const V3 qh = (1.0 / Qi.a) * q_rot(q_inv(Qi.R), q0);
+                const Pose cpc0 = s_cpc[0];
+                const Sot3 QLh_inv = sot3_inv(lift_q(cpc0, qh)); // liftVelocityDiscrete(xi_hat)^-1, landmark i
+                double* row = AL + i * DISC_SLOT;
+#pragma unroll 1
+                for (int c = 6 * wave; c < 6 * wave + 6; ++c) {
+                    V3 ep, em;
+                    if (c < 21) {
+                        ep = a0_discrete_landmark(chart, Qi, QLh_inv, s_cpc[1 + 2 * c], q0, q0);
+                        em = a0_discrete_landmark(chart, Qi, QLh_inv, s_cpc[2 + 2 * c], q0, q0);
+                    } else {
+                        const int k = c - 21;
+                        const V3 e = V3{k == 0 ? h : 0.0, k == 1 ? h : 0.0, k == 2 ? h : 0.0};
+                        ep = a0_discrete_landmark(chart, Qi, QLh_inv, cpc0, chart_bwd(chart, e, q0), q0);
+                        em = a0_discrete_landmark(chart, Qi, QLh_inv, cpc0, chart_bwd(chart, -e, q0), q0);
+                    }
+                    const V3 d = ih2 * (ep - em);
+                    row[c] = d.x;
+                    row[DISC_ROW + c] = d.y;
+                    row[2 * DISC_ROW + c] = d.z;
+                }
+                if (wave == 0) {
+                    const M3 e2i = ind ? ld_cc(L1, L, i, CC_E2I) : M3{};
+                    double al[45], bl[9];
+                    assemble_landmark<0>(lm66, chart, q0, Qi.R, Qi.a, e2i, M3{}, al, bl);
+                    for (int e = 0; e < 9; ++e)
+                        row[3 * DISC_ROW + e] = bl[e];
+                }
+            }
+            __syncthreads();
+            // ---- Sigma' = A_d Sigma A_d^T + dt (B Q B^T + P)
+            // row r of A_d applied to a vector given entry by entry (k_batch_riccati's phi_row)
+            auto ad_row = [&](int r, auto v) -> double {
+                double acc = 0.0;
+                if (r < 21) {
+                    for (int k = 0; k < 21; ++k)
+                        acc += sA[r * 21 + k] * v(k);
+                } else {
+                    const int i = (r - 21) / 3, aa = (r - 21) % 3;
+                    const double* rw = AL + i * DISC_SLOT + aa * DISC_ROW;
+                    for (int k = 0; k < 21; ++k)
+                        acc += rw[k] * v(k);
+                    for (int b = 0; b < 3; ++b)
+                        acc += rw[21 + b] * v(21 + 3 * i + b);
+                }
+                return acc;
+            };
+            auto b_entry = [&](int r, int e) -> double {
+                if (r < 21)
+                    return sB[r * 12 + e];
+                return e < 3 ? AL[((r - 21) / 3) * DISC_SLOT + 3 * DISC_ROW + ((r - 21) % 3) * 3 + e] : 0.0;
+            };
+            if constexpr (!(EQF_DISC_MEASURE_SKIP & 1)) {
+                const double* Ssrc = first ? S0 : S1;
+                for (int t = tid; t < n1 * n1; t += BATCH_T) {
+                    const int r = t % n1, c = t / n1;
+                    const double* col = Ssrc + (size_t)s_gidx[c] * ld;
+                    G[r + (size_t)c * ld] = ad_row(r, [&](int k) { return col[s_gidx[k]]; });
+                }
+                __syncthreads();
+                for (int t = tid; t < n1 * n1; t += BATCH_T) {
+                    const int r = t % n1, c = t / n1;
+                    if (r < c)
+                        continue;
+                    double v = ad_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
+                    double nz = 0.0;
+                    for (int e = 0; e < 12; ++e)
+                        nz += b_entry(r, e) * s_qp[e] * b_entry(c, e);
+                    if (r == c)
+                        nz += s_qp[12 + (r < 21 ? r / 3 : 7)];
+                    v += dt * nz;
+                    S1[r + (size_t)c * ld] = v;
+                    S1[c + (size_t)r * ld] = v;
+                }
+                if (first) { // the gathered rows' readers are behind the barrier above; the next reader is behind the sample's last one
+                    for (int r = tid; r < n1; r += BATCH_T)
+                        s_gidx[r] = r;
+                    first = false;
+                }
+            }
+        }
+        // ---- this sample's observer step of the landmarks
+        if (wave == 3 && lane < Ns) {
+            observer_chain(da.steps + in.obs_off + s, 1, p0, q, a);
+            L1[BATCH_QQ * L + lane] = q.w;
+            L1[(BATCH_QQ + 1) * L + lane] = q.x;
+            L1[(BATCH_QQ + 2) * L + lane] = q.y;
+            L1[(BATCH_QQ + 3) * L + lane] = q.z;
+            L1[BATCH_QA * L + lane] = a;
+        }
+        __syncthreads();
+    }
+    if (first) // no sample moved Sigma: the gathered Sigma as it is
+        for (int t = tid; t < n1 * n1; t += BATCH_T) {
+            const int r = t % n1, c = t / n1;
+            S1[r + (size_t)c * ld] = S0[s_gidx[r] + (size_t)s_gidx[c] * ld];
+        }
+    if (tid == 0) {
+        da.out[blockIdx.x].ric_samples = samples;
+        da.out[blockIdx.x].ric_squarings = 0;
     }
 }
 

@@ -44,7 +44,7 @@ struct eqf_batch {
         double inn_nis = 0.0, inn_logdet = 0.0;
         long tot_updates = 0, tot_dof = 0; // their sums over the steps that carried EQF_BATCH_UPDATED, in step order (eqf_batch_innovation_totals)
         double tot_nis = 0.0, tot_logdet = 0.0;
-        int ric_samples = 0, ric_squarings = 0; // the last accurate step's counters (eqf_batch_last_riccati); 0 after a fast step or a copy into the slot
+        int ric_samples = 0, ric_squarings = 0; // the last accurate or discrete step's counters (eqf_batch_last_riccati); 0 after a fast step or a copy into the slot
         eqvio_settings set{}; // the slot's own settings (eqf_batch_set_slot_settings; eqf_batch_create's until then)
         BatchSlotSet ss{};    // what the kernels read of them: copied into the slot's packet entry of every step
     };
@@ -55,6 +55,7 @@ struct eqf_batch {
     BatchPacket<BatchOut> out;
     BatchPacket<ObsStep> steps;
     BatchPacket<RicStep> rsteps; // eqf_batch_step_accurate: the sensor terms of A and B per sample
+    BatchPacket<DiscStep> dsteps; // eqf_batch_step_discrete: the sensor terms of B, the sample and the sensor parts of xi0 and X per sample
     BatchPacket<NeesIn> nin; // eqf_batch_nees, eqf_batch_consistency
     BatchPacket<NeesOut> nout;
     BatchPacket<eqf_batch_consistency_record> rec;
@@ -223,6 +224,7 @@ void eqf_batch_destroy(eqf_batch* b) {
     b->out.release();
     b->steps.release();
     b->rsteps.release();
+    b->dsteps.release();
     b->nin.release();
     b->nout.release();
     b->rec.release();
@@ -382,10 +384,13 @@ int eqf_batch_last_result(const eqf_batch* b, int slot, int* flags, double* dept
 }
 
 namespace {
-// eqf_batch_step and eqf_batch_step_accurate: one screening, one packet, one round trip, one host half of the results. accurate: the frame's propagation is
-// integrateUpToTime's with fastRiccati == false - the sensor terms of A and B at every sample's X ride along with the observer steps, and k_batch_riccati runs
-// in front of k_batch_frame_tail on the same stream; imu13_mean and dt_total are not read. (A template parameter: the fast instance is the function it was.)
-template <bool accurate> int batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
+// eqf_batch_step, eqf_batch_step_accurate and eqf_batch_step_discrete: one screening, one packet, one round trip, one host half of the results. STEP_ACCURATE:
+// the frame's propagation is integrateUpToTime's with fastRiccati == false - the sensor terms of A and B at every sample's X ride along with the observer steps,
+// and k_batch_riccati runs in front of k_batch_frame_tail on the same stream; imu13_mean and dt_total are not read. STEP_DISCRETE: the same with
+// useDiscreteStateMatrix == true - what rides along per sample is the sensor terms of B, the sample and the sensor parts of xi0 and X (DiscStep), and
+// k_batch_discrete runs in k_batch_riccati's place. (A template parameter: the fast instance is the function it was.)
+enum { STEP_FAST, STEP_ACCURATE, STEP_DISCRETE };
+template <int mode> int batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
     if (!b || count < 0 || (count > 0 && (!frames || !status)))
         return EQF_E_BAD_ARG;
     if (count == 0)
@@ -400,8 +405,12 @@ template <bool accurate> int batch_step(eqf_batch* b, int count, const eqf_batch
         return rc;
     if (int rc = b->steps.grow(std::max(total_steps, 64)))
         return rc;
-    if (accurate)
+    constexpr bool accurate = mode != STEP_FAST; // a Riccati step per sample, by either of the two per-sample kernels
+    if (mode == STEP_ACCURATE)
         if (int rc = b->rsteps.grow(std::max(total_steps, 64)))
+            return rc;
+    if (mode == STEP_DISCRETE)
+        if (int rc = b->dsteps.grow(std::max(total_steps, 64)))
             return rc;
     // host half: validation, the landmark bookkeeping the ids decide, the sensor-level terms and the observer steps' sensor part
     BatchScreen scr(b, count);
@@ -485,10 +494,17 @@ template <bool accurate> int batch_step(eqf_batch* b, int count, const eqf_batch
             std::memset(&in.ck, 0, sizeof(in.ck));
         GroupSensor X = sl.X;
         for (int s = 0; s < f.k; ++s) {
-            if (accurate) { // integrateRiccatiStateAccurate at the X the samples before this one have produced
+            if (mode == STEP_ACCURATE) { // integrateRiccatiStateAccurate at the X the samples before this one have produced
                 RicStep& rs = b->rsteps.h[nsteps + s];
                 rs.dt = f.dt_k[s];
                 compute_common_at(X, sl.xi0, f.imu13_k + 13 * s, cm, rs.ck);
+            } else if (mode == STEP_DISCRETE) { // integrateRiccatiStateDiscrete there: B's sensor terms, and what the device forms A_d from
+                DiscStep& ds = b->dsteps.h[nsteps + s];
+                ds.dt = f.dt_k[s];
+                compute_common_at(X, sl.xi0, f.imu13_k + 13 * s, cm, ds.ck);
+                std::memcpy(ds.imu, f.imu13_k + 13 * s, sizeof(ds.imu));
+                ds.X = X;
+                ds.xi0 = sl.xi0;
             }
             observer_host_step(X, sl.xi0, f.imu13_k + 13 * s, f.dt_k[s], sl.set.useDiscreteVelocityLift, b->steps.h[nsteps + s]);
         }
@@ -506,12 +522,18 @@ template <bool accurate> int batch_step(eqf_batch* b, int count, const eqf_batch
     const BatchArgs ba{b->buf, b->in.d, b->steps.d, b->out.d};
     if (nsteps) // the observer steps ride along, in front of the launch on the same stream
         HIPCHK(hipMemcpyAsync(b->steps.d, b->steps.h, sizeof(ObsStep) * nsteps, hipMemcpyHostToDevice, b->stream));
-    if (accurate && nsteps)
+    if (mode == STEP_ACCURATE && nsteps)
         HIPCHK(hipMemcpyAsync(b->rsteps.d, b->rsteps.h, sizeof(RicStep) * nsteps, hipMemcpyHostToDevice, b->stream));
+    if (mode == STEP_DISCRETE && nsteps)
+        HIPCHK(hipMemcpyAsync(b->dsteps.d, b->dsteps.h, sizeof(DiscStep) * nsteps, hipMemcpyHostToDevice, b->stream));
     const RicArgs ra{b->buf, b->in.d, b->steps.d, b->rsteps.d, b->out.d};
+    const DiscArgs da{b->buf, b->in.d, b->steps.d, b->dsteps.d, b->out.d};
     const auto launch = [&] {
-        if (accurate) {
+        if (mode == STEP_ACCURATE) {
             hipLaunchKernelGGL(k_batch_riccati, dim3(nin), dim3(BATCH_T), 0, b->stream, ra);
+            hipLaunchKernelGGL(k_batch_frame_tail, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
+        } else if (mode == STEP_DISCRETE) {
+            hipLaunchKernelGGL(k_batch_discrete, dim3(nin), dim3(BATCH_T), 0, b->stream, da);
             hipLaunchKernelGGL(k_batch_frame_tail, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
         } else {
             hipLaunchKernelGGL(k_batch_frame, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
@@ -569,8 +591,9 @@ template <bool accurate> int batch_step(eqf_batch* b, int count, const eqf_batch
 }
 } // namespace
 
-int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<false>(b, count, frames, status); }
-int eqf_batch_step_accurate(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<true>(b, count, frames, status); }
+int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<STEP_FAST>(b, count, frames, status); }
+int eqf_batch_step_accurate(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<STEP_ACCURATE>(b, count, frames, status); }
+int eqf_batch_step_discrete(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) { return batch_step<STEP_DISCRETE>(b, count, frames, status); }
 int eqf_batch_last_riccati(const eqf_batch* b, int slot, int* samples, int* max_squarings) {
     if (!batch_slot_ok(b, slot))
         return EQF_E_BAD_ARG;

@@ -57,18 +57,6 @@ int pick_ld(int x) {
     return ld;
 }
 
-struct SensorState { // host-resident 46 doubles
-    V3 bgyr, bacc;
-    Pose pose;
-    V3 vel;
-    Pose cam;
-};
-struct GroupSensor {
-    V3 bgyr, bacc; // beta
-    Pose A;
-    V3 w;
-    Pose B;
-};
 SensorState unpack_sensor(const double* s) {
     SensorState r;
     r.bgyr = v3(s[0], s[1], s[2]);
@@ -114,26 +102,6 @@ void pack_group(const GroupSensor& g, double* s) {
     pack_pose(g.A, s + 6, s + 10);
     pack_v3(g.w, s + 13);
     pack_pose(g.B, s + 16, s + 20);
-}
-// sensorStateGroupAction (src/mathematical/VIOGroup.cpp:25-32)
-SensorState sensor_action(const GroupSensor& X, const SensorState& s) {
-    SensorState r;
-    r.bgyr = s.bgyr + X.bgyr;
-    r.bacc = s.bacc + X.bacc;
-    r.pose = pose_mul(s.pose, X.A);
-    r.vel = q_rot(q_inv(X.A.R), s.vel - X.w);
-    r.cam = pose_mul(pose_mul(pose_inv(X.A), s.cam), X.B);
-    return r;
-}
-// VIOGroup::operator* on the sensor part (VIOGroup.cpp:71-92): r = a * b
-GroupSensor group_mul(const GroupSensor& a, const GroupSensor& b) {
-    GroupSensor r;
-    r.bgyr = a.bgyr + b.bgyr;
-    r.bacc = a.bacc + b.bacc;
-    r.A = pose_mul(a.A, b.A);
-    r.B = pose_mul(a.B, b.B);
-    r.w = a.w + q_rot(a.A.R, b.w);
-    return r;
 }
 
 } // namespace
@@ -2291,29 +2259,7 @@ int eqf_integrate_riccati_accurate(eqf_ctx* c, const double* imu13, double dt, c
 }
 
 // ---- integrateRiccatiStateDiscrete (VIO_eqf.cpp:93-103, EqFMatrices.cpp:24-41) -----------------------------------------------------------
-static GroupSensor lift_discrete_sensor(const SensorState& xs, const double* imu, double dt) { // liftVelocityDiscrete, sensor part (VIOGroup.cpp:229-250)
-    const V3 gyr = v3(imu[1], imu[2], imu[3]) - xs.bgyr;
-    const V3 acc = v3(imu[4], imu[5], imu[6]) - xs.bacc;
-    const V3 gdir = q_rot(q_inv(xs.pose.R), v3(0, 0, 1));
-    GroupSensor L;
-    L.bgyr = dt * v3(imu[7], imu[8], imu[9]);
-    L.bacc = dt * v3(imu[10], imu[11], imu[12]);
-    L.A.R = so3_exp(dt * gyr);
-    const V3 x = dt * q_rot(xs.pose.R, xs.vel) + (0.5 * dt * dt) * (q_rot(xs.pose.R, acc) + v3(0, 0, -kGravity));
-    L.A.x = q_rot(q_inv(xs.pose.R), x);
-    L.B = pose_mul(pose_mul(pose_inv(xs.cam), L.A), xs.cam);
-    L.w = xs.vel - (xs.vel + dt * (acc - kGravity * gdir));
-    return L;
-}
-static GroupSensor group_inv(const GroupSensor& X) { // VIOGroup::inverse, sensor part (VIOGroup.cpp:108-120)
-    GroupSensor r;
-    r.bgyr = -X.bgyr;
-    r.bacc = -X.bacc;
-    r.A = pose_inv(X.A);
-    r.B = pose_inv(X.B);
-    r.w = -q_rot(q_inv(X.A.R), X.w);
-    return r;
-}
+// (lift_discrete_sensor, group_inv, group_mul, sensor_action: eqf_kernels.hpp, callable on the device as well - k_batch_discrete runs this chain there)
 int eqf_integrate_riccati_discrete(eqf_ctx* c, const double* imu13, double dt, const double* Qdiag12, const double* Pdiag8) {
     // (B_t at the current X (inputMatrixB), for dt (B Q B^T + P). "The last reader of Q" is k_discrete_A below, not k_assemble_AB: the event is recorded there)
     EQFCHK(riccati_entry(c, imu13, dt, Qdiag12, Pdiag8, RiccatiEntry{true, true, false}));

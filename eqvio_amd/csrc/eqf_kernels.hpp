@@ -2549,6 +2549,64 @@ __global__ void k_gather_landmarks_aos(int N, int Ncap, const double* __restrict
         out[8 * i + 3 + c] = Qq[c * Ncap + i];
     out[8 * i + 7] = Qa[i];
 }
+// ---- the sensor part of the state and of the group, and the four helpers of a0Discrete's sensor chain: host code everywhere (eqf_hip.hip, eqf_batch_host.hpp) and,
+// in k_batch_discrete (eqf_batch.hpp), device code - the same expressions on both sides.
+struct SensorState { // host-resident 46 doubles
+    V3 bgyr, bacc;
+    Pose pose;
+    V3 vel;
+    Pose cam;
+};
+struct GroupSensor {
+    V3 bgyr, bacc; // beta
+    Pose A;
+    V3 w;
+    Pose B;
+};
+// sensorStateGroupAction (src/mathematical/VIOGroup.cpp:25-32)
+__host__ __device__ inline SensorState sensor_action(const GroupSensor& X, const SensorState& s) {
+    SensorState r;
+    r.bgyr = s.bgyr + X.bgyr;
+    r.bacc = s.bacc + X.bacc;
+    r.pose = pose_mul(s.pose, X.A);
+    r.vel = q_rot(q_inv(X.A.R), s.vel - X.w);
+    r.cam = pose_mul(pose_mul(pose_inv(X.A), s.cam), X.B);
+    return r;
+}
+// VIOGroup::operator* on the sensor part (VIOGroup.cpp:71-92): r = a * b
+__host__ __device__ inline GroupSensor group_mul(const GroupSensor& a, const GroupSensor& b) {
+    GroupSensor r;
+    r.bgyr = a.bgyr + b.bgyr;
+    r.bacc = a.bacc + b.bacc;
+    r.A = pose_mul(a.A, b.A);
+    r.B = pose_mul(a.B, b.B);
+    r.w = a.w + q_rot(a.A.R, b.w);
+    return r;
+}
+__host__ __device__ inline GroupSensor lift_discrete_sensor(const SensorState& xs, const double* imu, double dt) { // liftVelocityDiscrete, sensor part (VIOGroup.cpp:229-250)
+    const V3 gyr = v3(imu[1], imu[2], imu[3]) - xs.bgyr;
+    const V3 acc = v3(imu[4], imu[5], imu[6]) - xs.bacc;
+    const V3 gdir = q_rot(q_inv(xs.pose.R), v3(0, 0, 1));
+    GroupSensor L;
+    L.bgyr = dt * v3(imu[7], imu[8], imu[9]);
+    L.bacc = dt * v3(imu[10], imu[11], imu[12]);
+    L.A.R = so3_exp(dt * gyr);
+    const V3 x = dt * q_rot(xs.pose.R, xs.vel) + (0.5 * dt * dt) * (q_rot(xs.pose.R, acc) + v3(0, 0, -kGravity));
+    L.A.x = q_rot(q_inv(xs.pose.R), x);
+    L.B = pose_mul(pose_mul(pose_inv(xs.cam), L.A), xs.cam);
+    L.w = xs.vel - (xs.vel + dt * (acc - kGravity * gdir));
+    return L;
+}
+__host__ __device__ inline GroupSensor group_inv(const GroupSensor& X) { // VIOGroup::inverse, sensor part (VIOGroup.cpp:108-120)
+    GroupSensor r;
+    r.bgyr = -X.bgyr;
+    r.bacc = -X.bacc;
+    r.A = pose_inv(X.A);
+    r.B = pose_inv(X.B);
+    r.w = -q_rot(q_inv(X.A.R), X.w);
+    return r;
+}
+
 // integrateRiccatiStateDiscrete (VIO_eqf.cpp:93-103): A_d = numericalDifferential of a0Discrete (EqFMatrices.cpp:24-41) at 0, central
 // differences with h = cbrt(eps) (Geometry.cpp:25-36). a0Discrete has the arrow structure of A: a landmark's coordinates move only its own
 // three rows; the 21 sensor coordinates move everything. The sensor-level part of the 43 evaluations (nominal + 21 x +-h) is O(1) and done

@@ -116,6 +116,7 @@ VIOFilterBatch::VIOFilterBatch(eqf_batch* b) : batch(b) {
     const int slots = eqf_batch_slots(b);
     slotv.resize(slots);
     riccati_.assign(slots, EQVIO_BATCH_RICCATI_FAST);
+    stateMatrix_.assign(slots, EQVIO_BATCH_STATE_MATRIX_CONTINUOUS);
     for (int k = 0; k < slots; ++k) {
         try {
             resetSlot(k);
@@ -143,6 +144,19 @@ int VIOFilterBatch::setRiccatiMode(int k, int mode) {
     return 0;
 }
 int VIOFilterBatch::riccatiMode(int k) const { return k >= 0 && k < (int)slotv.size() ? riccati_[k] : EQF_E_BAD_ARG; }
+int VIOFilterBatch::setStateMatrix(int k, int kind) {
+    if ((kind != EQVIO_BATCH_STATE_MATRIX_CONTINUOUS && kind != EQVIO_BATCH_STATE_MATRIX_DISCRETE) || k >= (int)slotv.size())
+        return EQF_E_BAD_ARG;
+    if (k < 0)
+        stateMatrix_.assign(slotv.size(), kind);
+    else
+        stateMatrix_[k] = kind;
+    return 0;
+}
+int VIOFilterBatch::callOf(int k) const { // integrateUpToTime's choice (src/VIOFilter.cpp:160-178): the state matrix matters to an accurate slot only
+    return riccati_[k] != EQVIO_BATCH_RICCATI_ACCURATE ? 0 : stateMatrix_[k] == EQVIO_BATCH_STATE_MATRIX_DISCRETE ? 2 : 1;
+}
+int VIOFilterBatch::stateMatrix(int k) const { return k >= 0 && k < (int)slotv.size() ? stateMatrix_[k] : EQF_E_BAD_ARG; }
 VIOFilterBatch::InnovationTotals VIOFilterBatch::innovationTotals(int k) const {
     InnovationTotals t;
     check(eqf_batch_innovation_totals(batch, k, &t.updates, &t.dof, &t.nis, &t.logdet), "eqf_batch_innovation_totals");
@@ -290,29 +304,33 @@ void VIOFilterBatch::stepPrepared(const int* slots, const double* stamps, int* s
         frames_[t].dt_k = dts_[t].data();
     }
     st_.resize(frames_.size());
-    // every listed slot to the call of its mode: a step whose slots are all of one mode is one device call, a mixed step two
+    // every listed slot to the call of its mode, in the order fast, accurate, discrete: a step whose slots agree is one device call, a mixed step up to three
+    const auto call = [&](int which, int n, const eqf_batch_frame* fr, int* st) {
+        if (which == 2)
+            check(eqf_batch_step_discrete(batch, n, fr, st), "eqf_batch_step_discrete");
+        else if (which == 1)
+            check(eqf_batch_step_accurate(batch, n, fr, st), "eqf_batch_step_accurate");
+        else
+            check(eqf_batch_step(batch, n, fr, st), "eqf_batch_step");
+    };
     bool mixed = false;
     for (size_t t = 1; t < frames_.size(); ++t)
-        mixed = mixed || riccati_[frames_[t].slot] != riccati_[frames_[0].slot];
+        mixed = mixed || callOf(frames_[t].slot) != callOf(frames_[0].slot);
     if (!mixed) {
-        if (riccati_[frames_[0].slot] == EQVIO_BATCH_RICCATI_ACCURATE)
-            check(eqf_batch_step_accurate(batch, (int)frames_.size(), frames_.data(), st_.data()), "eqf_batch_step_accurate");
-        else
-            check(eqf_batch_step(batch, (int)frames_.size(), frames_.data(), st_.data()), "eqf_batch_step");
+        call(callOf(frames_[0].slot), (int)frames_.size(), frames_.data(), st_.data());
     } else {
         std::vector<int> pst;
-        for (const int mode : {EQVIO_BATCH_RICCATI_FAST, EQVIO_BATCH_RICCATI_ACCURATE}) {
+        for (const int which : {0, 1, 2}) {
             part_.clear(), partOf_.clear();
             for (size_t t = 0; t < frames_.size(); ++t)
-                if (riccati_[frames_[t].slot] == mode) {
+                if (callOf(frames_[t].slot) == which) {
                     part_.push_back(frames_[t]);
                     partOf_.push_back(t);
                 }
+            if (part_.empty())
+                continue;
             pst.assign(part_.size(), 0);
-            if (mode == EQVIO_BATCH_RICCATI_ACCURATE)
-                check(eqf_batch_step_accurate(batch, (int)part_.size(), part_.data(), pst.data()), "eqf_batch_step_accurate");
-            else
-                check(eqf_batch_step(batch, (int)part_.size(), part_.data(), pst.data()), "eqf_batch_step");
+            call(which, (int)part_.size(), part_.data(), pst.data());
             for (size_t t = 0; t < part_.size(); ++t)
                 st_[partOf_[t]] = pst[t];
         }
@@ -497,6 +515,8 @@ int eqvio_batch_set_slot_settings(eqvio_batch* b, int slot, const eqvio_settings
 }
 int eqvio_batch_set_slot_riccati(eqvio_batch* b, int slot, int mode) { return b ? b->f->setRiccatiMode(slot, mode) : EQF_E_BAD_ARG; }
 int eqvio_batch_get_slot_riccati(const eqvio_batch* b, int slot) { return b ? b->f->riccatiMode(slot) : EQF_E_BAD_ARG; }
+int eqvio_batch_set_slot_state_matrix(eqvio_batch* b, int slot, int kind) { return b ? b->f->setStateMatrix(slot, kind) : EQF_E_BAD_ARG; }
+int eqvio_batch_get_slot_state_matrix(const eqvio_batch* b, int slot) { return b ? b->f->stateMatrix(slot) : EQF_E_BAD_ARG; }
 int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out) {
     return b ? eqf_batch_get_slot_settings(b->f->core(), slot, out) : EQF_E_BAD_ARG;
 }

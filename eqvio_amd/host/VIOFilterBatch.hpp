@@ -57,6 +57,10 @@ class VIOFilterBatch {
     // EQF_E_BAD_ARG (bad mode or slot; nothing changes); riccatiMode returns the mode or EQF_E_BAD_ARG.
     int setRiccatiMode(int slot, int mode);
     int riccatiMode(int slot) const;
+    // The state matrix an ACCURATE slot's Riccati steps use, the reference's useDiscreteStateMatrix (include/eqvio_batch.h): EQVIO_BATCH_STATE_MATRIX_CONTINUOUS
+    // (every slot starts with it) or _DISCRETE (eqf_batch_step_discrete). A fast slot ignores it. Kept and refused like the Riccati mode.
+    int setStateMatrix(int slot, int kind);
+    int stateMatrix(int slot) const;
     // Entry e: slot dst[e] becomes slot src[e] as it was before the call - the EqF state on the device (eqf_batch_copy_slots: one launch, same status codes)
     // and the host half: IMU buffer, current time, initialised flag. The destination keeps its settings and innovation totals. A refused entry changes nothing.
     void copySlots(int count, const int* src, const int* dst, int* status);
@@ -105,6 +109,9 @@ class VIOFilterBatch {
     eqf_batch* batch = nullptr;
     std::vector<Slot> slotv;
     std::vector<int> riccati_; // per slot: EQVIO_BATCH_RICCATI_*
+    std::vector<int> stateMatrix_; // per slot: EQVIO_BATCH_STATE_MATRIX_*
+    // the device call slot k's frames go to: 0 eqf_batch_step, 1 eqf_batch_step_accurate, 2 eqf_batch_step_discrete
+    int callOf(int k) const;
     std::vector<eqf_batch_frame> part_; // stepPrepared: the frames of one mode
     std::vector<size_t> partOf_;
 };

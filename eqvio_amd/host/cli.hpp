@@ -171,8 +171,9 @@ inline std::string warmupSweepRefusal(const Sweep& sw) {
     return "";
 }
 
-// --batchRiccati M[,M...] with --batch B: the slots' propagation (eqvio_batch_set_slot_riccati), M = fast | accurate; one value for every slot, or B values,
-// one per slot. Returns what the flag is refused for, before any file or device is opened (empty: nothing); modes then holds B entries.
+// --batchRiccati M[,M...] with --batch B: the slots' propagation (eqvio_batch_set_slot_riccati, _set_slot_state_matrix), M = fast | accurate | discrete -
+// discrete is the accurate mode with the discrete state matrix, BATCH_CLI_DISCRETE in `modes` -; one value for every slot, or B values, one per slot. Returns what the flag is refused for, before any file or device is opened (empty: nothing); modes then holds B entries.
+constexpr int BATCH_CLI_DISCRETE = 2; // the flag's third word: EQVIO_BATCH_RICCATI_ACCURATE with EQVIO_BATCH_STATE_MATRIX_DISCRETE
 inline std::string batchRiccatiRefusal(const std::string& text, int B, std::vector<int>& modes) {
     if (B == 0)
         return "--batchRiccati needs --batch B (the mode is the filter batch's, per slot)";
@@ -180,9 +181,9 @@ inline std::string batchRiccatiRefusal(const std::string& text, int B, std::vect
     for (size_t p = 0; p <= text.size();) {
         const size_t c = std::min(text.find(',', p), text.size());
         const std::string w = text.substr(p, c - p);
-        if (w != "fast" && w != "accurate")
-            return "--batchRiccati: '" + w + "' is neither fast nor accurate";
-        given.push_back(w == "accurate" ? EQVIO_BATCH_RICCATI_ACCURATE : EQVIO_BATCH_RICCATI_FAST);
+        if (w != "fast" && w != "accurate" && w != "discrete")
+            return "--batchRiccati: '" + w + "' is neither fast nor accurate nor discrete";
+        given.push_back(w == "discrete" ? BATCH_CLI_DISCRETE : w == "accurate" ? EQVIO_BATCH_RICCATI_ACCURATE : EQVIO_BATCH_RICCATI_FAST);
         p = c + 1;
     }
     if (given.size() != 1 && (int)given.size() != B)
@@ -192,7 +193,10 @@ inline std::string batchRiccatiRefusal(const std::string& text, int B, std::vect
         modes[k] = given[k];
     return "";
 }
-inline const char* batchRiccatiName(int mode) { return mode == EQVIO_BATCH_RICCATI_ACCURATE ? "accurate" : "fast"; }
+inline const char* batchRiccatiName(int mode) { return mode == BATCH_CLI_DISCRETE ? "discrete" : mode == EQVIO_BATCH_RICCATI_ACCURATE ? "accurate" : "fast"; }
+// the two per-slot choices one word of the flag stands for
+inline int batchCliRiccati(int mode) { return mode == EQVIO_BATCH_RICCATI_FAST ? EQVIO_BATCH_RICCATI_FAST : EQVIO_BATCH_RICCATI_ACCURATE; }
+inline int batchCliStateMatrix(int mode) { return mode == BATCH_CLI_DISCRETE ? EQVIO_BATCH_STATE_MATRIX_DISCRETE : EQVIO_BATCH_STATE_MATRIX_CONTINUOUS; }
 
 // the filter settings as the C-ABI's eqvio_settings
 inline eqvio_settings batchSettings(const VIOFilter::Settings& fs) {

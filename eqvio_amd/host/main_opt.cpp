@@ -33,7 +33,7 @@ static void usage() {
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
               "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]\n"
-              "                            [--batchRiccati fast|accurate[,...]]]\n"
+              "                            [--batchRiccati fast|accurate|discrete[,...]]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
@@ -55,8 +55,9 @@ static void usage() {
               "  --warmupOnFilter   with --warmup F (F > 0): the F warm-up frames run on ONE single filter (the low-latency context path) with the command line's\n"
               "              settings instead of in slot 0; the filter is then loaded into all B slots on the device in one call, the sweep's values are applied and\n"
               "              scoring starts. With --record DIR every slot starts its files at the branch.\n"
-              "  --batchRiccati M[,M...]   with --batch B: the slots' propagation, M = fast (one fast Riccati step per frame) or accurate (the reference's default,\n"
-              "              fastRiccati: false: one accurate Riccati step per IMU sample); one value for every slot, or B values, one per slot. With this flag\n"
+              "  --batchRiccati M[,M...]   with --batch B: the slots' propagation, M = fast (one fast Riccati step per frame), accurate (the reference's default,\n"
+              "              fastRiccati: false: one accurate Riccati step per IMU sample) or discrete (accurate with the discrete state matrix,\n"
+              "              useDiscreteStateMatrix: true); one value for every slot, or B values, one per slot. With this flag\n"
               "              --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each slot's lines name its mode.");
 }
 
@@ -72,7 +73,7 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     }
     VIOFilterBatch filters(core); // every slot as VIOFilter(fs): it initialises itself from its first IMU sample
     for (int k = 0; k < B && !riccati.empty(); ++k) // kept through the warm-up's copies, like the settings
-        check_rc(filters.setRiccatiMode(k, riccati[k]), "--batchRiccati");
+        check_rc(filters.setRiccatiMode(k, batchCliRiccati(riccati[k])), "--batchRiccati"), check_rc(filters.setStateMatrix(k, batchCliStateMatrix(riccati[k])), "--batchRiccati");
     auto label = [&](int k) {
         return (swept ? " " + sweep.name + "=" + sweep.values[k] : std::string()) + (riccati.empty() ? std::string() : std::string(" riccati ") + batchRiccatiName(riccati[k]));
     };

@@ -22,7 +22,7 @@ static void usage() {
     std::puts("usage: eqvio_sim [--duration S] [--trajectory wave|square|sine|line] [--numPoints N] [--numWalls W] [--wallDistance D]\n"
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
               "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
-              "                 [--sweep NAME=v0,v1,...] [--innovation] [--record DIR] [--batchRiccati fast|accurate[,...]]\n"
+              "                 [--sweep NAME=v0,v1,...] [--innovation] [--record DIR] [--batchRiccati fast|accurate|discrete[,...]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
               "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
@@ -37,8 +37,9 @@ static void usage() {
               "  --record DIR   with --batch B: writes every run's consistency record to DIR/run_<k>/ - nees.csv (NEES, PoseNEES, AttitudeNEES),\n"
               "              poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv and landmarkError.csv, in the formats of --output - from one\n"
               "              launch per frame for all runs (eqvio_batch_run_sim_recorded).\n"
-              "  --batchRiccati M[,M...]   with --batch B: the runs' propagation, M = fast (one fast Riccati step per frame) or accurate (the reference's\n"
-              "              default, fastRiccati: false: one accurate Riccati step per IMU sample); one value for every run, or B values, one per run.\n"
+              "  --batchRiccati M[,M...]   with --batch B: the runs' propagation, M = fast (one fast Riccati step per frame), accurate (the reference's\n"
+              "              default, fastRiccati: false: one accurate Riccati step per IMU sample) or discrete (accurate with the discrete state matrix,\n"
+              "              useDiscreteStateMatrix: true); one value for every run, or B values, one per run.\n"
               "              With this flag --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each run's line names its mode.");
 }
 
@@ -94,7 +95,7 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
         }
     }
     for (int k = 0; k < B && !riccati.empty(); ++k)
-        if ((rc = eqvio_batch_set_slot_riccati(b, k, riccati[k]))) {
+        if ((rc = eqvio_batch_set_slot_riccati(b, k, batchCliRiccati(riccati[k]))) || (rc = eqvio_batch_set_slot_state_matrix(b, k, batchCliStateMatrix(riccati[k])))) {
             std::fprintf(stderr, "eqvio_sim: --batchRiccati: slot %d: %s\n", k, eqf_error_string(rc));
             eqvio_batch_destroy(b);
             release();

@@ -3,11 +3,12 @@
  *
  * A slot is what one reference VIOFilter does in processVisionData (src/VIOFilter.cpp:194-241): the propagation - with fast Riccati (eqf_batch_step)
  * integrateRiccatiStateFast with the frame's mean IMU sample and the k observer steps, with the reference's default (eqf_batch_step_accurate) one
- * integrateRiccatiStateAccurate per sample between the observer steps -, removeOldLandmarks (settings.removeLostLandmarks), removeOutliers, addNewLandmarks (median or fixed depth),
+ * integrateRiccatiStateAccurate per sample between the observer steps, with the discrete state matrix (eqf_batch_step_discrete) one integrateRiccatiStateDiscrete
+ * per sample in the same places -, removeOldLandmarks (settings.removeLostLandmarks), removeOutliers, addNewLandmarks (median or fixed depth),
  * performVisionUpdate and removeInvalidLandmarks. Its state is the one eqf_hip.h's context holds (xi0, X, Sigma; same flat layouts, eqvio_types.h).
  * The sensor-level work (the 46 doubles of xi0 / X, the terms of A and B, the observer steps' sensor part, the sensor lift) is done on the host, the
- * rest by the slot's workgroup. Only the discrete state matrix (useDiscreteStateMatrix) and the Normal chart are not available; settings with
- * fastRiccati == 0 are still refused (EQF_E_UNSUPPORTED at creation): the accurate mode is a call of its own, not a setting.
+ * rest by the slot's workgroup. Only the Normal chart is not available. Settings with fastRiccati == 0 are still refused (EQF_E_UNSUPPORTED at creation), and the
+ * useDiscreteStateMatrix field of eqvio_settings is not read: the accurate and the discrete mode are calls of their own, not settings.
  *
  * Return codes are eqf_hip.h's. Argument and settings checks come BEFORE the device is looked at: a call with bad arguments returns EQF_E_BAD_ARG /
  * EQF_E_UNSUPPORTED on a machine without a GPU as well; with valid arguments and no gfx950 device, eqf_batch_create returns EQF_E_NO_DEVICE.
@@ -109,8 +110,18 @@ int eqf_batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* 
  * remaining phases). The settings of a batch keep saying fastRiccati = 1: that field describes eqf_batch_step. Any slot may be advanced by either call in any
  * frame. */
 int eqf_batch_step_accurate(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status);
-/* Two counters of the slot's last eqf_batch_step_accurate, written by its kernel into the result record: how many samples had dt > 0, and the largest number
- * of squarings an exponential of the step took (0: |dt [A B]|_inf <= 0.25 for every sample). After eqf_batch_step, or a copy into the slot
+/* eqf_batch_step_accurate with the discrete state matrix, fastRiccati == false and useDiscreteStateMatrix == true (integrateUpToTime, src/VIOFilter.cpp:165-170):
+ * for sample i = 0 .. k-1, when dt_i > 0, Sigma <- A_d Sigma A_d^T + dt_i (B Q B^T + P) (integrateRiccatiStateDiscrete, VIO_eqf.cpp:93-103) with
+ * A_d = stateMatrixADiscrete(X, xi0, imu_i, dt_i) (EqFMatrices.cpp:24-41: the central difference, h = cbrt(eps), of a0Discrete) and B = inputMatrixB, both at the X
+ * that samples 0 .. i-1 have produced, Q and P the slot's own gains; then the observer step with sample i. A sample with dt_i == 0 skips its Riccati step and still
+ * runs its observer step. A_d is formed on the device, its sensor part included (k_batch_discrete). Everything else is eqf_batch_step_accurate's: the frame struct,
+ * the screening, the status codes, the result flags, the innovation statistics and the totals; imu13_mean and dt_total are not read and may be null / 0; a dt_k
+ * that is negative or not finite gives EQF_E_BAD_ARG, the slot untouched bit for bit; one packet to the device, one copy back and one synchronisation, two
+ * launches between them. Neither fastRiccati nor useDiscreteStateMatrix of the batch's settings says anything about this call: the mode is the call. Any slot may
+ * be advanced by any of the three calls in any frame. eqf_batch_last_riccati then reports the samples with dt > 0, and 0 squarings. */
+int eqf_batch_step_discrete(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status);
+/* Two counters of the slot's last eqf_batch_step_accurate / _discrete, written by its kernel into the result record: how many samples had dt > 0, and the largest
+ * number of squarings an exponential of the step took (0: |dt [A B]|_inf <= 0.25 for every sample; always 0 after eqf_batch_step_discrete). After eqf_batch_step, or a copy into the slot
  * (eqf_batch_copy_slots, eqf_batch_load_ctx), both read 0. Null output pointers are skipped; a null batch or a bad slot gives EQF_E_BAD_ARG; no device is looked at. */
 int eqf_batch_last_riccati(const eqf_batch* b, int slot, int* samples, int* max_squarings);
 /* flags (EQF_BATCH_*) of the slot's last step, and the depth its new landmarks got */

@@ -1,4 +1,4 @@
-/* eqvio_batch.h — C-ABI of the filter-level batch (eqvio_amd/host/VIOFilterBatch.hpp): B reference VIOFilters (fast or, per slot, accurate Riccati; <= 64
+/* eqvio_batch.h — C-ABI of the filter-level batch (eqvio_amd/host/VIOFilterBatch.hpp): B reference VIOFilters (fast or, per slot, accurate Riccati with the continuous or the discrete state matrix; <= 64
  * landmarks each) whose frames go to the device together, one device call per step and mode (include/eqf_batch.h). Each slot keeps what the reference's VIOFilter keeps on the host:
  * its IMU buffer, current time, initialised flag and landmark ids.
  *
@@ -42,6 +42,18 @@ int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings
 enum { EQVIO_BATCH_RICCATI_FAST = 0, EQVIO_BATCH_RICCATI_ACCURATE = 1 };
 int eqvio_batch_set_slot_riccati(eqvio_batch* b, int slot, int mode); /* slot < 0: every slot */
 int eqvio_batch_get_slot_riccati(const eqvio_batch* b, int slot);     /* mode, or EQF_E_BAD_ARG */
+/* The state matrix an ACCURATE slot's Riccati steps use - the reference picks its propagation with two booleans, fastRiccati and useDiscreteStateMatrix
+ * (integrateUpToTime, src/VIOFilter.cpp:160-178), and this is the second one: EQVIO_BATCH_STATE_MATRIX_CONTINUOUS - eqf_batch_step_accurate; every slot starts
+ * with it - or EQVIO_BATCH_STATE_MATRIX_DISCRETE - eqf_batch_step_discrete, one integrateRiccatiStateDiscrete per IMU sample (A_d = stateMatrixADiscrete, the
+ * mode the reference's own statistical test runs). The choice matters only while the slot's Riccati mode is EQVIO_BATCH_RICCATI_ACCURATE, as in
+ * integrateUpToTime; a fast slot keeps it and ignores it. Like the Riccati mode it is not a setting: the useDiscreteStateMatrix field of eqvio_settings is not read
+ * by the batch. A step sends its listed slots to the calls of their modes in the order fast, accurate, discrete: one device call when the slots agree, up to
+ * three when they do not. set: slot < 0 means every slot; a kind outside the enum, a slot index past the last slot or a null batch gives EQF_E_BAD_ARG, nothing
+ * changed, no device looked at. get returns the kind, or EQF_E_BAD_ARG. Kept like the Riccati mode: eqvio_batch_copy_slots and _load_filter leave the
+ * destination's choice alone, _store_filter leaves the filter's settings alone. */
+enum { EQVIO_BATCH_STATE_MATRIX_CONTINUOUS = 0, EQVIO_BATCH_STATE_MATRIX_DISCRETE = 1 };
+int eqvio_batch_set_slot_state_matrix(eqvio_batch* b, int slot, int kind); /* slot < 0: every slot */
+int eqvio_batch_get_slot_state_matrix(const eqvio_batch* b, int slot);     /* kind, or EQF_E_BAD_ARG */
 /* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56), with the slot's settings */
 int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time);
 void eqvio_batch_destroy(eqvio_batch* b);
