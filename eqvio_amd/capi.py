@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.environ.get("EQVIO_AMD_LIB_DIR") or os.path.join(_HERE, "lib")  # the override: same-box A/B of two builds (scripts/ab_builds.sh)
 
 COORD_EUCLIDEAN, COORD_INVDEPTH, COORD_NORMAL = 0, 1, 2
-OPT_RICCATI_DENSE, OPT_CHECK_FINITE, OPT_SIGMA_FP32, OPT_DOORBELL, OPT_SPECULATIVE, OPT_EARLY_LIFT, OPT_TRACE, OPT_FUSED_ASSEMBLY, OPT_LOOKAHEAD, OPT_LA_TIMEOUT_US, OPT_Z_IN_LOOKAHEAD, OPT_LA_SPLIT_ROWS, OPT_MEASURE_IN_PROPAGATE, OPT_LIFT_WITH_SYRK, OPT_LA_HOME, OPT_TILES_PER_WORKGROUP, OPT_GATHER_IN_PROPAGATE, OPT_HOLD_NEW_LANDMARKS, OPT_SELECT_ONE_WORKGROUP, OPT_LIVE_COLUMNS_FIRST, OPT_EARLY_DOORBELL, OPT_QUIET_DOOR_WAIT, OPT_TIMING = 1, 2, 3, 6, 7, 8, 9, 11, 12, 15, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 29, 100
+OPT_RICCATI_DENSE, OPT_CHECK_FINITE, OPT_SIGMA_FP32, OPT_DOORBELL, OPT_SPECULATIVE, OPT_EARLY_LIFT, OPT_TRACE, OPT_FUSED_ASSEMBLY, OPT_LOOKAHEAD, OPT_LA_TIMEOUT_US, OPT_Z_IN_LOOKAHEAD, OPT_LA_SPLIT_ROWS, OPT_MEASURE_IN_PROPAGATE, OPT_LIFT_WITH_SYRK, OPT_LA_HOME, OPT_TILES_PER_WORKGROUP, OPT_GATHER_IN_PROPAGATE, OPT_HOLD_NEW_LANDMARKS, OPT_SELECT_ONE_WORKGROUP, OPT_LIVE_COLUMNS_FIRST, OPT_EARLY_DOORBELL, OPT_QUIET_DOOR_WAIT, OPT_INNOVATION_STATS, OPT_TIMING = 1, 2, 3, 6, 7, 8, 9, 11, 12, 15, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 29, 30, 100
 
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)
@@ -236,9 +236,12 @@ def load_eqf_lib():
         "eqf_mfma_f64_peak": (C.c_int, [vp, c_double_p]),
         "eqf_mfma_f64_peak_clock": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "eqf_last_kernel_times": (C.c_int, [vp, c_int_p, P(C.c_float), C.c_int]),
+        "eqf_last_innovation": (C.c_int, [vp, c_int_p, c_double_p, c_double_p]),
+        "eqf_innovation_totals": (C.c_int, [vp, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
+        "eqf_reset_innovation_totals": (C.c_int, [vp]),
     }
     for name, (res, args) in protos.items():
-        if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_lookahead_home", "eqf_device_to_itself", "eqf_early_doorbell_stats", "eqf_update_unsettled", "eqf_remove_invalid_at_update", "eqf_gather_stats", "eqf_remove_unmeasured_landmarks", "eqf_find_unknown_ids", "eqf_add_landmarks_held", "eqf_hold_supported", "eqf_hold_stats", "eqf_same_as_mapped", "eqf_live_columns_stats", "eqf_own_hardware_queue") and not hasattr(lib, name):
+        if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_lookahead_home", "eqf_device_to_itself", "eqf_early_doorbell_stats", "eqf_update_unsettled", "eqf_remove_invalid_at_update", "eqf_gather_stats", "eqf_remove_unmeasured_landmarks", "eqf_find_unknown_ids", "eqf_add_landmarks_held", "eqf_hold_supported", "eqf_hold_stats", "eqf_same_as_mapped", "eqf_live_columns_stats", "eqf_own_hardware_queue", "eqf_last_innovation", "eqf_innovation_totals", "eqf_reset_innovation_totals") and not hasattr(lib, name):
             continue  # same-box A/B against the libraries of an older commit (scripts/ab_builds.sh): entry points that commit did not have yet
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
@@ -469,6 +472,21 @@ class EqfCore:
         self._chk0(self.lib.eqf_mfma_f64_peak(self.h, C.byref(t)))
         return t.value
 
+    def last_innovation(self):
+        """(dof, NIS, log det S) of the last vision update (OPT_INNOVATION_STATS; eqf_last_innovation)"""
+        dof, nis, logdet = C.c_int(), C.c_double(), C.c_double()
+        self._chk0(self.lib.eqf_last_innovation(self.h, C.byref(dof), C.byref(nis), C.byref(logdet)))
+        return dof.value, nis.value, logdet.value
+
+    def innovation_totals(self):
+        """(updates, sum dof, sum NIS, sum log det S) over the applied updates since the last reset"""
+        upd, dof, nis, logdet = C.c_long(), C.c_long(), C.c_double(), C.c_double()
+        self._chk0(self.lib.eqf_innovation_totals(self.h, C.byref(upd), C.byref(dof), C.byref(nis), C.byref(logdet)))
+        return upd.value, dof.value, nis.value, logdet.value
+
+    def reset_innovation_totals(self):
+        self._chk0(self.lib.eqf_reset_innovation_totals(self.h))
+
     def kernel_times(self, cap=4096):
         which = np.zeros(cap, np.int32)
         us = np.zeros(cap, np.float32)
@@ -513,8 +531,14 @@ def load_filter_lib():
         "eqvio_filter_last_timing": (C.c_int, [vp, c_double_p, c_double_p, c_double_p]),
         "eqvio_filter_run_frames": (C.c_int, [vp, P(Camera), C.c_int, c_int_p, c_double_p, c_double_p, c_int_p, c_int_p, c_double_p]),
         "eqvio_filter_run_prepared": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+        "eqvio_filter_set_innovation_stats": (C.c_int, [vp, C.c_int]),
+        "eqvio_filter_last_innovation": (C.c_int, [vp, c_int_p, c_double_p, c_double_p]),
+        "eqvio_filter_innovation_totals": (C.c_int, [vp, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
+        "eqvio_filter_reset_innovation_totals": (C.c_int, [vp]),
     }
     for name, (res, args) in protos.items():
+        if os.environ.get("EQVIO_AMD_LIB_DIR") and "innovation" in name and not hasattr(lib, name):
+            continue  # same-box A/B against the libraries of an older commit, as in load_eqf_lib
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -641,6 +665,23 @@ class VIOFilter:
 
     def synchronize(self):
         load_eqf_lib().eqf_synchronize(self.core_handle())
+
+    def set_innovation_stats(self, on=True):
+        """OPT_INNOVATION_STATS of the device context: every vision update from here on reports dof, NIS and log det S"""
+        self._chk(self.lib.eqvio_filter_set_innovation_stats(self.h, int(bool(on))))
+
+    def last_innovation(self):
+        dof, nis, logdet = C.c_int(), C.c_double(), C.c_double()
+        self._chk(self.lib.eqvio_filter_last_innovation(self.h, C.byref(dof), C.byref(nis), C.byref(logdet)))
+        return dof.value, nis.value, logdet.value
+
+    def innovation_totals(self):
+        upd, dof, nis, logdet = C.c_long(), C.c_long(), C.c_double(), C.c_double()
+        self._chk(self.lib.eqvio_filter_innovation_totals(self.h, C.byref(upd), C.byref(dof), C.byref(nis), C.byref(logdet)))
+        return upd.value, dof.value, nis.value, logdet.value
+
+    def reset_innovation_totals(self):
+        self._chk(self.lib.eqvio_filter_reset_innovation_totals(self.h))
 
     def last_timing(self):
         a, b, c = C.c_double(), C.c_double(), C.c_double()

@@ -3,6 +3,7 @@
 #include "eqf_hip.h"
 #include "eqf_kernels.hpp"
 #include "eqf_lookahead.hpp"
+#include "eqf_innovation.hpp"
 #include "eqf_batch.hpp"
 #include "eqf_batch.h"
 #include "host_prof.hpp"
@@ -10,6 +11,8 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <deque>
+#include <limits>
 #include <mutex>
 #include <optional>
 #include <cstdio>
@@ -44,10 +47,11 @@ enum KName {
     KN_DENSE_GEMM,
     KN_MISC,
     KN_CHOL_LOOKAHEAD,
+    KN_INNOVATION,
     KN_COUNT
 };
 const char* kNames[KN_COUNT] = {"k_assemble_AB", "k_observer",    "k_propagate_G", "k_propagate_main", "k_measure", "k_outlier_stats", "k_build_Z",
-                                "k_chol_step",   "k_chol_first", "k_gamma",       "k_syrk_sub",       "k_lift",    "k_gemm_nt",       "misc", "k_chol_lookahead"};
+                                "k_chol_step",   "k_chol_first", "k_gamma",       "k_syrk_sub",       "k_lift",    "k_gemm_nt",       "misc", "k_chol_lookahead", "k_innovation_stats"};
 
 int roundup(int x, int m) { return (x + m - 1) / m * m; }
 int pick_ld(int x) {
@@ -134,6 +138,8 @@ struct TailPlan {
     bool syrk_gamma = false;        // the covariance-update kernel produces Gamma = W z as a by-product of its diagonal tiles
     int early_seq = 0;              // the doorbell sequence the look-ahead kernel rings itself (0: this tail rings no early doorbell)
     bool sig32 = false, check = false; // Sigma stored as float; finite check behind the tail
+    bool innov = false;             // EQF_OPT_INNOVATION_STATS: k_innovation_stats behind the tail, and the launch chain keeps one inverse factor tile per panel (d_Linv_all)
+    bool masked = false;            // ... behind the device-side outlier decision: the columns of the discarded measurements are left out (h_sel through the index map)
 };
 
 // The members of a context are grouped by what a change of capacity (grow_capacity builds a second context and exchanges the two) does with them:
@@ -162,6 +168,7 @@ struct CtxOptions {
     int opt_live_first = 1;                  // EQF_OPT_LIVE_COLUMNS_FIRST
     int opt_measure_prop = 1;                // EQF_OPT_MEASURE_IN_PROPAGATE
     int opt_lift_syrk = 1;                   // EQF_OPT_LIFT_WITH_SYRK
+    int opt_innov = 0;                       // EQF_OPT_INNOVATION_STATS
     long long la_timeout_ticks = LA_TIMEOUT_TICKS; // EQF_OPT_LA_TIMEOUT_US: bound of every device-side wait of the look-ahead kernel (100 MHz ticks)
 };
 // What the *_stats getters, eqf_lookahead_home, eqf_nees_lu_fallbacks and eqf_host_wait_stats report, and the back-offs that count frames: they belong to the
@@ -185,6 +192,17 @@ struct CtxCounters {
     // host-side wait statistics (eqf_host_wait_stats): doorbell waits and the time spent spinning in them
     long wait_calls = 0, launch_calls = 0;
     double wait_seconds = 0.0, launch_seconds = 0.0;
+    // EQF_OPT_INNOVATION_STATS: host sums over the applied updates, in update order (eqf_innovation_totals), and the last result (eqf_last_innovation)
+    long innov_updates = 0, innov_dof = 0;
+    double innov_nis = 0.0, innov_logdet = 0.0;
+    int innov_last_kind = 0;                 // INNOV_NONE: no update yet; INNOV_VALUE; INNOV_FAILED: m, NaN, NaN; INNOV_OFF: the last applied update ran without the option
+    int innov_last_dof = 0;
+    double innov_last_nis = 0.0, innov_last_logdet = 0.0;
+};
+enum { INNOV_NONE = 0, INNOV_VALUE, INNOV_FAILED, INNOV_OFF };
+// an update whose innovation statistics have not been taken into the counters yet (innov_harvest): in update order
+struct InnovPending {
+    int kind, slot, seq, m;
 };
 // Every device and pinned allocation of a context, recorded by alloc_device / alloc_pinned (below HIPCHK) and released by eqf_destroy. Pointer VALUES, so that
 // the lists exchange with their context in std::swap(*c, *t).
@@ -260,6 +278,15 @@ struct eqf_ctx : CtxOptions, CtxCounters {
     // flight across grow_capacity, eqf_destroy or the batch bridge's entry into a context - every one of them passes enter() (or sync_ctx), which settles first - so none
     // of them mentions it.
     TailPlan tail{};
+    // EQF_OPT_INNOVATION_STATS (both allocated by the first tail planned with the option on): one inverse factor tile per panel for the launch chain (the look-ahead kernel
+    // keeps its own in d_pub), and a pinned ring of result slots - k_innovation_stats writes one per launch, the host takes them in update order when somebody asks
+    // (innov_harvest: the update call itself never waits for that kernel). grow_capacity harvests before it exchanges the buffers.
+    double* d_Linv_all = nullptr;
+    InnovSlot* h_innov = nullptr;
+    static constexpr int kInnovRing = 8;
+    int innov_pos = 0, innov_seq = 0;
+    int innov_cur_slot = 0, innov_cur_seq = 0; // the slot and number of the tail in flight
+    std::deque<InnovPending> innov_pending;
     int cu_count = 256;                      // compute units of the device: the look-ahead kernel needs all its workgroups resident at once
     std::vector<char> rm_drop;               // eqf_remove_landmarks' scratch
     std::vector<int> rm_ids, rm_map;
@@ -850,6 +877,8 @@ const char* eqf_kernel_name(int which) { return (which >= 0 && which < KN_COUNT)
 
 static int create_buffers(eqf_ctx* c, int max_landmarks, bool own_queue);
 static int grow_capacity(eqf_ctx* c, int new_cap);
+static int innov_harvest(eqf_ctx* c, bool wait);
+static void innov_note(eqf_ctx* c, int kind);
 static int flush_reshape(eqf_ctx* c);
 static int round_sigma(eqf_ctx* c, const int* spec = nullptr, int spec_seq = 0);
 // first statement of every entry point that uses the device state: select the device, apply the recorded landmark bookkeeping
@@ -1166,6 +1195,7 @@ static const OptRow kOptions[] = {
     {EQF_OPT_QUIET_DOOR_WAIT, &CtxOptions::opt_quiet_wait, OPT_BOOL, 0, 0},
     {EQF_OPT_MEASURE_IN_PROPAGATE, &CtxOptions::opt_measure_prop, OPT_BOOL, 0, 0},
     {EQF_OPT_LIFT_WITH_SYRK, &CtxOptions::opt_lift_syrk, OPT_BOOL, 0, 0},
+    {EQF_OPT_INNOVATION_STATS, &CtxOptions::opt_innov, OPT_BOOL, 0, 0},
     {EQF_OPT_TRACE, nullptr, OPT_PLAIN, 0, 0},
     {100, &CtxOptions::opt_timing, OPT_PLAIN, 0, 0},
     {102, &CtxOptions::opt_la_watch_ahead, OPT_BOOL, 0, 0}, // (debug knob, not in the header: same-process A/B of LaArgs::watch_ahead)
@@ -1448,6 +1478,9 @@ int eqf_state_estimate(eqf_ctx* c, double* sensor, int* ids, double* p, int cap)
 // the host (rare: capacities double), and exchange the two. Handles held by the caller stay valid (the eqf_ctx object is the same).
 static int grow_capacity(eqf_ctx* c, int new_cap) {
     int rc = keep_last_gamma(c);
+    if (rc)
+        return rc;
+    rc = innov_harvest(c, true); // the result slots stay with the old buffers: what they hold goes into the counters (carried over below) first
     if (rc)
         return rc;
     const int N = c->N, n = c->n();
@@ -2478,8 +2511,9 @@ int eqf_propagate_fast(eqf_ctx* c, const double* imu13_mean, double dt_total, co
 
 // Blocked right-looking factorisation of Z (rows x m, leading dimension ldz): one launch per 32-column panel
 // (k_chol_step), preceded by the elimination of the first diagonal tile. Rows >= m of W receive Z[rows >= m] L^-T.
+// (linv_all: one tile per panel - step k reads tile k and leaves tile k + 1 - instead of the two tiles of d_Linv in turns; host addressing only)
 static int launch_chain(eqf_ctx* c, int rows, int m, int ldz, double* Z, double* W, bool first_tile_done = false, const int* spec = nullptr, int spec_seq = 0,
-                        double* gpart = nullptr) {
+                        double* gpart = nullptr, double* linv_all = nullptr) {
     constexpr int NB = 32;
     if (!first_tile_done) { // the vision update's k_build_Z eliminates the first tile itself
         KTimer t(c, KN_CHOL_UPDATE);
@@ -2491,8 +2525,8 @@ static int launch_chain(eqf_ctx* c, int rows, int m, int ldz, double* Z, double*
     for (int kb = 0; kb < m; kb += NB, ++step) {
         const int w = std::min(NB, m - kb);
         const int c0 = kb + w;
-        double* Lin = c->d_Linv + 1024 * (step & 1);
-        double* Lout = c->d_Linv + 1024 * ((step + 1) & 1);
+        double* Lin = linv_all ? linv_all + 1024 * (size_t)step : c->d_Linv + 1024 * (step & 1);
+        double* Lout = linv_all ? linv_all + 1024 * (size_t)(step + 1) : c->d_Linv + 1024 * ((step + 1) & 1);
         const int gx = blocks(rows - c0, 32);
         const int nyS = c0 < m ? blocks(m - c0, 32) : 1;
         // gpart: the last launch (c0 == m) also produces Gamma = W z as GAMMA_G + 1 partial vectors (extra grid rows + its own panel)
@@ -2532,6 +2566,8 @@ static int la_workgroups(const eqf_ctx* c, int rows, int m) {
     const int base = (2 * blocks(m, 32) - 1) + blocks(rows - m, 16);
     return base + 1 + la_split_extra(c, blocks(m, 32), base);
 }
+// where k_build_Z leaves L_0^-1 and the launch chain its tiles: the two tiles of d_Linv, or (EQF_OPT_INNOVATION_STATS) the per-panel array
+static double* linv_base(const eqf_ctx* c, const TailPlan& p) { return p.innov ? c->d_Linv_all : c->d_Linv; }
 // (p: what plan_tail decided - the self-test passes a plan of sizes only)
 static int launch_lookahead(eqf_ctx* c, const TailPlan& p) {
     const int zb = p.zb;
@@ -2571,7 +2607,7 @@ static int launch_lookahead(eqf_ctx* c, const TailPlan& p) {
     }
     a.timeout_ticks = c->la_timeout_ticks;
     a.Z = c->d_Z, a.W = c->d_W, a.gamma = c->d_gamma, a.flags = c->d_flags;
-    a.Linv0 = c->d_Linv; // k_build_Z leaves L_0^-1 where step 0 of the launch chain reads it
+    a.Linv0 = linv_base(c, p); // k_build_Z leaves L_0^-1 where step 0 of the launch chain reads it
     a.pub = c->d_pub, a.pubf = c->d_pubf, a.puby = c->d_puby;
     a.spec = p.spec, a.spec_seq = p.spec_seq, a.live_cols = p.live_cols;
     if (a.live_cols)
@@ -2579,7 +2615,7 @@ static int launch_lookahead(eqf_ctx* c, const TailPlan& p) {
     a.tr_steps = trace_slot(c, TR_STEP0), a.dbg = c->d_trace ? c->d_ladbg : nullptr;
     if (zb) { // EQF_OPT_Z_IN_LOOKAHEAD: the half-rows build their rows of Z themselves
         a.zb_sig = (const double*)c->sigma(), a.zb_ld = c->ld, a.zb_M = p.m / 2, a.zb_Mcap = c->Ncap, a.zb_var = p.meas_var;
-        a.zb_C = c->d_C, a.zb_ytil = c->d_ytil, a.zb_lmidx = c->d_lmidx, a.zb_linv0 = c->d_Linv;
+        a.zb_C = c->d_C, a.zb_ytil = c->d_ytil, a.zb_lmidx = c->d_lmidx, a.zb_linv0 = linv_base(c, p);
         // (the pinned packet's mapping is the one this update was mapped with - map_measurement ran in this call or, for a staged measurement, in stage_prepare)
         a.zb_ident = (zb != 2 && p.ident) ? 1 : 0;
         a.tr_zb = trace_slot(c, TR_BUILD_Z);
@@ -2913,6 +2949,7 @@ struct TailCall {
     const MeasFuse* fuse = nullptr; // measurement fusion (the speculative tail), or none
     bool live_first = false;        // k_stats_select in front of this tail has put the measurements of the landmarks that stay first
     bool takes_early = false;       // the caller can return on the look-ahead kernel's own doorbell (door_wait(.., &early))
+    bool masked = false;            // the device-side outlier decision in front of this tail has masked the discarded landmarks' measurements (h_sel says which)
 };
 // Every decision of a tail, from the context's options and state and the call, before the tail's first launch. chain_only: the look-ahead kernel's compute units did
 // not come free (la_book - which waits, and is therefore the caller's: queue_tail).
@@ -2925,6 +2962,7 @@ static void plan_tail(const eqf_ctx* c, TailPlan& p, const TailCall& call, bool 
     if (fuse) // with spec != nullptr every kernel of the tail first compares *spec with spec_seq and returns at once if they match (cancelled tail)
         p.mf = *fuse, p.spec = fuse->spec_w, p.spec_seq = fuse->spec_seq;
     p.sig32 = c->sig32, p.check = c->opt_check != 0;
+    p.innov = c->opt_innov != 0 && c->d_Linv_all && c->h_innov, p.masked = call.masked; // (the buffers: queue_tail's, in front of this plan)
     const int NJ = blocks(p.m, 32);
     // "measurement j is landmark j" lets the Z-building prologue skip the index map: true only if the mapping in the pinned packet is the one of THESE ids
     // (k_stats_select in front of this tail puts the measurements of the landmarks that stay first: the index map is not the identity)
@@ -2986,7 +3024,7 @@ static int launch_build_Z(eqf_ctx* c, const TailPlan& p) {
     const bool fused = p.mf.enabled != 0;
     auto launch = [&](auto kern, auto* sig) {
         hipLaunchKernelGGL(kern, dim3(blocks(p.n + p.M + 1, 256), blocks(p.M, BZ_JB) + 1 + (fused ? 1 : 0)), dim3(256), 0, c->stream, p.n, p.M, c->Ncap, c->ld, c->ldz, p.meas_var, c->d_lmidx, sig,
-                           c->d_C, c->d_ytil, c->d_Z, c->d_Linv, c->d_flags, fused ? (const int*)nullptr : p.spec, p.spec_seq, p.mf, trace_slot(c, TR_BUILD_Z));
+                           c->d_C, c->d_ytil, c->d_Z, linv_base(c, p), c->d_flags, fused ? (const int*)nullptr : p.spec, p.spec_seq, p.mf, trace_slot(c, TR_BUILD_Z));
     };
     if (p.in_prop) // the propagation kernel has evaluated this measurement's output blocks: nobody evaluates them again
         launch(k_build_Z<double, true, true>, (const double*)c->sigma());
@@ -2998,6 +3036,80 @@ static int launch_build_Z(eqf_ctx* c, const TailPlan& p) {
         launch(k_build_Z<double, true>, (const double*)c->sigma());
     else
         launch(k_build_Z<double, false>, (const double*)c->sigma());
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// EQF_OPT_INNOVATION_STATS. The statistics of an update are three numbers in a pinned slot that k_innovation_stats fills BEHIND the tail; nobody waits for them in the
+// update call. An applied (or failed) update is noted in update order (innov_note, from finish_update / finish_update_early: a cancelled tail notes nothing, a retry's
+// launch has replaced the stalled one's slot by then); innov_harvest takes the noted updates into the counters - the last result and the totals - as far as their slots
+// have arrived, or all of them (wait: the getters, grow_capacity).
+static void innov_take(eqf_ctx* c, const InnovPending& e) {
+    c->innov_last_kind = e.kind;
+    if (e.kind == INNOV_FAILED) {
+        c->innov_last_dof = e.m;
+        c->innov_last_nis = c->innov_last_logdet = std::numeric_limits<double>::quiet_NaN();
+    } else if (e.kind == INNOV_VALUE) {
+        const InnovSlot& s = c->h_innov[e.slot];
+        c->innov_last_dof = s.dof, c->innov_last_nis = s.nis, c->innov_last_logdet = s.logdet;
+        ++c->innov_updates;
+        c->innov_dof += s.dof, c->innov_nis += s.nis, c->innov_logdet += s.logdet;
+    }
+}
+static int innov_harvest(eqf_ctx* c, bool wait) {
+    while (!c->innov_pending.empty()) {
+        const InnovPending e = c->innov_pending.front();
+        if (e.kind == INNOV_VALUE) {
+            const int* word = &c->h_innov[e.slot].seq;
+            long spins_after_done = 0;
+            for (long it = 1; __atomic_load_n(word, __ATOMIC_ACQUIRE) != e.seq; ++it) {
+                if (!wait)
+                    return 0;
+                if (spins_after_done || (it & 0xfff) == 0) { // (as door_wait: a kernel fault is reported, and a slot that never arrives fails loudly)
+                    const hipError_t q = hipStreamQuery(c->stream);
+                    if (q != hipSuccess && q != hipErrorNotReady)
+                        return (int)q;
+                    if (q == hipSuccess && ++spins_after_done > 1000000) {
+                        std::fprintf(stderr, "[eqf_hip] innovation statistics of an applied update never arrived (slot %d, expected %d)\n", e.slot, e.seq);
+                        c->innov_pending.clear();
+                        return (int)hipErrorUnknown;
+                    }
+                }
+            }
+        }
+        innov_take(c, e);
+        c->innov_pending.pop_front();
+    }
+    return 0;
+}
+static void innov_note(eqf_ctx* c, int kind) {
+    const InnovPending e{kind, c->innov_cur_slot, c->innov_cur_seq, c->tail.m};
+    if (kind != INNOV_VALUE && c->innov_pending.empty())
+        innov_take(c, e); // (nothing of the device involved - every update of a context that runs without the option ends here)
+    else
+        c->innov_pending.push_back(e);
+}
+static int launch_innovation(eqf_ctx* c, const TailPlan& p, int stall_seq) {
+    EQFCHK(innov_harvest(c, false));
+    const int slot = c->innov_pos;
+    c->innov_pos = (c->innov_pos + 1) % eqf_ctx::kInnovRing;
+    for (const InnovPending& e : c->innov_pending)
+        if (e.kind == INNOV_VALUE && e.slot == slot) { // (not reached: an update call returns behind the factorisation of its tail, which runs behind the previous tail's statistics)
+            EQFCHK(innov_harvest(c, true));
+            break;
+        }
+    if (++c->innov_seq <= 0) // positive: 0 is the initial state of every slot
+        c->innov_seq = 1;
+    c->innov_cur_slot = slot, c->innov_cur_seq = c->innov_seq;
+    InnovArgs a{};
+    a.m = p.m, a.rows = p.rows, a.ldz = c->ldz;
+    a.W = c->d_W;
+    a.tiles = p.la ? c->d_pub : c->d_Linv_all; // tile p of either: L_p^-1 (la_i_linv(a, p) == p)
+    a.lmidx = c->d_lmidx, a.removed = p.masked ? c->h_sel : nullptr, a.nlm = c->N;
+    a.spec = p.spec, a.spec_seq = p.spec_seq;
+    a.flags = c->d_flags, a.stall_seq = stall_seq;
+    a.out = c->h_innov + slot, a.seq = c->innov_seq;
+    KTimer t(c, KN_INNOVATION);
+    launch_innovation_kernel(a, c->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -3014,7 +3126,7 @@ static int launch_tail(eqf_ctx* c, const TailPlan& p) {
         ++c->la_launches;
         EQFCHK(launch_lookahead(c, p));
     } else
-        EQFCHK(launch_chain(c, p.rows, p.m, c->ldz, c->d_Z, c->d_W, true, p.spec, p.spec_seq, p.lift_before_syrk ? c->d_gpart : nullptr));
+        EQFCHK(launch_chain(c, p.rows, p.m, c->ldz, c->d_Z, c->d_W, true, p.spec, p.spec_seq, p.lift_before_syrk ? c->d_gpart : nullptr, p.innov ? c->d_Linv_all : nullptr));
     const int stall_seq = p.la ? c->la_seq : -1; // the stall word the kernels behind the factorisation compare (sequence valued: eqf_lookahead.hpp)
     const double* gpart = p.la ? nullptr : c->d_gpart; // (the look-ahead kernel leaves Gamma complete, the chain as partial vectors)
     const int nt = blocks(p.n, 32);
@@ -3047,6 +3159,8 @@ static int launch_tail(eqf_ctx* c, const TailPlan& p) {
         EQFCHK(launch_lift(c, p, nullptr, stall_seq));
     if (p.check)
         EQFCHK(launch_check_finite(c));
+    if (p.innov)
+        EQFCHK(launch_innovation(c, p, stall_seq));
     booking.keep = p.la; // a look-ahead launch is in flight: released by the doorbell wait (door_wait), sync_ctx or eqf_destroy
     return 0;
 }
@@ -3060,6 +3174,10 @@ static int queue_tail(eqf_ctx* c, const TailCall& call) {
         chain_only = !la_book(c, la_workgroups(c, 2 * call.M + c->n() + 1, 2 * call.M));
         if (chain_only)
             ++c->la_book_timeouts;
+    }
+    if (c->opt_innov && !c->h_innov) {
+        EQFCHK(alloc_device(c, c->d_Linv_all, 1024 * ((size_t)blocks(c->mcap, 32) + 1)));
+        EQFCHK(alloc_pinned(c, c->h_innov, eqf_ctx::kInnovRing, true));
     }
     plan_tail(c, c->tail, call, chain_only);
     c->me_valid = false; // (the plan has looked at the propagation kernel's output blocks: they are this measurement's or nobody's)
@@ -3110,10 +3228,13 @@ static int finish_update(eqf_ctx* c, int discreteCorr, bool retried = false) {
                          c->h_resflags[1], c->h_resflags[2], c->h_resflags[3], c->la_seq);
         c->est_valid = false, ++c->est_epoch;
         c->meas_valid = false;
+        if (c->tail.innov)
+            innov_note(c, INNOV_FAILED);
         return c->h_resflags[3] ? EQF_E_STALLED : EQF_E_NOT_SPD;
     }
     if (c->tail.la)
         c->la_consecutive_stalls = 0;
+    innov_note(c, c->tail.innov ? INNOV_VALUE : INNOV_OFF);
     c->gamma_stale = true;
     c->n_at_update = n;
     c->est_cache.assign(c->h_res + 3 * (size_t)c->Ncap, c->h_res + 3 * (size_t)c->Ncap + 4 * N);
@@ -3127,6 +3248,7 @@ static int finish_update_early(eqf_ctx* c, int discreteCorr, int seq) {
     c->h_flags[0] = c->h_flags[1] = 0;
     if (c->tail.la)
         c->la_consecutive_stalls = 0;
+    innov_note(c, c->tail.innov ? INNOV_VALUE : INNOV_OFF);
     c->gamma_stale = true;
     c->n_at_update = c->n();
     c->est_valid = false, ++c->est_epoch;
@@ -3334,7 +3456,7 @@ static int stats_select_route(eqf_ctx* c, const StatsCall& s) {
     }
     c->meas_valid = false;
     TailCall call{s.ids, M, s.meas_var, s.discreteCorr, s.use_door, s.seq};
-    call.live_first = live_first, call.takes_early = true;
+    call.live_first = live_first, call.takes_early = true, call.masked = true;
     EQFCHK(queue_tail(c, call));
     bool early;
     EQFCHK(await_tail(c, s, &early));
@@ -3867,6 +3989,51 @@ int eqf_host_wait_stats(eqf_ctx* c, long* calls, double* seconds, int reset) {
         c->wait_calls = c->launch_calls = 0;
         c->wait_seconds = c->launch_seconds = 0.0;
     }
+    return 0;
+}
+
+// See include/eqf_hip.h. The getters take what has been noted since the last call into the counters first; that may wait for the statistics kernel of the last update.
+static int innov_enter(eqf_ctx* c) {
+    if (c->innov_pending.empty() && !c->unsettled)
+        return 0;
+    HIPCHK(hipSetDevice(c->device));
+    EQFCHK(settle_update(c));
+    return innov_harvest(c, true);
+}
+int eqf_last_innovation(eqf_ctx* c, int* dof, double* nis, double* logdet) {
+    if (!c)
+        return EQF_E_BAD_ARG;
+    EQFCHK(innov_enter(c));
+    if (c->innov_last_kind == INNOV_OFF)
+        return EQF_E_UNSUPPORTED;
+    if (dof)
+        *dof = c->innov_last_dof;
+    if (nis)
+        *nis = c->innov_last_nis;
+    if (logdet)
+        *logdet = c->innov_last_logdet;
+    return 0;
+}
+int eqf_innovation_totals(eqf_ctx* c, long* updates, long* dof, double* nis, double* logdet) {
+    if (!c)
+        return EQF_E_BAD_ARG;
+    EQFCHK(innov_enter(c));
+    if (updates)
+        *updates = c->innov_updates;
+    if (dof)
+        *dof = c->innov_dof;
+    if (nis)
+        *nis = c->innov_nis;
+    if (logdet)
+        *logdet = c->innov_logdet;
+    return 0;
+}
+int eqf_reset_innovation_totals(eqf_ctx* c) {
+    if (!c)
+        return EQF_E_BAD_ARG;
+    EQFCHK(innov_enter(c)); // (what is still on its way belongs to the totals that are being cleared)
+    c->innov_updates = c->innov_dof = 0;
+    c->innov_nis = c->innov_logdet = 0.0;
     return 0;
 }
 

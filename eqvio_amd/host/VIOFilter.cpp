@@ -801,6 +801,22 @@ void VIOFilter::processVisionData(const VisionMeasurement& measurement) { // :19
 }
 VIOState VIOFilter::stateEstimate() const { return filterState.stateEstimate(); }
 const VIO_eqf& VIOFilter::viewEqFState() const { return filterState; }
+static void checkInnovation(int rc, const char* what) {
+    if (rc != 0)
+        throw std::runtime_error(std::string("eqf_hip: ") + what + ": " + eqf_error_string(rc));
+}
+void VIOFilter::setInnovationStats(bool on) { checkInnovation(eqf_set_option(filterState.ctx, EQF_OPT_INNOVATION_STATS, on ? 1 : 0), "eqf_set_option"); }
+bool VIOFilter::lastInnovation(int& dof, double& nis, double& logdet) {
+    const int rc = eqf_last_innovation(filterState.ctx, &dof, &nis, &logdet);
+    if (rc == EQF_E_UNSUPPORTED)
+        return false;
+    checkInnovation(rc, "eqf_last_innovation");
+    return true;
+}
+void VIOFilter::innovationTotals(long& updates, long& dof, double& nis, double& logdet) {
+    checkInnovation(eqf_innovation_totals(filterState.ctx, &updates, &dof, &nis, &logdet), "eqf_innovation_totals");
+}
+void VIOFilter::resetInnovationTotals() { checkInnovation(eqf_reset_innovation_totals(filterState.ctx), "eqf_reset_innovation_totals"); }
 double VIOFilter::getTime() const { return filterState.currentTime; }
 VIOState integrateSystemFunction(const VIOState& state, const IMUVelocity& velocity, const double& dt) { // VIOState.cpp:28-68
     VIOState ns;

@@ -277,6 +277,12 @@ class VIOFilter {
     VIOState stateEstimate() const;
     const VIO_eqf& viewEqFState() const;
     VIO_eqf& eqfState() { return filterState; }
+    // Innovation statistics of the vision updates (EQF_OPT_INNOVATION_STATS, include/eqf_hip.h): the filter keeps nothing of its own, the device context counts -
+    // on every route processVisionData takes. lastInnovation: false if the last applied update ran with the option off (nothing written).
+    void setInnovationStats(bool on);
+    bool lastInnovation(int& dof, double& nis, double& logdet);
+    void innovationTotals(long& updates, long& dof, double& nis, double& logdet);
+    void resetInnovationTotals();
     // what the filter keeps on the host beside the EqF state, for moving a whole filter in or out (VIOFilterBatch::loadFilter / storeFilter)
     const std::vector<IMUVelocity>& imuBuffer() const { return velocityBuffer; }
     void adoptHostState(const std::vector<IMUVelocity>& buffer, double time, bool initialised); // after the context was given another filter's EqF state

@@ -201,6 +201,49 @@ int eqvio_filter_last_timing(const eqvio_filter* f, double* a, double* b, double
         *c = f->t_corr;
     return 0;
 }
+int eqvio_filter_set_innovation_stats(eqvio_filter* f, int on) {
+    if (!f)
+        return -1;
+    return guarded(f, [&] { f->filter->setInnovationStats(on != 0); });
+}
+int eqvio_filter_last_innovation(eqvio_filter* f, int* dof, double* nis, double* logdet) {
+    if (!f)
+        return -1;
+    return guarded(f, [&] {
+        int d = 0;
+        double a = 0.0, b = 0.0;
+        if (!f->filter->lastInnovation(d, a, b))
+            throw std::runtime_error("eqvio_filter_last_innovation: the last update ran without innovation statistics (eqvio_filter_set_innovation_stats)");
+        if (dof)
+            *dof = d;
+        if (nis)
+            *nis = a;
+        if (logdet)
+            *logdet = b;
+    });
+}
+int eqvio_filter_innovation_totals(eqvio_filter* f, long* updates, long* dof, double* nis, double* logdet) {
+    if (!f)
+        return -1;
+    return guarded(f, [&] {
+        long u = 0, d = 0;
+        double a = 0.0, b = 0.0;
+        f->filter->innovationTotals(u, d, a, b);
+        if (updates)
+            *updates = u;
+        if (dof)
+            *dof = d;
+        if (nis)
+            *nis = a;
+        if (logdet)
+            *logdet = b;
+    });
+}
+int eqvio_filter_reset_innovation_totals(eqvio_filter* f) {
+    if (!f)
+        return -1;
+    return guarded(f, [&] { f->filter->resetInnovationTotals(); });
+}
 eqvio_frames* eqvio_frames_create(const eqvio_camera* cam, int nframes, const int* imu_counts, const double* imu13_all, const double* stamps, const int* meas_counts,
                                   const int* ids_all, const double* y_all) {
     if (!cam || nframes < 0 || (nframes > 0 && (!imu_counts || !stamps || !meas_counts)))

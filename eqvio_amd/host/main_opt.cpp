@@ -33,6 +33,7 @@ static void usage() {
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
               "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]\n"
+              "                 [--nis]\n"
               "                            [--batchRiccati fast|accurate|discrete[,...]]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
@@ -40,6 +41,8 @@ static void usage() {
               "              (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood. Needs --fastRiccati 1 and at most 64\n"
               "              features per frame; --output, --dumpStates and --sigmaFP32 are refused. With --groundtruth FILE one more line per slot: the position\n"
               "              RMSE of the slot's trajectory against the ground-truth poses nearest in time, after aligning the first poses.\n"
+              "  --nis   a single-filter run (no --batch): switches the device context's innovation statistics on (EQF_OPT_INNOVATION_STATS) and prints, after the\n"
+              "              run, the frames updated, the mean NIS per degree of freedom and the total innovation log-likelihood, in the wording of --batch's slot lines\n"
               "  --record DIR   with --batch B: slot k's IMUState.csv, camera.csv, bias.csv and points.csv (the formats of --output) go to DIR/run_<k>/, one row per\n"
               "              vision measurement per live slot, from one estimates call over the live slots per measurement. With --warmup F slots 1 .. B-1 start\n"
               "              their files at the branch.\n"
@@ -253,7 +256,7 @@ int main(int argc, char** argv) {
     cam->c.width = 752;
     cam->c.height = 480;
     double cameraLag = 0, startTime = -1, stopTime = -1;
-    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false;
+    bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false, nisLine = false;
     int batch = 0;
     std::string warmupText, riccatiText;
     bool haveRiccati = false;
@@ -312,6 +315,7 @@ int main(int argc, char** argv) {
             else if (a == "--batch") batch = std::atoi(val());
             else if (a == "--record") recordDir = val();
             else if (a == "--predictions") predictions = true;
+            else if (a == "--nis") nisLine = true;
             else if (a == "--warmupOnFilter") warmupOnFilter = true;
             else if (a == "--batchRiccati") {
                 riccatiText = val();
@@ -328,6 +332,10 @@ int main(int argc, char** argv) {
                 usage();
                 return a == "--help" ? 0 : 2;
             }
+        }
+        if (nisLine && batch != 0) { // before any file or device is opened
+            std::fprintf(stderr, "eqvio_opt: --nis is the single filter's score; with --batch B every slot's line carries it already\n");
+            return 2;
         }
         if (haveSweep && batch == 0) {
             std::fprintf(stderr, "eqvio_opt: --sweep needs --batch B (one value per slot)\n");
@@ -436,6 +444,8 @@ int main(int argc, char** argv) {
         VIOFilter filter(fs); // main_opt.cpp:150
         if (sigmaFP32) // BASELINE config 5: Sigma stored as float in HBM (include/eqf_hip.h)
             eqf_set_option(filter.eqfState().ctx, EQF_OPT_SIGMA_FP32, 2);
+        if (nisLine)
+            filter.setInnovationStats(true);
         std::unique_ptr<VIOWriter> vioWriter;
         if (!outputDir.empty())
             vioWriter = std::make_unique<VIOWriter>(outputDir);
@@ -501,6 +511,12 @@ int main(int argc, char** argv) {
         const VIOState est = filter.stateEstimate();
         std::printf("final time %.9g  position %.6g %.6g %.6g  landmarks %d  vision updates/s %.1f\n", filter.getTime(), est.sensor.pose.x.x, est.sensor.pose.x.y,
                     est.sensor.pose.x.z, filter.viewEqFState().numLandmarks(), visionDataCounter / elapsed);
+        if (nisLine) { // the wording of --batch B's per-slot line
+            long updates = 0, dof = 0;
+            double nis = 0, logdet = 0;
+            filter.innovationTotals(updates, dof, nis, logdet);
+            std::printf("single filter: frames updated %ld  mean NIS/dof %.9g  log-likelihood %.9g\n", updates, nis / (double)dof, -0.5 * (nis + logdet + (double)dof * std::log(2.0 * M_PI)));
+        }
         if (!gtName.empty()) { // distance to the ground-truth pose nearest in time, after aligning the first poses
             const std::vector<StampedPose> gt = TrackReplayServer::groundtruth(gtName, format);
             if (!gt.empty()) {

@@ -22,7 +22,7 @@ static void usage() {
     std::puts("usage: eqvio_sim [--duration S] [--trajectory wave|square|sine|line] [--numPoints N] [--numWalls W] [--wallDistance D]\n"
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
               "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
-              "                 [--sweep NAME=v0,v1,...] [--innovation] [--record DIR] [--batchRiccati fast|accurate|discrete[,...]]\n"
+              "                 [--sweep NAME=v0,v1,...] [--innovation] [--nis] [--record DIR] [--batchRiccati fast|accurate|discrete[,...]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
               "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
@@ -34,6 +34,8 @@ static void usage() {
               "  --innovation   with --batch B: behind those lines, one line per run with the number of vision updates, the mean normalised innovation\n"
               "              squared per degree of freedom (sum NIS / sum dof: about 1 for a consistent filter) and the total innovation log-likelihood\n"
               "              (eqvio_batch_innovation_totals). Needs no true state, unlike NEES.\n"
+              "  --nis   a single run (no --batch): switches the device context's innovation statistics on (EQF_OPT_INNOVATION_STATS) and prints, after the run,\n"
+              "              the number of vision updates, the mean NIS per degree of freedom and the total innovation log-likelihood, in --innovation's wording\n"
               "  --record DIR   with --batch B: writes every run's consistency record to DIR/run_<k>/ - nees.csv (NEES, PoseNEES, AttitudeNEES),\n"
               "              poseConsistency.csv, cameraConsistency.csv, biasConsistency.csv and landmarkError.csv, in the formats of --output - from one\n"
               "              launch per frame for all runs (eqvio_batch_run_sim_recorded).\n"
@@ -148,7 +150,7 @@ int main(int argc, char** argv) {
     SimSettings sim;
     sim.duration = 20.0;
     VIOFilter::Settings fs;
-    bool fullState = false, quiet = false, sigmaFP32 = false, innovation = false;
+    bool fullState = false, quiet = false, sigmaFP32 = false, innovation = false, nisLine = false;
     double landmarkResetTime = -1.0;
     int batch = 0;
     Sweep sweep;
@@ -185,6 +187,7 @@ int main(int argc, char** argv) {
         else if (a == "--sigmaFP32") sigmaFP32 = true;
         else if (a == "--batch") batch = std::atoi(val());
         else if (a == "--innovation") innovation = true;
+        else if (a == "--nis") nisLine = true;
         else if (a == "--record") recordDir = val();
         else if (a == "--batchRiccati") {
             riccatiText = val();
@@ -202,6 +205,10 @@ int main(int argc, char** argv) {
     }
     if (haveSweep && batch == 0) {
         std::fprintf(stderr, "eqvio_sim: --sweep needs --batch B (one value per slot)\n");
+        return 2;
+    }
+    if (nisLine && batch != 0) { // before any device is opened
+        std::fprintf(stderr, "eqvio_sim: --nis is the single filter's score; with --batch B the filter batch reports it (--innovation)\n");
         return 2;
     }
     if (innovation && batch == 0) {
@@ -274,6 +281,8 @@ int main(int argc, char** argv) {
         VIOFilter filter(simDataServer.getInitialCondition(), fs);
         if (sigmaFP32) // BASELINE config 5: Sigma stored as float in HBM (include/eqf_hip.h)
             eqf_set_option(filter.eqfState().ctx, EQF_OPT_SIGMA_FP32, 2);
+        if (nisLine)
+            filter.setInnovationStats(true);
         int imuDataCounter = 0, visionDataCounter = 0;
         double neesSum = 0, neesMax = 0, posErr = 0;
         int neesFailures = 0;
@@ -337,6 +346,12 @@ int main(int argc, char** argv) {
                   << "Time taken: " << elapsed << " seconds." << std::endl;
         std::printf("mean NEES %.6g  max NEES %.6g  final position error %.6g m  landmarks %d  vision updates/s %.1f\n", neesSum / std::max(visionDataCounter - neesFailures, 1), neesMax,
                     posErr, filter.viewEqFState().numLandmarks(), visionDataCounter / elapsed);
+        if (nisLine) { // the wording of --batch B --innovation's per-run line
+            long updates = 0, dof = 0;
+            double nis = 0, logdet = 0;
+            filter.innovationTotals(updates, dof, nis, logdet);
+            std::printf("innovation: updates %ld  mean NIS/dof %.9g  log-likelihood %.9g\n", updates, nis / (double)dof, -0.5 * (nis + logdet + (double)dof * std::log(2.0 * M_PI)));
+        }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "eqvio_sim: %s\n", e.what());
         return 1;

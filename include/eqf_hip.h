@@ -140,6 +140,10 @@ enum {
     EQF_OPT_LIVE_COLUMNS_FIRST = 26, /* 1 (default): in eqf_stats_select_update up to 16 panels (256 measurements), k_stats_select puts the measurements of the landmarks that stay in
                                   front of the discarded ones and the look-ahead kernel ends with the last panel that holds one of them (the discarded landmarks' columns of Z are
                                   decoupled, W = 0 there): the same Sigma+ up to the rounding of a different column order. 0: measurement order kept, every panel factorised */
+    EQF_OPT_INNOVATION_STATS = 30, /* 0 (default): a frame is exactly the frame without this option. 1: every vision update (eqf_vision_update, eqf_stats_then_update,
+                                  eqf_stats_select_update) is followed by ONE more launch of one workgroup (k_innovation_stats) that forms dof, NIS = yTilde^T S^-1 yTilde and
+                                  log det S from the factorisation that ran (eqf_last_innovation, eqf_innovation_totals); the launch chain then keeps one inverse factor tile
+                                  per panel instead of two in turns. The update call does not wait for that kernel. State, Sigma and every counter are bit-identical to 0. */
     EQF_OPT_SIGMA_FP32 = 3     /* fp32-Sigma path (BASELINE config 5); all arithmetic stays fp64.
                                   2: Sigma is STORED as float in HBM (4 bytes per element; loads widen, stores round). Fast-Riccati
                                      path only: dense / accurate Riccati return EQF_E_UNSUPPORTED.
@@ -366,6 +370,21 @@ int eqf_mfma_f64_peak_clock(eqf_ctx* ctx, double* tflops, double* sclk_ghz);
 
 /* per-kernel timing of the last frame's launches on the context's stream (HIP events); fills up to cap
  * (name index, microseconds) pairs; see eqf_kernel_name. Enabled with eqf_set_option(ctx, 100, 1). */
+/* EQF_OPT_INNOVATION_STATS: the innovation statistics of the single filter's vision updates - eqf_batch_last_innovation's semantics for a context, any landmark count,
+ * any chart. With z = L^-1 yTilde from the factorisation [S ; T ; yTilde^T] -> [L ; W ; z^T] of the update that was applied:
+ *   dof    = 2 x (features that entered the update; the measurements the device-side outlier decision discarded do not count),
+ *   nis    = sum z_j^2 = yTilde^T S^-1 yTilde,    logdet = 2 sum log L_jj = log det S   over those columns,
+ * both sums in a fixed order (the same frame gives the same bits on every run). The values describe the factorisation that ran: with EQF_OPT_SIGMA_FP32 they are those of
+ * the rounded Sigma the update saw, and no parity bound against the fp64 filter is claimed for them.
+ * eqf_last_innovation: after an applied update its values; after a failed one (EQF_E_NOT_SPD, EQF_E_STALLED) m, NaN, NaN; a cancelled speculative tail or a call that
+ * applied nothing (*updated 0 or -1) leaves the last result; 0, 0, 0 on a context that never updated. Returns EQF_E_UNSUPPORTED, writing nothing, if the last applied
+ * update ran with the option off. eqf_innovation_totals: host sums over the applied updates in update order; only eqf_reset_innovation_totals clears them
+ * (eqf_set_state / eqf_set_sigma do not). Null outputs are skipped; a null context is EQF_E_BAD_ARG. Option, totals and last result survive capacity growth.
+ * The three calls may wait for the last update's statistics kernel (and settle an update taken from the early doorbell); the update calls never do.
+ * kernel-time slot of eqf_last_kernel_times: "k_innovation_stats". */
+int eqf_last_innovation(eqf_ctx* ctx, int* dof, double* nis, double* logdet);
+int eqf_innovation_totals(eqf_ctx* ctx, long* updates, long* dof, double* nis, double* logdet);
+int eqf_reset_innovation_totals(eqf_ctx* ctx);
 int eqf_last_kernel_times(eqf_ctx* ctx, int* which, float* usec, int cap);
 /* EQF_OPT_TRACE = 1: device-side timeline of the last 1024 frames, no profiler and no events involved.
  * device_ticks[1024][48] (100 MHz device wall clock; 0 = not stamped): slot 0 k_assemble_AB start, 1 k_propagate_main start, 2 k_build_Z start,

@@ -51,6 +51,13 @@ int eqvio_filter_get_feature_predictions(eqvio_filter* f, const eqvio_camera* ca
 eqf_ctx* eqvio_filter_core(eqvio_filter* f);
 /* loopTimer sections of the last processVisionData (VIOFilter.cpp:196-236), seconds */
 int eqvio_filter_last_timing(const eqvio_filter* f, double* propagation, double* preprocessing, double* correction);
+/* Innovation statistics of the filter's vision updates (EQF_OPT_INNOVATION_STATS of the device context, include/eqf_hip.h: eqf_last_innovation /
+ * eqf_innovation_totals, whose semantics these forward): dof, NIS = yTilde^T S^-1 yTilde and log det S per update, and host sums over the applied updates.
+ * The filter keeps nothing of its own. 0, or -1 (eqvio_filter_last_error: e.g. the last update ran with the statistics off). Null outputs are skipped. */
+int eqvio_filter_set_innovation_stats(eqvio_filter* f, int on);
+int eqvio_filter_last_innovation(eqvio_filter* f, int* dof, double* nis, double* logdet);
+int eqvio_filter_innovation_totals(eqvio_filter* f, long* updates, long* dof, double* nis, double* logdet);
+int eqvio_filter_reset_innovation_totals(eqvio_filter* f);
 
 /* Prepared replay. eqvio_frames_create builds, once, what the reference's tracker / data server hands to the filter: the IMU
  * samples and one VisionMeasurement (a std::map of pixel coordinates) per frame, from arrays concatenated over frames (frame j:

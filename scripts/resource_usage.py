@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register / scratch / LDS use of every kernel instantiation in libeqf_hip.so: compiles eqvio_amd/csrc/eqf_hip.hip with
+"""Register / scratch / LDS use of every kernel instantiation in libeqf_hip.so: compiles the library's translation units (eqvio_amd/csrc/eqf_hip.hip, eqf_innovation.hip) with
 -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints one line per kernel, demangled. `python scripts/resource_usage.py > profiles/rNN_resource_usage.txt`."""
 import os
 import re
@@ -10,13 +10,16 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "eqvio_amd", "csrc")
 with tempfile.TemporaryDirectory() as td:
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I../../include", "-Wno-unused", "-c", "-o", os.path.join(td, "x.o"),
-                        "eqf_hip.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=src, capture_output=True, text=True)
-    if r.returncode:
-        sys.stderr.write(r.stderr[-4000:])
-        sys.exit(r.returncode)
+    remarks = ""
+    for unit in ("eqf_hip.hip", "eqf_innovation.hip"):  # the library's translation units
+        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I../../include", "-Wno-unused", "-c", "-o", os.path.join(td, "x.o"),
+                            unit, "-Rpass-analysis=kernel-resource-usage"], cwd=src, capture_output=True, text=True)
+        if r.returncode:
+            sys.stderr.write(r.stderr[-4000:])
+            sys.exit(r.returncode)
+        remarks += r.stderr
 rows, cur = [], None
-for line in r.stderr.splitlines():
+for line in remarks.splitlines():
     m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]|TotalSGPRs):\s+(\S+)", line)
     if not m:
         continue
