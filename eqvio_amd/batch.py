@@ -101,6 +101,8 @@ def load_batch_protos():
         "eqf_batch_set_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
         "eqf_batch_get_slot_settings": (C.c_int, [vp, C.c_int, P(Settings)]),
         "eqf_batch_check_settings": (C.c_int, [P(Settings)]),
+        "eqf_batch_set_slot_chart": (C.c_int, [vp, C.c_int, C.c_int]),
+        "eqf_batch_get_slot_chart": (C.c_int, [vp, C.c_int]),
         "eqf_batch_num_landmarks": (C.c_int, [vp, C.c_int]),
         "eqf_batch_set_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
         "eqf_batch_get_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_int]),
@@ -140,6 +142,8 @@ def load_batch_protos():
         "eqvio_batch_get_slot_riccati": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_set_slot_state_matrix": (C.c_int, [vp, C.c_int, C.c_int]),
         "eqvio_batch_get_slot_state_matrix": (C.c_int, [vp, C.c_int]),
+        "eqvio_batch_set_slot_chart": (C.c_int, [vp, C.c_int, C.c_int]),
+        "eqvio_batch_get_slot_chart": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_process_imu": (C.c_int, [vp, C.c_int, c_double_p]),
         "eqvio_batch_process_vision": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, P(Camera), c_int_p, c_int_p, c_double_p, c_int_p]),
         "eqvio_batch_run_prepared": (C.c_int, [vp, P(vp), C.c_int, C.c_int]),
@@ -170,7 +174,8 @@ def load_batch_protos():
         for name, (res, args) in protos.items():
             if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_batch_load_ctx", "eqf_batch_store_ctx", "eqvio_batch_load_filter", "eqvio_batch_store_filter", "eqf_batch_step_accurate", "eqf_batch_last_riccati",
                                                                    "eqvio_batch_set_slot_riccati", "eqvio_batch_get_slot_riccati", "eqf_batch_step_discrete",
-                                                                   "eqvio_batch_set_slot_state_matrix", "eqvio_batch_get_slot_state_matrix") and not hasattr(lib, name):
+                                                                   "eqvio_batch_set_slot_state_matrix", "eqvio_batch_get_slot_state_matrix", "eqf_batch_set_slot_chart",
+                                                                   "eqf_batch_get_slot_chart", "eqvio_batch_set_slot_chart", "eqvio_batch_get_slot_chart") and not hasattr(lib, name):
                 continue  # same-box A/B against the libraries of an older commit (as capi.load_eqf_lib): entry points that commit did not have yet
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
@@ -228,6 +233,16 @@ class BatchCore:
         if self.h and self.owner is None:
             self.elib.eqf_batch_destroy(self.h)
         self.h = C.c_void_p()
+
+    def set_slot_chart(self, k, chart):
+        """Slot k's coordinate chart on its own (eqf_batch_set_slot_chart), COORD_NORMAL included; raises BatchError with EQF_E_BAD_ARG when refused."""
+        self._chk(self.elib.eqf_batch_set_slot_chart(self.h, k, chart))
+
+    def slot_chart(self, k):
+        rc = self.elib.eqf_batch_get_slot_chart(self.h, k)
+        if rc < 0:
+            self._chk(rc)
+        return rc
 
     def __del__(self):
         try:
@@ -363,6 +378,20 @@ class VIOFilterBatch:
         rc = self.lib.eqvio_batch_set_slot_state_matrix(self.h, -1 if k is None else k, kind)
         if rc != 0:
             raise BatchError(f"set_slot_state_matrix({k}, {kind}): " + self.elib.eqf_error_string(rc).decode(), rc)
+
+    def set_slot_chart(self, k, chart):
+        """Slot k's coordinate chart on its own, from its next frame on (eqvio_batch_set_slot_chart): COORD_EUCLIDEAN, COORD_INVDEPTH or COORD_NORMAL - the way to
+        the Normal chart, which the settings calls refuse. k None: every slot (all of them or none). A chart outside the enum, a bad slot, or a slot that holds
+        landmarks under another chart raises BatchError with EQF_E_BAD_ARG and changes nothing."""
+        rc = self.lib.eqvio_batch_set_slot_chart(self.h, -1 if k is None else k, chart)
+        if rc:
+            raise BatchError(f"set_slot_chart({k}, {chart}): " + self.elib.eqf_error_string(rc).decode(), rc)
+
+    def slot_chart(self, k):
+        rc = self.lib.eqvio_batch_get_slot_chart(self.h, k)
+        if rc < 0:
+            raise BatchError(f"slot_chart({k}): " + self.elib.eqf_error_string(rc).decode(), rc)
+        return rc
 
     def slot_state_matrix(self, k):
         rc = self.lib.eqvio_batch_get_slot_state_matrix(self.h, k)
@@ -626,6 +655,15 @@ class BatchSlot:
     @state_matrix.setter
     def state_matrix(self, kind):
         self.b.set_slot_state_matrix(self.k, kind)
+
+    @property
+    def chart(self):
+        """COORD_EUCLIDEAN, COORD_INVDEPTH or COORD_NORMAL (VIOFilterBatch.set_slot_chart)."""
+        return self.b.slot_chart(self.k)
+
+    @chart.setter
+    def chart(self, chart):
+        self.b.set_slot_chart(self.k, chart)
 
     def copy_to(self, dsts):
         """This slot into every slot of dsts (one slot or a list), one launch (VIOFilterBatch.copy_slots); returns the status codes."""

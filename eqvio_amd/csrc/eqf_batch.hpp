@@ -1,5 +1,5 @@
 // Filter batch (include/eqf_batch.h): B independent filters of at most 64 landmarks, one workgroup per slot, ONE launch per frame of all of them.
-// The device side: the packet structs and the eleven kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
+// The device side: the packet structs and the kernels. The host side (the batch object, its packet buffers, the entry points) is eqf_batch_host.hpp;
 // eqf_hip.hip includes both. Every piece of EqF arithmetic below is a helper of eqf_kernels.hpp / eqf_math.hpp, called unchanged.
 //
 // Per slot s, in HBM (fp64): two Sigma buffers (n x n column-major, leading dimension ld, n <= 21 + 3 * 64), two landmark buffers (35 SoA planes of stride
@@ -175,6 +175,268 @@ __global__ void __launch_bounds__(BATCH_T, 2) k_batch_frame_tail(const BatchArgs
 }
 
 // ===================================================================================================
+// The Normal chart (eqf_batch_set_slot_chart, include/eqf_batch.h; coordinateSuite/normal.cpp). A Normal slot's Sigma is expressed in Normal coordinates; its
+// Riccati step is the Euclidean step between two congruences with the block-diagonal change of coordinates M (eqf_math.hpp, normal_M; eqf_kernels.hpp,
+// NormalM / normal_row), as riccati_open / riccati_close do on the context path:
+//   Sigma' = M [ F_e (M^-1 Sigma M^-T) F_e^T + noise_e ] M^T + dt P.
+// M depends on xi0 alone - the sensor block on its velocity and camera offset, which the host supplies in the slot's BatchNormalIn as normal_congruence does,
+// a landmark's 3 x 3 block on its origin point q0 - and so is constant over a frame's propagation. Phases 2 - 5 of the frame need nothing new: measure_one,
+// outlier_stats_body, lift_load / lift_landmark and store_chart_constants carry the Normal chart through in.ss.chart, as they do for a context.
+struct BatchNormalIn {
+    NormalM inv; // dir -1: M^-1
+    NormalM fwd; // dir +1: M; k_batch_normal adds fwd.dtP on the diagonal (addP), the per-sample kernels add their noise in Euclidean coordinates (addP 0)
+};
+// Row i of T = M (nm.dir > 0) or M^-1, in normal_row's form (indices and coefficients, at most 7): a landmark row from the slot's table sM (LDS: T's 3 x 3 block of landmark l, row-major, at 9 l)
+__device__ __forceinline__ int batch_normal_row(const NormalM& nm, const double* sM, int i, int (&idx)[7], double (&co)[7]) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        idx[k] = 0;
+        co[k] = 0.0;
+    }
+    if (i < 21) { // normal_row's sensor rows, with every index of idx / co a constant (registers, no private memory)
+        const double sg = nm.dir > 0 ? 1.0 : -1.0;
+        idx[0] = i;
+        co[0] = 1.0;
+        if (i < 12)
+            return 1;
+        if (i < 15) { // [12:15, 6:9] = -skew(v0) (inverse: +skew(v0))
+            const V3 r = row(skew(V3{nm.v0[0], nm.v0[1], nm.v0[2]}), i - 12);
+            idx[1] = 6, idx[2] = 7, idx[3] = 8;
+            co[1] = -sg * r.x, co[2] = -sg * r.y, co[3] = -sg * r.z;
+            return 4;
+        }
+        const double* ad = nm.Ad + 6 * (i - 15); // [15:21, 6:12] = Ad(T0^-1) (inverse: -Ad(T0^-1))
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            idx[1 + c] = 6 + c;
+            co[1 + c] = sg * ad[c];
+        }
+        return 7;
+    }
+    const int l = (i - 21) / 3, r = (i - 21) % 3;
+    idx[0] = 21 + 3 * l, idx[1] = idx[0] + 1, idx[2] = idx[0] + 2;
+    co[0] = sM[9 * l + 3 * r], co[1] = sM[9 * l + 3 * r + 1], co[2] = sM[9 * l + 3 * r + 2];
+    return 3;
+}
+// The landmarks' blocks of M (sMf) and M^-1 (sMi) into LDS: landmark i's origin point is entry (map ? map[i] : i) of the planes
+__device__ __forceinline__ void batch_normal_tables(const double* planes, const int* map, int Ns, double* sMf, double* sMi) {
+    for (int i = threadIdx.x; i < Ns; i += BATCH_T) {
+        const V3 p0 = ld3(planes, BATCH_L, map ? map[i] : i);
+        const M3 Mf = normal_M(p0), Mi = normal_Minv(p0);
+        const double f[9] = {Mf.a00, Mf.a01, Mf.a02, Mf.a10, Mf.a11, Mf.a12, Mf.a20, Mf.a21, Mf.a22};
+        const double v[9] = {Mi.a00, Mi.a01, Mi.a02, Mi.a10, Mi.a11, Mi.a12, Mi.a20, Mi.a21, Mi.a22};
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+            sMf[9 * i + e] = f[e];
+            sMi[9 * i + e] = v[e];
+        }
+    }
+}
+// dst (n1 x n1: lower half, mirrored, so that Sigma stays exactly symmetric) = T src[g, g] T^T, plus nm.dtP on the diagonal when nm.addP; T and sM as in
+// batch_normal_row, g = gidx (LDS). dst and src are different buffers. k_congruence_normal's sums, inside the slot's workgroup.
+__device__ __forceinline__ void batch_normal_congruence(const NormalM& nm, const double* sM, int n1, int ld, const double* src, const int* gidx, double* dst) {
+    for (int t = threadIdx.x; t < n1 * n1; t += BATCH_T) {
+        const int i = t % n1, j = t / n1;
+        if (i < j)
+            continue;
+        int ii[7], jj[7];
+        double ci[7], cj[7];
+        const int ni = batch_normal_row(nm, sM, i, ii, ci), nj = batch_normal_row(nm, sM, j, jj, cj);
+        double acc = 0.0;
+#pragma unroll
+        for (int b = 0; b < 7; ++b) {
+            if (b < nj) {
+                const double* col = src + (size_t)gidx[jj[b]] * ld;
+                double s = 0.0;
+#pragma unroll
+                for (int a = 0; a < 7; ++a)
+                    if (a < ni)
+                        s = fma(ci[a], col[gidx[ii[a]]], s);
+                acc = fma(cj[b], s, acc);
+            }
+        }
+        if (nm.addP && i == j)
+            acc += nm.dtP[i < 21 ? i / 3 : 7];
+        dst[i + (size_t)j * ld] = acc;
+        dst[j + (size_t)i * ld] = acc;
+    }
+}
+// The process noise of a Normal slot in Euclidean coordinates, M^-1 P M^-T (block diagonal like M), for the per-sample kernels: the 21 x 21 sensor block
+// (row-major) at pe, the landmarks' 3 x 3 blocks behind it (9 per landmark, at 441 + 9 l). nm = the slot's M^-1, sMi its landmark table, Pd the eight variances.
+constexpr int BATCH_NORMAL_PE = 441 + 9 * BATCH_L;
+static_assert(BATCH_NORMAL_PE <= 16 * BATCH_L, "M^-1 P M^-T fits into the statistics rows of the slot's scratch area");
+__device__ __forceinline__ void batch_normal_noise(const NormalM& nm, const double* sMi, int Ns, const double* Pd, double* pe) {
+    for (int t = threadIdx.x; t < 441; t += BATCH_T) {
+        const int r = t / 21, c = t % 21;
+        int ii[7], jj[7];
+        double ci[7], cj[7];
+        const int ni = batch_normal_row(nm, sMi, r, ii, ci), nj = batch_normal_row(nm, sMi, c, jj, cj);
+        double acc = 0.0;
+#pragma unroll
+        for (int a = 0; a < 7; ++a)
+#pragma unroll
+            for (int b = 0; b < 7; ++b)
+                if (a < ni && b < nj && ii[a] == jj[b])
+                    acc += ci[a] * cj[b] * Pd[ii[a] / 3];
+        pe[t] = acc;
+    }
+    for (int t = threadIdx.x; t < 9 * Ns; t += BATCH_T) {
+        const int l = t / 9, a = (t % 9) / 3, b = t % 3;
+        const double* m = sMi + 9 * l;
+        pe[441 + t] = Pd[7] * (m[3 * a] * m[3 * b] + m[3 * a + 1] * m[3 * b + 1] + m[3 * a + 2] * m[3 * b + 2]);
+    }
+}
+// entry (r, c), r >= c, of that noise
+__device__ __forceinline__ double batch_normal_noise_at(const double* pe, int r, int c) {
+    if (r < 21)
+        return pe[r * 21 + c];
+    if (c < 21 || (r - 21) / 3 != (c - 21) / 3)
+        return 0.0;
+    return pe[441 + 9 * ((r - 21) / 3) + 3 * ((r - 21) % 3) + (c - 21) % 3];
+}
+
+// eqf_batch_step of the Normal slots: what phases 0 and 1 of k_batch_frame do for the other charts, followed by k_batch_frame_tail on the same stream, as
+// k_batch_riccati / k_batch_discrete are. A kernel of its own and not another shape of the frame body: k_batch_frame keeps its text (eqf_batch_frame_body.inc).
+//   0  as k_batch_frame's phase 0, with the rows assemble_landmark gives for the Euclidean chart, kept as dt A_e (the entries of F_e - I, as the reference's
+//      I + dt A has them: a Sigma with entries near the largest double does not overflow in a sum that dt would have scaled down afterwards); the landmarks'
+//      blocks of M and M^-1 into LDS, behind the rows
+//      (the region the update's S needs anyway: BATCH_SM doubles, k_batch_frame's footprint);
+//   a  Sigma_e = M^-1 Sigma[g, g] M^-T, gathered through the surviving rows, into the other Sigma buffer;
+//   b  G = F_e Sigma_e into the scratch area;
+//   c  G F_e^T + dt B_e Q B_e^T (no P) into the current Sigma buffer, whose contents step a has finished with - phase 3 of the tail overwrites it in any case;
+//   d  Sigma' = M ( . ) M^T + dt P into the other Sigma buffer: where k_batch_frame_tail expects the propagated Sigma.
+static_assert(BATCH_SM_PROP + 20 + 18 * BATCH_L <= BATCH_SM, "the landmarks' blocks of M and M^-1 sit behind the propagation rows and the slot's Qd / Pd");
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_normal(const BatchArgs ba, const BatchNormalIn* nrm) {
+    __shared__ double sm[BATCH_SM];
+    __shared__ int s_gidx[BATCH_NMAX];
+    __shared__ int s_surv[BATCH_L];
+    const BatchIn& in = ba.in[blockIdx.x];
+    const BatchNormalIn& nb = nrm[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int L = BATCH_L, ld = ba.buf.ld;
+    const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
+    double* S0 = ba.buf.sig_of(slot, cur);
+    double* S1 = ba.buf.sig_of(slot, nxt);
+    const double* L0 = ba.buf.lm_of(slot, cur);
+    double* L1 = ba.buf.lm_of(slot, nxt);
+    double* G = ba.buf.scr_of(slot);
+    const int Ns = in.Ns, n1 = 21 + 3 * Ns;
+    const double dt = in.dt;
+    double* Ass = sm;
+    double* Bs = sm + 441;
+    double* lm66 = sm + 693;
+    double* Al = sm + 759;
+    double* Bl = Al + BATCH_L * 45;
+    double* Qd = sm + BATCH_SM_PROP;
+    double* sMf = Qd + 20;
+    double* sMi = sMf + 9 * BATCH_L;
+    if (tid < 12)
+        Qd[tid] = in.ss.Qd[tid];
+    for (int t = tid; t < 441; t += BATCH_T)
+        Ass[t] = dt * sensor_Ass_entry(in.ck, t); // dt A_e: F_e = I + dt A_e entry by entry, as the reference forms it
+    for (int t = tid; t < 252; t += BATCH_T)
+        Bs[t] = sensor_Bs_entry(in.ck, t);
+    for (int t = tid; t < 66; t += BATCH_T)
+        lm66[t] = in.ck.lm[t];
+    for (int t = tid; t < Ns; t += BATCH_T)
+        s_surv[t] = in.surv[t];
+    __syncthreads();
+    for (int r = tid; r < n1; r += BATCH_T)
+        s_gidx[r] = r < 21 ? r : 21 + 3 * s_surv[(r - 21) / 3] + (r - 21) % 3;
+    batch_normal_tables(L0, s_surv, Ns, sMf, sMi);
+    {
+        // k_batch_frame's split: waves 0 / 1 / 2 the three column parts of a landmark's rows of A_e and B_e, wave 3 its planes and the observer steps
+        const int wave = tid >> 6, i = tid & 63;
+        if (i < Ns) {
+            const int o = s_surv[i];
+            const V3 p0 = ld3(L0, L, o);
+            Qt q = ldq(L0 + BATCH_QQ * L, L, o);
+            double a = L0[BATCH_QA * L + o];
+            if (wave < 3) {
+                double al[45], bl[9];
+                if (wave == 0) {
+                    assemble_landmark<0>(lm66, EQVIO_COORD_EUCLIDEAN, p0, q, a, M3{}, M3{}, al, bl);
+                    for (int r = 0; r < 3; ++r)
+                        for (int c = 0; c < 6; ++c)
+                            Al[i * 45 + r * 15 + c] = dt * al[r * 15 + c];
+                    for (int e = 0; e < 9; ++e)
+                        Bl[i * 9 + e] = bl[e];
+                } else if (wave == 1) {
+                    assemble_landmark<1>(lm66, EQVIO_COORD_EUCLIDEAN, p0, q, a, M3{}, M3{}, al, bl);
+                    for (int r = 0; r < 3; ++r)
+                        for (int c = 6; c < 12; ++c)
+                            Al[i * 45 + r * 15 + c] = dt * al[r * 15 + c];
+                } else {
+                    assemble_landmark<2>(lm66, EQVIO_COORD_EUCLIDEAN, p0, q, a, M3{}, M3{}, al, bl);
+                    for (int r = 0; r < 3; ++r)
+                        for (int c = 12; c < 15; ++c)
+                            Al[i * 45 + r * 15 + c] = dt * al[r * 15 + c];
+                }
+            } else {
+                for (int pl = 0; pl < BATCH_QQ; ++pl)
+                    L1[pl * L + i] = L0[pl * L + o];
+                if (in.k > 0)
+                    observer_chain(ba.steps + in.obs_off, in.k, p0, q, a);
+                L1[BATCH_QQ * L + i] = q.w;
+                L1[(BATCH_QQ + 1) * L + i] = q.x;
+                L1[(BATCH_QQ + 2) * L + i] = q.y;
+                L1[(BATCH_QQ + 3) * L + i] = q.z;
+                L1[BATCH_QA * L + i] = a;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- a: into Euclidean coordinates
+    batch_normal_congruence(nb.inv, sMi, n1, ld, S0, s_gidx, S1);
+    __syncthreads();
+    for (int r = tid; r < n1; r += BATCH_T)
+        s_gidx[r] = r;
+    // ---- b, c: k_batch_frame's phase 1 on Sigma_e, without P
+    auto f_row = [&](int r, auto v) -> double {
+        double acc = 0.0;
+        if (r < 21) {
+            for (int k = 0; k < 21; ++k)
+                acc += Ass[r * 21 + k] * v(k);
+        } else {
+            const int i = (r - 21) / 3, a = (r - 21) % 3;
+            const double* row = Al + i * 45 + a * 15;
+            for (int e = 0; e < 12; ++e)
+                acc += row[e] * v(al_col(e));
+            for (int b = 0; b < 3; ++b)
+                acc += row[12 + b] * v(21 + 3 * i + b);
+        }
+        return v(r) + acc;
+    };
+    auto b_entry = [&](int r, int e) -> double {
+        if (r < 21)
+            return Bs[r * 12 + e];
+        const int i = (r - 21) / 3, a = (r - 21) % 3;
+        return e < 3 ? Bl[i * 9 + a * 3 + e] : 0.0;
+    };
+    for (int t = tid; t < n1 * n1; t += BATCH_T) {
+        const int r = t % n1, c = t / n1;
+        const double* col = S1 + (size_t)c * ld;
+        G[r + (size_t)c * ld] = f_row(r, [&](int k) { return col[k]; });
+    }
+    __syncthreads();
+    for (int t = tid; t < n1 * n1; t += BATCH_T) {
+        const int r = t % n1, c = t / n1;
+        if (r < c)
+            continue;
+        double v = f_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
+        double nz = 0.0;
+        for (int e = 0; e < 12; ++e)
+            nz += b_entry(r, e) * Qd[e] * b_entry(c, e);
+        v += dt * nz;
+        S0[r + (size_t)c * ld] = v;
+        S0[c + (size_t)r * ld] = v;
+    }
+    __syncthreads();
+    // ---- d: back into Normal coordinates, plus dt P
+    batch_normal_congruence(nb.fwd, sMf, n1, ld, S0, s_gidx, S1);
+}
+
+// ===================================================================================================
 // eqf_batch_step_accurate (include/eqf_batch.h): integrateUpToTime with fastRiccati == false (src/VIOFilter.cpp:160-178) - per IMU sample one
 // integrateRiccatiStateAccurate (VIO_eqf.cpp:74-91) at the X the samples before it have produced, then that sample's observer step - as a kernel of its own in
 // front of k_batch_frame_tail, on the same stream within the same round trip. It ends where phases 0 and 1 of k_batch_frame end: Sigma of the surviving
@@ -204,318 +466,21 @@ constexpr int RIC_SLOT = 3 * 33 + 9;                   // a landmark's Y and F; 
 constexpr int RIC_SM = 4 * RIC_EN + 66 + BATCH_L * RIC_SLOT;
 static_assert(4 * (3 * 33) <= RIC_EN, "the waves' staging rows fit into the sensor series' temporary");
 
+// The kernel's body is eqf_batch_riccati_body.inc, included once per kernel like the frame's. k_batch_riccati_normal (the Normal slots): the same samples in
+// Euclidean coordinates between the two congruences. Before the first sample Sigma_e = M^-1 Sigma[g, g] M^-T goes to the other buffer in the gather's place; every
+// sample works with the rows assemble_landmark gives for the Euclidean chart and adds dt M^-1 P M^-T (batch_normal_noise, kept in the statistics rows of the
+// scratch area, which nothing reads before k_batch_frame_tail writes them) where the other charts add dt P; behind the last sample Sigma' = M Sigma_e M^T goes
+// through the scratch area back to the other buffer. The landmark tables of M and M^-1 use the kernel's LDS while no sample does. Without a sample of dt > 0
+// there is no congruence either: the gathered Sigma, bit for bit.
 __global__ void __launch_bounds__(BATCH_T, 2) k_batch_riccati(const RicArgs ra) {
-    __shared__ double sm[RIC_SM];
-    __shared__ double s_red[BATCH_T / 64];
-    __shared__ double s_qp[20]; // Q / dt and dt P of the sample
-    __shared__ int s_gidx[BATCH_NMAX];
-    __shared__ int s_surv[BATCH_L];
-    const BatchIn& in = ra.in[blockIdx.x];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int L = BATCH_L, ld = ra.buf.ld;
-    const int chart = in.ss.chart;
-    const bool ind = chart == EQVIO_COORD_INVDEPTH;
-    const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
-    const double* S0 = ra.buf.sig_of(slot, cur);
-    double* S1 = ra.buf.sig_of(slot, nxt);
-    const double* L0 = ra.buf.lm_of(slot, cur);
-    double* L1 = ra.buf.lm_of(slot, nxt);
-    double* G = ra.buf.scr_of(slot);
-    const int Ns = in.Ns, n1 = 21 + 3 * Ns, K = in.k;
-    double* sP = sm;              // [A B] of the sensor rows (21 x 33, row-major), then scaled
-    double* sE = sP + RIC_EN;     // E
-    double* sT = sE + RIC_EN;     // the series' current term; afterwards the waves' staging rows (3 x 33 each)
-    double* sN = sT + RIC_EN;     // the next term, the next square
-    double* lm66 = sN + RIC_EN;
-    double* YF = lm66 + 66;       // per landmark: Y (3 x 33, row-major), F (3 x 3)
-
-    for (int t = tid; t < Ns; t += BATCH_T)
-        s_surv[t] = in.surv[t];
-    __syncthreads();
-    for (int r = tid; r < n1; r += BATCH_T)
-        s_gidx[r] = r < 21 ? r : 21 + 3 * s_surv[(r - 21) / 3] + (r - 21) % 3;
-    // the surviving landmarks' planes into the other buffer; wave 3 keeps (q, a) of its landmark and takes it through the observer steps
-    V3 p0{};
-    Qt q{};
-    double a = 1.0;
-    if (wave == 3 && lane < Ns) {
-        const int o = s_surv[lane];
-        for (int pl = 0; pl < BATCH_PLANES; ++pl)
-            L1[pl * L + lane] = L0[pl * L + o];
-        p0 = ld3(L0, L, o);
-        q = ldq(L0 + BATCH_QQ * L, L, o);
-        a = L0[BATCH_QA * L + o];
-    }
-    __syncthreads();
-
-    bool first = true; // Sigma is still the current buffer's, to be gathered
-    int samples = 0, max_sq = 0;
-    for (int s = 0; s < K; ++s) {
-        const RicStep& rs = ra.rsteps[in.obs_off + s];
-        const double dt = rs.dt;
-        if (dt > 0.0) {
-            // ---- A and B at this sample's X: the sensor rows into sP, the landmarks' rows into their slots (assemble_landmark<PART>, a wave per column part)
-            for (int t = tid; t < RIC_EN; t += BATCH_T) {
-                const int r = t / 33, c = t % 33;
-                sP[t] = c < 21 ? sensor_Ass_entry(rs.ck, r * 21 + c) : sensor_Bs_entry(rs.ck, r * 12 + (c - 21));
-            }
-            for (int t = tid; t < 66; t += BATCH_T)
-                lm66[t] = rs.ck.lm[t];
-            if (tid < 12)
-                s_qp[tid] = in.ss.Qd[tid] / dt;
-            else if (tid < 20)
-                s_qp[tid] = dt * in.ss.Pd[tid - 12];
-            __syncthreads();
-            if (wave < 3 && lane < Ns) {
-                const int i = lane;
-                const V3 pi = ld3(L1, L, i);
-                const Qt qi = ldq(L1 + BATCH_QQ * L, L, i);
-                const double ai = L1[BATCH_QA * L + i];
-                const M3 e2i = ind ? ld_cc(L1, L, i, CC_E2I) : M3{}, i2e = ind && wave == 2 ? ld_cc(L1, L, i, CC_I2E) : M3{};
-                double al[45], bl[9];
-                double* Al = YF + i * RIC_SLOT;
-                if (wave == 0) {
-                    assemble_landmark<0>(lm66, chart, pi, qi, ai, e2i, i2e, al, bl);
-                    for (int r = 0; r < 3; ++r)
-                        for (int c = 0; c < 6; ++c)
-                            Al[r * 15 + c] = al[r * 15 + c];
-                    for (int e = 0; e < 9; ++e)
-                        Al[45 + e] = bl[e];
-                } else if (wave == 1) {
-                    assemble_landmark<1>(lm66, chart, pi, qi, ai, e2i, i2e, al, bl);
-                    for (int r = 0; r < 3; ++r)
-                        for (int c = 6; c < 12; ++c)
-                            Al[r * 15 + c] = al[r * 15 + c];
-                } else {
-                    assemble_landmark<2>(lm66, chart, pi, qi, ai, e2i, i2e, al, bl);
-                    for (int r = 0; r < 3; ++r)
-                        for (int c = 12; c < 15; ++c)
-                            Al[r * 15 + c] = al[r * 15 + c];
-                }
-            }
-            __syncthreads();
-            // ---- the scaling: s with |dt [A B]|_inf / 2^s <= 0.25 (k_expm_sensor's rule)
-            {
-                double mx = 0.0;
-                if (tid < 21) {
-                    for (int c = 0; c < 33; ++c)
-                        mx += fabs(sP[tid * 33 + c]);
-                } else if (tid >= 64 && tid - 64 < 3 * Ns) {
-                    const int i = (tid - 64) / 3, r = (tid - 64) % 3;
-                    const double* Al = YF + i * RIC_SLOT;
-                    for (int e = 0; e < 15; ++e)
-                        mx += fabs(Al[r * 15 + e]);
-                    for (int e = 0; e < 3; ++e)
-                        mx += fabs(Al[45 + r * 3 + e]);
-                }
-                for (int o = 32; o > 0; o >>= 1)
-                    mx = fmax(mx, __shfl_xor(mx, o, 64));
-                if (lane == 0)
-                    s_red[wave] = mx;
-            }
-            __syncthreads();
-            int sc = 0;
-            {
-                const double nrm = dt * fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
-                while (sc < EXPM_SMAX && ldexp(nrm, -sc) > 0.25)
-                    ++sc;
-            }
-            const double scale = ldexp(dt, -sc);
-            ++samples;
-            max_sq = max(max_sq, sc);
-            // ---- sensor part: E = sum_k Ps^k / k! (rows 21 .. 32 of Ps are zero: the inner index runs over 21)
-            for (int t = tid; t < RIC_EN; t += BATCH_T) {
-                const double v = scale * sP[t];
-                sP[t] = v;
-                sT[t] = v;
-                sE[t] = v + (t / 33 == t % 33 ? 1.0 : 0.0);
-            }
-            __syncthreads();
-            for (int k = 2; k <= EXPM_K; ++k) {
-                for (int t = tid; t < RIC_EN; t += BATCH_T) {
-                    const int r = t / 33, c = t % 33;
-                    double acc = 0.0;
-                    for (int qq = 0; qq < 21; ++qq)
-                        acc += sT[r * 33 + qq] * sP[qq * 33 + c];
-                    sN[t] = acc / k;
-                }
-                __syncthreads();
-                for (int t = tid; t < RIC_EN; t += BATCH_T) {
-                    sT[t] = sN[t];
-                    sE[t] += sN[t];
-                }
-                __syncthreads();
-            }
-            // ---- landmark part, a wave per landmark and a lane per column: term_k = (term_{k-1} Ps + S^(k-1) / (k-1)! R) / k (k_expm_landmarks)
-            {
-                double* sR = sT + wave * 99;
-                const int c = lane;
-                for (int i = wave; i < Ns; i += BATCH_T / 64) {
-                    double* sl = YF + i * RIC_SLOT;
-                    double R[3] = {0, 0, 0};
-                    if (c < 33) {
-                        const int e = c < 3 ? c : (c >= 12 && c < 15) ? 3 + (c - 12) : (c >= 15 && c < 21) ? 6 + (c - 15) : -1;
-                        for (int r = 0; r < 3; ++r) {
-                            if (e >= 0)
-                                R[r] = scale * sl[r * 15 + e];
-                            else if (c >= 21 && c < 24)
-                                R[r] = scale * sl[45 + r * 3 + (c - 21)];
-                        }
-                    }
-                    double S[9], F[9], Spow[9];
-                    for (int r = 0; r < 3; ++r)
-                        for (int qq = 0; qq < 3; ++qq) {
-                            S[r * 3 + qq] = scale * sl[r * 15 + 12 + qq];
-                            Spow[r * 3 + qq] = S[r * 3 + qq];
-                            F[r * 3 + qq] = (r == qq ? 1.0 : 0.0) + S[r * 3 + qq];
-                        }
-                    double T[3] = {R[0], R[1], R[2]}, Y[3] = {R[0], R[1], R[2]};
-                    for (int k = 2; k <= EXPM_K; ++k) {
-                        batch_wave_sync(); // the staging rows' readers of the round before (and the slot's, before the first one) are done
-                        if (c < 33)
-                            for (int r = 0; r < 3; ++r)
-                                sR[r * 33 + c] = T[r];
-                        batch_wave_sync();
-                        double nt[3] = {0, 0, 0};
-                        if (c < 33) {
-                            for (int qq = 0; qq < 21; ++qq) {
-                                const double pv = sP[qq * 33 + c];
-                                nt[0] += sR[qq] * pv;
-                                nt[1] += sR[33 + qq] * pv;
-                                nt[2] += sR[66 + qq] * pv;
-                            }
-                            for (int r = 0; r < 3; ++r)
-                                nt[r] = (nt[r] + Spow[r * 3 + 0] * R[0] + Spow[r * 3 + 1] * R[1] + Spow[r * 3 + 2] * R[2]) / k;
-                        }
-                        double ns[9];
-                        for (int r = 0; r < 3; ++r)
-                            for (int qq = 0; qq < 3; ++qq)
-                                ns[r * 3 + qq] = (Spow[r * 3 + 0] * S[0 * 3 + qq] + Spow[r * 3 + 1] * S[1 * 3 + qq] + Spow[r * 3 + 2] * S[2 * 3 + qq]) / k;
-                        for (int r = 0; r < 3; ++r) {
-                            T[r] = nt[r];
-                            Y[r] += nt[r];
-                        }
-                        for (int e = 0; e < 9; ++e) {
-                            Spow[e] = ns[e];
-                            F[e] += ns[e];
-                        }
-                    }
-                    batch_wave_sync();
-                    if (c < 33)
-                        for (int r = 0; r < 3; ++r)
-                            sl[r * 33 + c] = Y[r];
-                    if (c < 9)
-                        sl[99 + c] = F[c];
-                }
-            }
-            __syncthreads();
-            // ---- squarings, in lockstep: Y <- Y E + F Y and F <- F F of every landmark with this round's E, then E <- E E (rows 21 .. 32 of E are [0 I])
-            for (int j = 0; j < sc; ++j) {
-                const int c = lane;
-                for (int i = wave; i < Ns; i += BATCH_T / 64) {
-                    double* sl = YF + i * RIC_SLOT;
-                    double ny[3] = {0, 0, 0}, nf = 0.0;
-                    if (c < 33) {
-                        for (int r = 0; r < 3; ++r)
-                            ny[r] = c >= 21 ? sl[r * 33 + c] : 0.0;
-                        for (int qq = 0; qq < 21; ++qq) {
-                            const double pv = sE[qq * 33 + c];
-                            ny[0] += sl[qq] * pv;
-                            ny[1] += sl[33 + qq] * pv;
-                            ny[2] += sl[66 + qq] * pv;
-                        }
-                        const double y0 = sl[c], y1 = sl[33 + c], y2 = sl[66 + c];
-                        for (int r = 0; r < 3; ++r)
-                            ny[r] += sl[99 + r * 3 + 0] * y0 + sl[99 + r * 3 + 1] * y1 + sl[99 + r * 3 + 2] * y2;
-                    }
-                    if (c < 9) {
-                        const int r = c / 3, qq = c % 3;
-                        nf = sl[99 + r * 3 + 0] * sl[99 + 0 * 3 + qq] + sl[99 + r * 3 + 1] * sl[99 + 1 * 3 + qq] + sl[99 + r * 3 + 2] * sl[99 + 2 * 3 + qq];
-                    }
-                    batch_wave_sync();
-                    if (c < 33)
-                        for (int r = 0; r < 3; ++r)
-                            sl[r * 33 + c] = ny[r];
-                    if (c < 9)
-                        sl[99 + c] = nf;
-                }
-                for (int t = tid; t < RIC_EN; t += BATCH_T) {
-                    const int r = t / 33, cc = t % 33;
-                    double acc = cc >= 21 ? sE[r * 33 + cc] : 0.0;
-                    for (int qq = 0; qq < 21; ++qq)
-                        acc += sE[r * 33 + qq] * sE[qq * 33 + cc];
-                    sN[t] = acc;
-                }
-                __syncthreads();
-                for (int t = tid; t < RIC_EN; t += BATCH_T)
-                    sE[t] = sN[t];
-                __syncthreads();
-            }
-            // ---- Sigma' = Phi Sigma Phi^T + Phi_B (Q / dt) Phi_B^T + dt P
-            // row r of Phi applied to a vector given entry by entry (the shape of k_batch_frame's f_row; a landmark row carries all 21 sensor columns)
-            auto phi_row = [&](int r, auto v) -> double {
-                double acc = 0.0;
-                if (r < 21) {
-                    for (int k = 0; k < 21; ++k)
-                        acc += sE[r * 33 + k] * v(k);
-                } else {
-                    const int i = (r - 21) / 3, aa = (r - 21) % 3;
-                    const double* sl = YF + i * RIC_SLOT;
-                    for (int k = 0; k < 21; ++k)
-                        acc += sl[aa * 33 + k] * v(k);
-                    for (int b = 0; b < 3; ++b)
-                        acc += sl[99 + aa * 3 + b] * v(21 + 3 * i + b);
-                }
-                return acc;
-            };
-            auto phib = [&](int r, int e) -> double { return r < 21 ? sE[r * 33 + 21 + e] : YF[((r - 21) / 3) * RIC_SLOT + ((r - 21) % 3) * 33 + 21 + e]; };
-            const double* Ssrc = first ? S0 : S1;
-            for (int t = tid; t < n1 * n1; t += BATCH_T) {
-                const int r = t % n1, c = t / n1;
-                const double* col = Ssrc + (size_t)s_gidx[c] * ld;
-                G[r + (size_t)c * ld] = phi_row(r, [&](int k) { return col[s_gidx[k]]; });
-            }
-            __syncthreads();
-            for (int t = tid; t < n1 * n1; t += BATCH_T) {
-                const int r = t % n1, c = t / n1;
-                if (r < c)
-                    continue;
-                double v = phi_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
-                double nz = 0.0;
-                for (int e = 0; e < 12; ++e)
-                    nz += phib(r, e) * s_qp[e] * phib(c, e);
-                v += nz;
-                if (r == c)
-                    v += s_qp[12 + (r < 21 ? r / 3 : 7)];
-                S1[r + (size_t)c * ld] = v;
-                S1[c + (size_t)r * ld] = v;
-            }
-            if (first) { // the gathered rows' readers are behind the barrier above; the next reader is behind the sample's last one
-                for (int r = tid; r < n1; r += BATCH_T)
-                    s_gidx[r] = r;
-                first = false;
-            }
-        }
-        // ---- this sample's observer step of the landmarks
-        if (wave == 3 && lane < Ns) {
-            observer_chain(ra.steps + in.obs_off + s, 1, p0, q, a);
-            L1[BATCH_QQ * L + lane] = q.w;
-            L1[(BATCH_QQ + 1) * L + lane] = q.x;
-            L1[(BATCH_QQ + 2) * L + lane] = q.y;
-            L1[(BATCH_QQ + 3) * L + lane] = q.z;
-            L1[BATCH_QA * L + lane] = a;
-        }
-        __syncthreads();
-    }
-    if (first) // no sample moved Sigma: the gathered Sigma as it is
-        for (int t = tid; t < n1 * n1; t += BATCH_T) {
-            const int r = t % n1, c = t / n1;
-            S1[r + (size_t)c * ld] = S0[s_gidx[r] + (size_t)s_gidx[c] * ld];
-        }
-    if (tid == 0) {
-        ra.out[blockIdx.x].ric_samples = samples;
-        ra.out[blockIdx.x].ric_squarings = max_sq;
-    }
+#define EQF_BATCH_NORMAL 0
+#include "eqf_batch_riccati_body.inc"
+#undef EQF_BATCH_NORMAL
+}
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_riccati_normal(const RicArgs ra, const BatchNormalIn* nrm) {
+#define EQF_BATCH_NORMAL 1
+#include "eqf_batch_riccati_body.inc"
+#undef EQF_BATCH_NORMAL
 }
 
 // ===================================================================================================
@@ -567,7 +532,9 @@ constexpr int DISC_SM = 441 + 252 + 66 + DISC_NPERT * 21 + BATCH_L * DISC_SLOT;
 // pose change of liftVelocityDiscrete(xi_hat) -, lane 2 j + s < 42 the one with sensor coordinate j moved by +h (s = 0) or -h (s = 1), which leaves its cpc and its
 // 21-vector epsilon_1. The chain is eqf_integrate_riccati_discrete's discrete_A (eqf_hip.hip), term for term. A function of its own (noinline): its 46-double
 // states are live only here, not across the kernel. The order keeps few of them live at once: Lambda_hat^-1, then xi_e and its lift, then the products.
-__device__ __attribute__((noinline)) void disc_sensor_eval(const DiscStep& ds, int lane, double h, double* sCol, Pose* cpc) {
+// (VARIANT: one copy per kernel that calls it - the kernel's EQF_BATCH_NORMAL -, so that each kernel is compiled with a callee of its own, as k_batch_discrete
+// was when it was the only caller.)
+template <int VARIANT> __device__ __attribute__((noinline)) void disc_sensor_eval(const DiscStep& ds, int lane, double h, double* sCol, Pose* cpc) {
     const double dt = ds.dt;
     const SensorState xhat = sensor_action(ds.X, ds.xi0);
     const GroupSensor Lh = lift_discrete_sensor(xhat, ds.imu, dt);
@@ -608,183 +575,18 @@ __device__ __attribute__((noinline)) void disc_sensor_eval(const DiscStep& ds, i
     }
 }
 
+// The kernel's body is eqf_batch_discrete_body.inc, included once per kernel. k_batch_discrete_normal (the Normal slots): as k_batch_riccati_normal - A_d under
+// the Normal chart is M A_d,e M^-1, as on the context path (the reference differentiates in Normal coordinates; the two agree to the differencing's own noise),
+// so A_d,e and B_e are formed for the Euclidean chart and the samples run between the two congruences, with dt M^-1 P M^-T in dt P's place.
 __global__ void __launch_bounds__(BATCH_T, 2) k_batch_discrete(const DiscArgs da) {
-    __shared__ double sm[DISC_SM];
-    __shared__ Pose s_cpc[1 + DISC_NPERT]; // [0] nominal, [1 + 2 j + s]: DiscreteAArgs::cpc's order
-    __shared__ double s_qp[20];            // Q and P of the slot
-    __shared__ int s_gidx[BATCH_NMAX];
-    __shared__ int s_surv[BATCH_L];
-    const BatchIn& in = da.in[blockIdx.x];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int L = BATCH_L, ld = da.buf.ld;
-    const int chart = in.ss.chart;
-    const bool ind = chart == EQVIO_COORD_INVDEPTH;
-    const int slot = in.slot, cur = in.cur, nxt = cur ^ 1;
-    const double* S0 = da.buf.sig_of(slot, cur);
-    double* S1 = da.buf.sig_of(slot, nxt);
-    const double* L0 = da.buf.lm_of(slot, cur);
-    double* L1 = da.buf.lm_of(slot, nxt);
-    double* G = da.buf.scr_of(slot);
-    const int Ns = in.Ns, n1 = 21 + 3 * Ns, K = in.k;
-    double* sA = sm;              // sensor block of A_d, row-major 21 x 21
-    double* sB = sA + 441;        // sensor rows of B, row-major 21 x 12
-    double* lm66 = sB + 252;
-    double* sCol = lm66 + 66;     // the 42 perturbed evaluations' 21-vectors
-    double* AL = sCol + DISC_NPERT * 21; // per landmark: rows of A_d (3 x 24, row-major), then B (3 x 3)
-    const double h = cbrt(2.220446049250313e-16), ih2 = 1.0 / (2.0 * h);
-
-    for (int t = tid; t < Ns; t += BATCH_T)
-        s_surv[t] = in.surv[t];
-    if (tid < 12)
-        s_qp[tid] = in.ss.Qd[tid];
-    else if (tid < 20)
-        s_qp[tid] = in.ss.Pd[tid - 12];
-    __syncthreads();
-    for (int r = tid; r < n1; r += BATCH_T)
-        s_gidx[r] = r < 21 ? r : 21 + 3 * s_surv[(r - 21) / 3] + (r - 21) % 3;
-    // the surviving landmarks' planes into the other buffer; wave 3 keeps (q, a) of its landmark and takes it through the observer steps
-    V3 p0{};
-    Qt q{};
-    double a = 1.0;
-    if (wave == 3 && lane < Ns) {
-        const int o = s_surv[lane];
-        for (int pl = 0; pl < BATCH_PLANES; ++pl)
-            L1[pl * L + lane] = L0[pl * L + o];
-        p0 = ld3(L0, L, o);
-        q = ldq(L0 + BATCH_QQ * L, L, o);
-        a = L0[BATCH_QA * L + o];
-    }
-    __syncthreads();
-
-    bool first = true; // Sigma is still the current buffer's, to be gathered
-    int samples = 0;
-    for (int s = 0; s < K; ++s) {
-        const DiscStep& ds = da.dsteps[in.obs_off + s];
-        const double dt = ds.dt;
-        if (dt > 0.0) {
-            ++samples;
-            // ---- a0Discrete's sensor part: the nominal evaluation and the 42 perturbed ones (wave 0); B's sensor rows and the landmark factors (the other waves)
-            if (wave == 0) {
-                if (lane <= DISC_NPERT)
-                    disc_sensor_eval(ds, lane, h, sCol, s_cpc);
-            } else {
-                for (int t = tid - 64; t < 252; t += BATCH_T - 64)
-                    sB[t] = sensor_Bs_entry(ds.ck, t);
-                for (int t = tid - 64; t < 66; t += BATCH_T - 64)
-                    lm66[t] = ds.ck.lm[t];
-            }
-            __syncthreads();
-            // ---- the sensor block: the pairs differenced
-            for (int t = tid; t < 441; t += BATCH_T) {
-                const int r = t / 21, j = t % 21;
-                sA[t] = (sCol[(2 * j) * 21 + r] - sCol[(2 * j + 1) * 21 + r]) * ih2;
-            }
-            // ---- the landmarks' rows: a lane per landmark, six of its 24 central differences per wave; wave 0 also its 3 x 3 of B
-            if (lane < Ns) {
-                const int i = lane;
-                const V3 q0 = ld3(L1, L, i);
-                const Sot3 Qi{ldq(L1 + BATCH_QQ * L, L, i), L1[BATCH_QA * L + i]};
-                const V3 qh = (1.0 / Qi.a) * q_rot(q_inv(Qi.R), q0);
-                const Pose cpc0 = s_cpc[0];
-                const Sot3 QLh_inv = sot3_inv(lift_q(cpc0, qh)); // liftVelocityDiscrete(xi_hat)^-1, landmark i
-                double* row = AL + i * DISC_SLOT;
-#pragma unroll 1
-                for (int c = 6 * wave; c < 6 * wave + 6; ++c) {
-                    V3 ep, em;
-                    if (c < 21) {
-                        ep = a0_discrete_landmark(chart, Qi, QLh_inv, s_cpc[1 + 2 * c], q0, q0);
-                        em = a0_discrete_landmark(chart, Qi, QLh_inv, s_cpc[2 + 2 * c], q0, q0);
-                    } else {
-                        const int k = c - 21;
-                        const V3 e = V3{k == 0 ? h : 0.0, k == 1 ? h : 0.0, k == 2 ? h : 0.0};
-                        ep = a0_discrete_landmark(chart, Qi, QLh_inv, cpc0, chart_bwd(chart, e, q0), q0);
-                        em = a0_discrete_landmark(chart, Qi, QLh_inv, cpc0, chart_bwd(chart, -e, q0), q0);
-                    }
-                    const V3 d = ih2 * (ep - em);
-                    row[c] = d.x;
-                    row[DISC_ROW + c] = d.y;
-                    row[2 * DISC_ROW + c] = d.z;
-                }
-                if (wave == 0) {
-                    const M3 e2i = ind ? ld_cc(L1, L, i, CC_E2I) : M3{};
-                    double al[45], bl[9];
-                    assemble_landmark<0>(lm66, chart, q0, Qi.R, Qi.a, e2i, M3{}, al, bl);
-                    for (int e = 0; e < 9; ++e)
-                        row[3 * DISC_ROW + e] = bl[e];
-                }
-            }
-            __syncthreads();
-            // ---- Sigma' = A_d Sigma A_d^T + dt (B Q B^T + P)
-            // row r of A_d applied to a vector given entry by entry (k_batch_riccati's phi_row)
-            auto ad_row = [&](int r, auto v) -> double {
-                double acc = 0.0;
-                if (r < 21) {
-                    for (int k = 0; k < 21; ++k)
-                        acc += sA[r * 21 + k] * v(k);
-                } else {
-                    const int i = (r - 21) / 3, aa = (r - 21) % 3;
-                    const double* rw = AL + i * DISC_SLOT + aa * DISC_ROW;
-                    for (int k = 0; k < 21; ++k)
-                        acc += rw[k] * v(k);
-                    for (int b = 0; b < 3; ++b)
-                        acc += rw[21 + b] * v(21 + 3 * i + b);
-                }
-                return acc;
-            };
-            auto b_entry = [&](int r, int e) -> double {
-                if (r < 21)
-                    return sB[r * 12 + e];
-                return e < 3 ? AL[((r - 21) / 3) * DISC_SLOT + 3 * DISC_ROW + ((r - 21) % 3) * 3 + e] : 0.0;
-            };
-            if constexpr (!(EQF_DISC_MEASURE_SKIP & 1)) {
-                const double* Ssrc = first ? S0 : S1;
-                for (int t = tid; t < n1 * n1; t += BATCH_T) {
-                    const int r = t % n1, c = t / n1;
-                    const double* col = Ssrc + (size_t)s_gidx[c] * ld;
-                    G[r + (size_t)c * ld] = ad_row(r, [&](int k) { return col[s_gidx[k]]; });
-                }
-                __syncthreads();
-                for (int t = tid; t < n1 * n1; t += BATCH_T) {
-                    const int r = t % n1, c = t / n1;
-                    if (r < c)
-                        continue;
-                    double v = ad_row(c, [&](int k) { return G[r + (size_t)k * ld]; });
-                    double nz = 0.0;
-                    for (int e = 0; e < 12; ++e)
-                        nz += b_entry(r, e) * s_qp[e] * b_entry(c, e);
-                    if (r == c)
-                        nz += s_qp[12 + (r < 21 ? r / 3 : 7)];
-                    v += dt * nz;
-                    S1[r + (size_t)c * ld] = v;
-                    S1[c + (size_t)r * ld] = v;
-                }
-                if (first) { // the gathered rows' readers are behind the barrier above; the next reader is behind the sample's last one
-                    for (int r = tid; r < n1; r += BATCH_T)
-                        s_gidx[r] = r;
-                    first = false;
-                }
-            }
-        }
-        // ---- this sample's observer step of the landmarks
-        if (wave == 3 && lane < Ns) {
-            observer_chain(da.steps + in.obs_off + s, 1, p0, q, a);
-            L1[BATCH_QQ * L + lane] = q.w;
-            L1[(BATCH_QQ + 1) * L + lane] = q.x;
-            L1[(BATCH_QQ + 2) * L + lane] = q.y;
-            L1[(BATCH_QQ + 3) * L + lane] = q.z;
-            L1[BATCH_QA * L + lane] = a;
-        }
-        __syncthreads();
-    }
-    if (first) // no sample moved Sigma: the gathered Sigma as it is
-        for (int t = tid; t < n1 * n1; t += BATCH_T) {
-            const int r = t % n1, c = t / n1;
-            S1[r + (size_t)c * ld] = S0[s_gidx[r] + (size_t)s_gidx[c] * ld];
-        }
-    if (tid == 0) {
-        da.out[blockIdx.x].ric_samples = samples;
-        da.out[blockIdx.x].ric_squarings = 0;
-    }
+#define EQF_BATCH_NORMAL 0
+#include "eqf_batch_discrete_body.inc"
+#undef EQF_BATCH_NORMAL
+}
+__global__ void __launch_bounds__(BATCH_T, 2) k_batch_discrete_normal(const DiscArgs da, const BatchNormalIn* nrm) {
+#define EQF_BATCH_NORMAL 1
+#include "eqf_batch_discrete_body.inc"
+#undef EQF_BATCH_NORMAL
 }
 
 // ===================================================================================================
@@ -968,7 +770,7 @@ template <bool REC> __device__ __forceinline__ void batch_nees_body(const NeesAr
     if (tid < N) {
         const int i = tid;
         const V3 pe = lm[BATCH_QA * L + i] * q_rot(ldq(lm + BATCH_QQ * L, L, i), V3{in.p[3 * i], in.p[3 * i + 1], in.p[3 * i + 2]}); // (Q_i^-1)^-1 p = a R p
-        const V3 e = point_chart(in.chart == EQVIO_COORD_INVDEPTH, pe, ld3(lm, L, i));
+        const V3 e = chart_fwd(in.chart, pe, ld3(lm, L, i)); // pointChart of the slot's chart (normal_chart under Normal)
         s_eps[21 + 3 * i] = e.x;
         s_eps[22 + 3 * i] = e.y;
         s_eps[23 + 3 * i] = e.z;

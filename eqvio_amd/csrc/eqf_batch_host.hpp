@@ -56,6 +56,7 @@ struct eqf_batch {
     BatchPacket<ObsStep> steps;
     BatchPacket<RicStep> rsteps; // eqf_batch_step_accurate: the sensor terms of A and B per sample
     BatchPacket<DiscStep> dsteps; // eqf_batch_step_discrete: the sensor terms of B, the sample and the sensor parts of xi0 and X per sample
+    BatchPacket<BatchNormalIn> nrm; // the three step calls: the sensor blocks of M and M^-1 of the Normal slots, at the entry's place in the packet
     BatchPacket<NeesIn> nin; // eqf_batch_nees, eqf_batch_consistency
     BatchPacket<NeesOut> nout;
     BatchPacket<eqf_batch_consistency_record> rec;
@@ -225,6 +226,7 @@ void eqf_batch_destroy(eqf_batch* b) {
     b->steps.release();
     b->rsteps.release();
     b->dsteps.release();
+    b->nrm.release();
     b->nin.release();
     b->nout.release();
     b->rec.release();
@@ -267,6 +269,20 @@ int eqf_batch_set_slot_settings(eqf_batch* b, int slot, const eqvio_settings* st
     return 0;
 }
 int eqf_batch_check_settings(const eqvio_settings* st) { return st ? batch_settings_check(st) : EQF_E_BAD_ARG; }
+// The chart alone, Normal included: eqf_batch_set_slot_settings's rule for a slot that holds landmarks. No device work - the chart travels in the packet entry.
+int eqf_batch_set_slot_chart(eqf_batch* b, int slot, int chart) {
+    if (!batch_slot_ok(b, slot))
+        return EQF_E_BAD_ARG;
+    if (chart != EQVIO_COORD_EUCLIDEAN && chart != EQVIO_COORD_INVDEPTH && chart != EQVIO_COORD_NORMAL)
+        return EQF_E_BAD_ARG;
+    eqf_batch::Slot& sl = b->s[slot];
+    if (chart != sl.set.coordinateChoice && !sl.ids.empty())
+        return EQF_E_BAD_ARG; // the slot's Sigma is in the old chart's coordinates
+    sl.set.coordinateChoice = chart;
+    sl.ss.chart = chart;
+    return 0;
+}
+int eqf_batch_get_slot_chart(const eqf_batch* b, int slot) { return batch_slot_ok(b, slot) ? b->s[slot].set.coordinateChoice : EQF_E_BAD_ARG; }
 int eqf_batch_get_slot_settings(const eqf_batch* b, int slot, eqvio_settings* out) {
     if (!batch_slot_ok(b, slot) || !out)
         return EQF_E_BAD_ARG;
@@ -390,6 +406,73 @@ namespace {
 // useDiscreteStateMatrix == true - what rides along per sample is the sensor terms of B, the sample and the sensor parts of xi0 and X (DiscStep), and
 // k_batch_discrete runs in k_batch_riccati's place. (A template parameter: the fast instance is the function it was.)
 enum { STEP_FAST, STEP_ACCURATE, STEP_DISCRETE };
+// The sensor blocks of M and M^-1 of a Normal slot, as normal_congruence (eqf_hip.hip) fills them for a context: xi0's velocity and Ad(T0^-1) of its camera
+// offset. dtP: dt P for the closing congruence of the fast step; null for the per-sample modes, which add their noise in Euclidean coordinates.
+void batch_normal_pack(const SensorState& xi0, const double* dtP, BatchNormalIn& nb) {
+    NormalM nm{};
+    nm.v0[0] = xi0.vel.x, nm.v0[1] = xi0.vel.y, nm.v0[2] = xi0.vel.z;
+    const M6 Ad = se3_Adjoint(pose_inv(xi0.cam));
+    for (int e = 0; e < 36; ++e)
+        nm.Ad[e] = Ad.a[e];
+    nm.dir = -1;
+    nb.inv = nm;
+    nm.dir = +1;
+    nm.addP = dtP ? 1 : 0;
+    for (int k = 0; k < 8; ++k)
+        nm.dtP[k] = dtP ? dtP[k] : 0.0;
+    nb.fwd = nm;
+}
+// A step that lists Normal slots: their packet entries move behind the others' (both groups keep their order), scr.in_of follows, and every Normal entry gets its
+// BatchNormalIn at its place in b->nrm, sent ahead on the batch's stream. nE: the entries in front. Functions of their own (noinline), so that a step without a
+// Normal slot runs the host code it always ran.
+__attribute__((noinline)) int batch_normal_partition(eqf_batch* b, BatchScreen& scr, int count, int nin, bool fast, int& nE) {
+    std::vector<int> pos(nin);
+    int nn = 0;
+    for (int i = 0; i < nin; ++i)
+        nn += b->in.h[i].ss.chart == EQVIO_COORD_NORMAL;
+    nE = nin - nn;
+    int ie = 0, in_ = nE;
+    bool moved = false;
+    for (int i = 0; i < nin; ++i) {
+        pos[i] = b->in.h[i].ss.chart == EQVIO_COORD_NORMAL ? in_++ : ie++;
+        moved = moved || pos[i] != i;
+    }
+    if (moved) {
+        const std::vector<BatchIn> held(b->in.h, b->in.h + nin);
+        for (int i = 0; i < nin; ++i)
+            b->in.h[pos[i]] = held[i];
+        for (int e = 0; e < count; ++e)
+            if (scr.in_of[e] >= 0)
+                scr.in_of[e] = pos[scr.in_of[e]];
+    }
+    if (int rc = b->nrm.grow(std::max(count, 64)))
+        return rc;
+    for (int i = nE; i < nin; ++i) {
+        const BatchIn& in = b->in.h[i];
+        const eqf_batch::Slot& sl = b->s[in.slot];
+        double dtP[8];
+        for (int k = 0; k < 8; ++k)
+            dtP[k] = in.dt * sl.ss.Pd[k];
+        batch_normal_pack(sl.xi0, fast ? dtP : nullptr, b->nrm.h[i]);
+    }
+    HIPCHK(hipMemcpyAsync(b->nrm.d + nE, b->nrm.h + nE, sizeof(BatchNormalIn) * nn, hipMemcpyHostToDevice, b->stream));
+    return 0;
+}
+// the propagation of the Normal entries [nE, nE + nN) of a step's packet; the fast step's also their k_batch_frame_tail (the per-sample modes run one tail over all entries)
+__attribute__((noinline)) void batch_launch_normal(eqf_batch* b, int mode, int nE, int nN) {
+    const BatchNormalIn* nrm = b->nrm.d + nE;
+    const BatchArgs ban{b->buf, b->in.d + nE, b->steps.d, b->out.d + nE};
+    if (mode == STEP_ACCURATE) {
+        const RicArgs ran{b->buf, b->in.d + nE, b->steps.d, b->rsteps.d, b->out.d + nE};
+        hipLaunchKernelGGL(k_batch_riccati_normal, dim3(nN), dim3(BATCH_T), 0, b->stream, ran, nrm);
+    } else if (mode == STEP_DISCRETE) {
+        const DiscArgs dan{b->buf, b->in.d + nE, b->steps.d, b->dsteps.d, b->out.d + nE};
+        hipLaunchKernelGGL(k_batch_discrete_normal, dim3(nN), dim3(BATCH_T), 0, b->stream, dan, nrm);
+    } else {
+        hipLaunchKernelGGL(k_batch_normal, dim3(nN), dim3(BATCH_T), 0, b->stream, ban, nrm);
+        hipLaunchKernelGGL(k_batch_frame_tail, dim3(nN), dim3(BATCH_T), 0, b->stream, ban);
+    }
+}
 template <int mode> int batch_step(eqf_batch* b, int count, const eqf_batch_frame* frames, int* status) {
     if (!b || count < 0 || (count > 0 && (!frames || !status)))
         return EQF_E_BAD_ARG;
@@ -417,7 +500,7 @@ template <int mode> int batch_step(eqf_batch* b, int count, const eqf_batch_fram
     std::vector<GroupSensor> X_after(count);
     std::vector<std::vector<int>> surv_ids(count), new_ids(count);
     std::vector<int> removed_old(count, 0);
-    int nsteps = 0;
+    int nsteps = 0, n_normal = 0;
     for (int e = 0; e < count; ++e) {
         const eqf_batch_frame& f = frames[e];
         status[e] = 0;
@@ -513,12 +596,20 @@ template <int mode> int batch_step(eqf_batch* b, int count, const eqf_batch_fram
         for (int i : surv)
             surv_ids[e].push_back(sl.ids[i]);
         removed_old[e] = (int)surv.size() < N0;
+        n_normal += sl.ss.chart == EQVIO_COORD_NORMAL;
         scr.list(f.slot);
         scr.accept(e);
     }
     const int nin = scr.nin;
     if (nin == 0)
         return 0;
+    // The Normal slots' entries go behind the others' in the packet: entries [0, nE) are launched with the other charts' propagation, [nE, nin) with the Normal
+    // chart's, each on its part of the packet. A step without a Normal slot packs and launches what it always did.
+    int nE = nin;
+    if (n_normal > 0)
+        if (int rc = batch_normal_partition(b, scr, count, nin, !accurate, nE))
+            return rc;
+    const int nN = nin - nE;
     const BatchArgs ba{b->buf, b->in.d, b->steps.d, b->out.d};
     if (nsteps) // the observer steps ride along, in front of the launch on the same stream
         HIPCHK(hipMemcpyAsync(b->steps.d, b->steps.h, sizeof(ObsStep) * nsteps, hipMemcpyHostToDevice, b->stream));
@@ -530,13 +621,22 @@ template <int mode> int batch_step(eqf_batch* b, int count, const eqf_batch_fram
     const DiscArgs da{b->buf, b->in.d, b->steps.d, b->dsteps.d, b->out.d};
     const auto launch = [&] {
         if (mode == STEP_ACCURATE) {
-            hipLaunchKernelGGL(k_batch_riccati, dim3(nin), dim3(BATCH_T), 0, b->stream, ra);
+            if (nE)
+                hipLaunchKernelGGL(k_batch_riccati, dim3(nE), dim3(BATCH_T), 0, b->stream, ra);
+            if (nN)
+                batch_launch_normal(b, mode, nE, nN);
             hipLaunchKernelGGL(k_batch_frame_tail, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
         } else if (mode == STEP_DISCRETE) {
-            hipLaunchKernelGGL(k_batch_discrete, dim3(nin), dim3(BATCH_T), 0, b->stream, da);
+            if (nE)
+                hipLaunchKernelGGL(k_batch_discrete, dim3(nE), dim3(BATCH_T), 0, b->stream, da);
+            if (nN)
+                batch_launch_normal(b, mode, nE, nN);
             hipLaunchKernelGGL(k_batch_frame_tail, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
         } else {
-            hipLaunchKernelGGL(k_batch_frame, dim3(nin), dim3(BATCH_T), 0, b->stream, ba);
+            if (nE)
+                hipLaunchKernelGGL(k_batch_frame, dim3(nE), dim3(BATCH_T), 0, b->stream, ba);
+            if (nN)
+                batch_launch_normal(b, mode, nE, nN);
         }
     };
     if (int rc = batch_round_trip(b, b->in, nin, launch, &b->out))

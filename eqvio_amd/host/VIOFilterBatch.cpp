@@ -157,6 +157,21 @@ int VIOFilterBatch::callOf(int k) const { // integrateUpToTime's choice (src/VIO
     return riccati_[k] != EQVIO_BATCH_RICCATI_ACCURATE ? 0 : stateMatrix_[k] == EQVIO_BATCH_STATE_MATRIX_DISCRETE ? 2 : 1;
 }
 int VIOFilterBatch::stateMatrix(int k) const { return k >= 0 && k < (int)slotv.size() ? stateMatrix_[k] : EQF_E_BAD_ARG; }
+int VIOFilterBatch::groupOf(int k) const { return 2 * callOf(k) + (eqf_batch_get_slot_chart(batch, k) == EQVIO_COORD_NORMAL ? 1 : 0); }
+int VIOFilterBatch::setChart(int k, int chart) {
+    if (k >= (int)slotv.size() || (chart != EQVIO_COORD_EUCLIDEAN && chart != EQVIO_COORD_INVDEPTH && chart != EQVIO_COORD_NORMAL))
+        return EQF_E_BAD_ARG;
+    if (k >= 0)
+        return eqf_batch_set_slot_chart(batch, k, chart);
+    for (int j = 0; j < (int)slotv.size(); ++j) // every slot, or none: the one refusal left is a slot with landmarks under another chart
+        if (eqf_batch_get_slot_chart(batch, j) != chart && eqf_batch_num_landmarks(batch, j) > 0)
+            return EQF_E_BAD_ARG;
+    for (int j = 0; j < (int)slotv.size(); ++j)
+        if (const int rc = eqf_batch_set_slot_chart(batch, j, chart))
+            return rc;
+    return 0;
+}
+int VIOFilterBatch::chart(int k) const { return eqf_batch_get_slot_chart(batch, k); }
 VIOFilterBatch::InnovationTotals VIOFilterBatch::innovationTotals(int k) const {
     InnovationTotals t;
     check(eqf_batch_innovation_totals(batch, k, &t.updates, &t.dof, &t.nis, &t.logdet), "eqf_batch_innovation_totals");
@@ -304,7 +319,8 @@ void VIOFilterBatch::stepPrepared(const int* slots, const double* stamps, int* s
         frames_[t].dt_k = dts_[t].data();
     }
     st_.resize(frames_.size());
-    // every listed slot to the call of its mode, in the order fast, accurate, discrete: a step whose slots agree is one device call, a mixed step up to three
+    // every listed slot to the call of its mode, in the order fast, accurate, discrete, and within a mode the Normal-chart slots behind the others: one device
+    // call per (mode, Normal or not) group that is present - a step whose slots agree is one device call
     const auto call = [&](int which, int n, const eqf_batch_frame* fr, int* st) {
         if (which == 2)
             check(eqf_batch_step_discrete(batch, n, fr, st), "eqf_batch_step_discrete");
@@ -314,16 +330,18 @@ void VIOFilterBatch::stepPrepared(const int* slots, const double* stamps, int* s
             check(eqf_batch_step(batch, n, fr, st), "eqf_batch_step");
     };
     bool mixed = false;
-    for (size_t t = 1; t < frames_.size(); ++t)
-        mixed = mixed || callOf(frames_[t].slot) != callOf(frames_[0].slot);
+    const int group0 = groupOf(frames_[0].slot);
+    for (size_t t = 1; t < frames_.size() && !mixed; ++t)
+        mixed = groupOf(frames_[t].slot) != group0;
     if (!mixed) {
         call(callOf(frames_[0].slot), (int)frames_.size(), frames_.data(), st_.data());
     } else {
         std::vector<int> pst;
-        for (const int which : {0, 1, 2}) {
+        for (int group = 0; group < 6; ++group) {
+            const int which = group / 2;
             part_.clear(), partOf_.clear();
             for (size_t t = 0; t < frames_.size(); ++t)
-                if (callOf(frames_[t].slot) == which) {
+                if (groupOf(frames_[t].slot) == group) {
                     part_.push_back(frames_[t]);
                     partOf_.push_back(t);
                 }
@@ -517,6 +535,8 @@ int eqvio_batch_set_slot_riccati(eqvio_batch* b, int slot, int mode) { return b 
 int eqvio_batch_get_slot_riccati(const eqvio_batch* b, int slot) { return b ? b->f->riccatiMode(slot) : EQF_E_BAD_ARG; }
 int eqvio_batch_set_slot_state_matrix(eqvio_batch* b, int slot, int kind) { return b ? b->f->setStateMatrix(slot, kind) : EQF_E_BAD_ARG; }
 int eqvio_batch_get_slot_state_matrix(const eqvio_batch* b, int slot) { return b ? b->f->stateMatrix(slot) : EQF_E_BAD_ARG; }
+int eqvio_batch_set_slot_chart(eqvio_batch* b, int slot, int chart) { return b ? b->f->setChart(slot, chart) : EQF_E_BAD_ARG; }
+int eqvio_batch_get_slot_chart(const eqvio_batch* b, int slot) { return b ? b->f->chart(slot) : EQF_E_BAD_ARG; }
 int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out) {
     return b ? eqf_batch_get_slot_settings(b->f->core(), slot, out) : EQF_E_BAD_ARG;
 }

@@ -61,6 +61,11 @@ class VIOFilterBatch {
     // (every slot starts with it) or _DISCRETE (eqf_batch_step_discrete). A fast slot ignores it. Kept and refused like the Riccati mode.
     int setStateMatrix(int slot, int kind);
     int stateMatrix(int slot) const;
+    // The slot's coordinate chart on its own, the Normal chart included (eqf_batch_set_slot_chart, include/eqf_batch.h: the chart is the device layer's, kept
+    // nowhere else). slot < 0: every slot - then nothing changes unless every slot takes the chart. Returns 0 or EQF_E_BAD_ARG (a chart outside the enum, a bad
+    // slot, or a slot that holds landmarks under another chart); chart returns the slot's chart or EQF_E_BAD_ARG.
+    int setChart(int slot, int chart);
+    int chart(int slot) const;
     // Entry e: slot dst[e] becomes slot src[e] as it was before the call - the EqF state on the device (eqf_batch_copy_slots: one launch, same status codes)
     // and the host half: IMU buffer, current time, initialised flag. The destination keeps its settings and innovation totals. A refused entry changes nothing.
     void copySlots(int count, const int* src, const int* dst, int* status);
@@ -112,6 +117,8 @@ class VIOFilterBatch {
     std::vector<int> stateMatrix_; // per slot: EQVIO_BATCH_STATE_MATRIX_*
     // the device call slot k's frames go to: 0 eqf_batch_step, 1 eqf_batch_step_accurate, 2 eqf_batch_step_discrete
     int callOf(int k) const;
+    // the group of a step slot k's frame goes in: 2 callOf(k) + (the slot's chart is Normal) - one device call per group that is present
+    int groupOf(int k) const;
     std::vector<eqf_batch_frame> part_; // stepPrepared: the frames of one mode
     std::vector<size_t> partOf_;
 };

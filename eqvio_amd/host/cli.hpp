@@ -198,6 +198,34 @@ inline const char* batchRiccatiName(int mode) { return mode == BATCH_CLI_DISCRET
 inline int batchCliRiccati(int mode) { return mode == EQVIO_BATCH_RICCATI_FAST ? EQVIO_BATCH_RICCATI_FAST : EQVIO_BATCH_RICCATI_ACCURATE; }
 inline int batchCliStateMatrix(int mode) { return mode == BATCH_CLI_DISCRETE ? EQVIO_BATCH_STATE_MATRIX_DISCRETE : EQVIO_BATCH_STATE_MATRIX_CONTINUOUS; }
 
+// --batchChart C[,C...] with --batch B: the slots' coordinate chart (eqvio_batch_set_slot_chart), C = euclidean | invdepth | normal; one value for every slot, or
+// B values, one per slot. The one way to the Normal chart in a batch: --coordinateChoice Normal and --sweep coordinateChoice=...,Normal stay refused, as the
+// settings calls refuse it. Returns what the flag is refused for, before any file or device is opened (empty: nothing); charts then holds B entries.
+inline std::string batchChartRefusal(const std::string& text, int B, std::vector<int>& charts) {
+    if (B == 0)
+        return "--batchChart needs --batch B (the chart is the filter batch's, per slot)";
+    std::vector<int> given;
+    for (size_t p = 0; p <= text.size();) {
+        const size_t c = std::min(text.find(',', p), text.size());
+        const std::string w = text.substr(p, c - p);
+        if (w != "euclidean" && w != "invdepth" && w != "normal")
+            return "--batchChart: '" + w + "' is neither euclidean nor invdepth nor normal";
+        given.push_back(w == "normal" ? EQVIO_COORD_NORMAL : w == "invdepth" ? EQVIO_COORD_INVDEPTH : EQVIO_COORD_EUCLIDEAN);
+        p = c + 1;
+    }
+    if (given.size() != 1 && (int)given.size() != B)
+        return "--batchChart has " + std::to_string(given.size()) + " values for --batch " + std::to_string(B) + ": one value, or one per slot";
+    charts.assign(std::max(B, 0), given[0]);
+    for (int k = 0; k < B && given.size() > 1; ++k)
+        charts[k] = given[k];
+    return "";
+}
+// --batchChart beside a sweep of the chart itself: two flags would name the slots' charts, and the later call would silently win
+inline std::string batchChartSweepRefusal(const Sweep& sw) {
+    return sw.name == "coordinateChoice" ? "--batchChart with --sweep coordinateChoice: both name the slots' charts; give one of them" : "";
+}
+inline const char* batchChartName(int chart) { return chart == EQVIO_COORD_NORMAL ? "normal" : chart == EQVIO_COORD_INVDEPTH ? "invdepth" : "euclidean"; }
+
 // the filter settings as the C-ABI's eqvio_settings
 inline eqvio_settings batchSettings(const VIOFilter::Settings& fs) {
     eqvio_settings es;

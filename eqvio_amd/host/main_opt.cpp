@@ -34,7 +34,8 @@ static void usage() {
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
               "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]\n"
               "                 [--nis]\n"
-              "                            [--batchRiccati fast|accurate|discrete[,...]]]\n"
+              "                            [--batchRiccati fast|accurate|discrete[,...]]\n"
+              "                            [--batchChart euclidean|invdepth|normal[,...]]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
@@ -61,12 +62,17 @@ static void usage() {
               "  --batchRiccati M[,M...]   with --batch B: the slots' propagation, M = fast (one fast Riccati step per frame), accurate (the reference's default,\n"
               "              fastRiccati: false: one accurate Riccati step per IMU sample) or discrete (accurate with the discrete state matrix,\n"
               "              useDiscreteStateMatrix: true); one value for every slot, or B values, one per slot. With this flag\n"
-              "              --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each slot's lines name its mode.");
+              "              --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each slot's lines name its mode.\n"
+              "  --batchChart C[,C...]   with --batch B: the slots' coordinate chart, C = euclidean, invdepth or normal (the reference's third chart, which\n"
+              "              --coordinateChoice and --sweep coordinateChoice=... do not take with --batch); one value for every slot, or B values, one per slot.\n"
+              "              Combines with --batchRiccati and --sweep, not with --warmup F > 0 (the chart cannot change under a filter that holds landmarks).\n"
+              "              Each slot's lines name its chart.");
 }
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
 static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime,
-                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions, bool warmupOnFilter, const std::vector<int>& riccati) {
+                    const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions, bool warmupOnFilter, const std::vector<int>& riccati,
+                    const std::vector<int>& charts) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -78,7 +84,8 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     for (int k = 0; k < B && !riccati.empty(); ++k) // kept through the warm-up's copies, like the settings
         check_rc(filters.setRiccatiMode(k, batchCliRiccati(riccati[k])), "--batchRiccati"), check_rc(filters.setStateMatrix(k, batchCliStateMatrix(riccati[k])), "--batchRiccati");
     auto label = [&](int k) {
-        return (swept ? " " + sweep.name + "=" + sweep.values[k] : std::string()) + (riccati.empty() ? std::string() : std::string(" riccati ") + batchRiccatiName(riccati[k]));
+        return (swept ? " " + sweep.name + "=" + sweep.values[k] : std::string()) + (riccati.empty() ? std::string() : std::string(" riccati ") + batchRiccatiName(riccati[k])) +
+               (charts.empty() ? std::string() : std::string(" chart ") + batchChartName(charts[k]));
     };
     // --warmupOnFilter: the warm-up's frames run here, on the context path, and no slot runs before the branch
     std::unique_ptr<VIOFilter> warm;
@@ -139,6 +146,8 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
     };
     if (warmup == 0)
         applySweep();
+    for (int k = 0; k < B && !charts.empty(); ++k) // behind the sweep's settings, which carry a chart of their own; no slot holds a landmark yet
+        check_rc(filters.setChart(k, charts[k]), "--batchChart");
     std::vector<int> slots(B), status(B), failed(B, 0);
     for (int k = 0; k < B; ++k)
         slots[k] = k;
@@ -258,9 +267,9 @@ int main(int argc, char** argv) {
     double cameraLag = 0, startTime = -1, stopTime = -1;
     bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false, nisLine = false;
     int batch = 0;
-    std::string warmupText, riccatiText;
-    bool haveRiccati = false;
-    std::vector<int> riccati;
+    std::string warmupText, riccatiText, chartText;
+    bool haveRiccati = false, haveChart = false;
+    std::vector<int> riccati, charts;
     Sweep sweep;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -320,6 +329,9 @@ int main(int argc, char** argv) {
             else if (a == "--batchRiccati") {
                 riccatiText = val();
                 haveRiccati = true;
+            } else if (a == "--batchChart") {
+                chartText = val();
+                haveChart = true;
             }
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
@@ -359,6 +371,13 @@ int main(int argc, char** argv) {
             }
             fs.fastRiccati = true; // the batch's settings describe eqf_batch_step; the modes go to the slots
         }
+        if (haveChart) { // before any file or device is opened
+            const std::string refusal = batchChartRefusal(chartText, batch < 0 ? 0 : batch, charts);
+            if (!refusal.empty()) {
+                std::fprintf(stderr, "eqvio_opt: %s\n", refusal.c_str());
+                return 2;
+            }
+        }
         int warmup = 0;
         if (haveWarmup) { // before any file or device is opened, as the refusals of --batch
             char* end = nullptr;
@@ -389,6 +408,10 @@ int main(int argc, char** argv) {
                 why = sweepRefusal(sweep, batch, batchSettings(fs));
             if (why.empty() && warmup > 0)
                 why = warmupSweepRefusal(sweep);
+            if (why.empty() && haveSweep && haveChart)
+                why = batchChartSweepRefusal(sweep);
+            if (why.empty() && warmup > 0 && haveChart)
+                why = "--warmup with --batchChart: the chart cannot change under a filter that holds landmarks";
             if (!why.empty()) {
                 std::fprintf(stderr, "eqvio_opt: --batch %d: %s\n", batch, why.c_str());
                 return 2;
@@ -438,7 +461,7 @@ int main(int argc, char** argv) {
             std::vector<StampedPose> gt;
             if (!gtName.empty())
                 gt = TrackReplayServer::groundtruth(gtName, format);
-            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter, riccati);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter, riccati, charts);
         }
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150

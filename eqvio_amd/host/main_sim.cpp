@@ -23,6 +23,7 @@ static void usage() {
               "                 [--maxFeatures M] [--seed S] [--imuFreq HZ] [--imageFreq HZ] [--initialNoise] [--inputNoise] [--outputNoise]\n"
               "                 [--fullState] [--landmarkReset S] [--output DIR] [--writeDataset DIR] [--sigmaFP32] [--quiet] [--batch B]\n"
               "                 [--sweep NAME=v0,v1,...] [--innovation] [--nis] [--record DIR] [--batchRiccati fast|accurate|discrete[,...]]\n"
+              "                 [--batchChart euclidean|invdepth|normal[,...]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   runs the seeds --seed .. --seed + B - 1 as B slots of one filter batch (include/eqvio_batch.h) and prints each run's mean\n"
               "              NEES and their mean. The batch needs fast Riccati, which is not the default: give --fastRiccati 1 (the setting of the\n"
@@ -42,12 +43,15 @@ static void usage() {
               "  --batchRiccati M[,M...]   with --batch B: the runs' propagation, M = fast (one fast Riccati step per frame), accurate (the reference's\n"
               "              default, fastRiccati: false: one accurate Riccati step per IMU sample) or discrete (accurate with the discrete state matrix,\n"
               "              useDiscreteStateMatrix: true); one value for every run, or B values, one per run.\n"
-              "              With this flag --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each run's line names its mode.");
+              "              With this flag --fastRiccati 1 need not be given: the tool hands the batch that setting itself. Each run's line names its mode.\n"
+              "  --batchChart C[,C...]   with --batch B: the runs' coordinate chart, C = euclidean, invdepth or normal (the reference's third chart, which\n"
+              "              --coordinateChoice and --sweep coordinateChoice=... do not take with --batch); one value for every run, or B values, one per run.\n"
+              "              Combines with --batchRiccati and --sweep. Each run's line names its chart.");
 }
 
 // --batch B: the default-mode loop of main() for B seeds in lockstep, through eqvio_batch_run_sim (augment, vision step and NEES: one launch each per frame)
 static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B, bool quiet, const Sweep& sweep, bool innovation, const std::string& recordDir,
-                    const std::vector<int>& riccati) {
+                    const std::vector<int>& riccati, const std::vector<int>& charts) {
     const bool swept = !sweep.name.empty();
     eqvio_sim_settings ss;
     eqvio_sim_default_settings(&ss);
@@ -103,6 +107,13 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
             release();
             return 1;
         }
+    for (int k = 0; k < B && !charts.empty(); ++k) // behind the sweep's settings, which carry a chart of their own; the slots hold no landmark yet
+        if ((rc = eqvio_batch_set_slot_chart(b, k, charts[k]))) {
+            std::fprintf(stderr, "eqvio_sim: --batchChart: slot %d: %s\n", k, eqf_error_string(rc));
+            eqvio_batch_destroy(b);
+            release();
+            return 1;
+        }
     const int maxFrames = (int)std::ceil(sim.duration * sim.imageFreq) + 2;
     std::vector<double> nees((size_t)maxFrames * B);
     int frames = 0;
@@ -127,7 +138,8 @@ static int runBatch(const SimSettings& sim, const VIOFilter::Settings& fs, int B
         }
         const double mean = s / std::max(n, 1);
         sumOfMeans += mean;
-        const std::string mode = riccati.empty() ? "" : std::string(" riccati ") + batchRiccatiName(riccati[k]);
+        const std::string mode = (riccati.empty() ? std::string() : std::string(" riccati ") + batchRiccatiName(riccati[k])) +
+                                 (charts.empty() ? std::string() : std::string(" chart ") + batchChartName(charts[k]));
         if (swept)
             std::printf("run %d seed %u %s=%s%s: mean NEES %.9g over %d frames\n", k, sim.randomSeed, sweep.name.c_str(), sweep.values[k].c_str(), mode.c_str(), mean, n);
         else
@@ -155,9 +167,9 @@ int main(int argc, char** argv) {
     int batch = 0;
     Sweep sweep;
     bool haveSweep = false;
-    std::string outputDir, datasetDir, recordDir, riccatiText;
-    bool haveRiccati = false;
-    std::vector<int> riccati;
+    std::string outputDir, datasetDir, recordDir, riccatiText, chartText;
+    bool haveRiccati = false, haveChart = false;
+    std::vector<int> riccati, charts;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         std::function<const char*()> val = [&]() -> const char* {
@@ -193,6 +205,10 @@ int main(int argc, char** argv) {
             riccatiText = val();
             haveRiccati = true;
         }
+        else if (a == "--batchChart") {
+            chartText = val();
+            haveChart = true;
+        }
         else if (a == "--sweep") {
             sweep = parseSweep(val());
             haveSweep = true;
@@ -227,6 +243,13 @@ int main(int argc, char** argv) {
         }
         fs.fastRiccati = true; // the batch's settings describe eqf_batch_step; the modes go to the slots
     }
+    if (haveChart) { // before any device is opened
+        const std::string refusal = batchChartRefusal(chartText, batch < 0 ? 0 : batch, charts);
+        if (!refusal.empty()) {
+            std::fprintf(stderr, "eqvio_sim: %s\n", refusal.c_str());
+            return 2;
+        }
+    }
     if (batch != 0) { // what the filter batch refuses, before any device is opened
         const char* why = batch < 1 ? "--batch needs B >= 1"
                           : !fs.fastRiccati ? "--batch needs --fastRiccati 1 (the batch has fast Riccati only; the default is 0)"
@@ -243,13 +266,15 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (haveSweep) {
-            const std::string refusal = sweepRefusal(sweep, batch, batchSettings(fs));
+            std::string refusal = sweepRefusal(sweep, batch, batchSettings(fs));
+            if (refusal.empty() && haveChart)
+                refusal = batchChartSweepRefusal(sweep);
             if (!refusal.empty()) {
                 std::fprintf(stderr, "eqvio_sim: %s\n", refusal.c_str());
                 return 2;
             }
         }
-        return runBatch(sim, fs, batch, quiet, sweep, innovation, recordDir, riccati);
+        return runBatch(sim, fs, batch, quiet, sweep, innovation, recordDir, riccati, charts);
     }
     double lastLandmarkReset = landmarkResetTime > 0 ? 0.0 : std::nan("");
 

@@ -7,8 +7,10 @@
  * per sample in the same places -, removeOldLandmarks (settings.removeLostLandmarks), removeOutliers, addNewLandmarks (median or fixed depth),
  * performVisionUpdate and removeInvalidLandmarks. Its state is the one eqf_hip.h's context holds (xi0, X, Sigma; same flat layouts, eqvio_types.h).
  * The sensor-level work (the 46 doubles of xi0 / X, the terms of A and B, the observer steps' sensor part, the sensor lift) is done on the host, the
- * rest by the slot's workgroup. Only the Normal chart is not available. Settings with fastRiccati == 0 are still refused (EQF_E_UNSUPPORTED at creation), and the
+ * rest by the slot's workgroup. All three coordinate charts are available: Euclidean and InvDepth through the settings, Normal through a call of its own
+ * (eqf_batch_set_slot_chart) - settings that name the Normal chart are still refused, as settings with fastRiccati == 0 are (EQF_E_UNSUPPORTED at creation). The
  * useDiscreteStateMatrix field of eqvio_settings is not read: the accurate and the discrete mode are calls of their own, not settings.
+ * What remains refused of the Normal chart is the bridge to a context: eqf_batch_load_ctx / eqf_batch_store_ctx refuse a Normal-chart context.
  *
  * Return codes are eqf_hip.h's. Argument and settings checks come BEFORE the device is looked at: a call with bad arguments returns EQF_E_BAD_ARG /
  * EQF_E_UNSUPPORTED on a machine without a GPU as well; with valid arguments and no gfx950 device, eqf_batch_create returns EQF_E_NO_DEVICE.
@@ -51,7 +53,7 @@ enum {
     EQF_BATCH_REMOVED_INVALID = 32
 };
 
-/* slots >= 1, 1 <= max_landmarks <= 64; settings: fastRiccati must be 1 and the chart Euclidean or InvDepth. Every slot starts with these settings and
+/* slots >= 1, 1 <= max_landmarks <= 64; settings: fastRiccati must be 1 and the chart Euclidean or InvDepth (Normal: eqf_batch_set_slot_chart). Every slot starts with these settings and
  * keeps them until eqf_batch_set_slot_settings gives it its own: gains, thresholds, depth, lift choices and chart are per slot, so one step can run B
  * different tunings. Every slot starts with no landmark, Sigma = 0 and xi0 = X = identity (set them with eqf_batch_set_state / _set_sigma). */
 int eqf_batch_create(eqf_batch** out, int device, int slots, int max_landmarks, const eqvio_settings* s);
@@ -74,6 +76,24 @@ int eqf_batch_get_slot_settings(const eqf_batch* b, int slot, eqvio_settings* ou
 /* What eqf_batch_create and eqf_batch_set_slot_settings make of these settings on their own: 0, EQF_E_BAD_ARG (null, or a coordinateChoice outside the enum)
  * or EQF_E_UNSUPPORTED (fastRiccati == 0 or the Normal chart). Looks at no device and no batch: a caller can refuse a whole list of settings up front. */
 int eqf_batch_check_settings(const eqvio_settings* s);
+
+/* The slot's coordinate chart on its own: EQVIO_COORD_EUCLIDEAN, EQVIO_COORD_INVDEPTH or EQVIO_COORD_NORMAL - the one way to the Normal chart, which the settings
+ * calls above refuse. From the slot's next call on every step mode (eqf_batch_step, _step_accurate, _step_discrete), eqf_batch_nees / _consistency,
+ * eqf_batch_predictions and the rest run the slot under that chart: its Sigma is then expressed in that chart's coordinates. A Normal slot's propagation is
+ * the Euclidean one between two congruences with the chart's change of coordinates M (coordinateSuite/normal.cpp; k_batch_normal, k_batch_riccati_normal,
+ * k_batch_discrete_normal), the rest of its frame the kernel every slot runs. One step may list slots of all three charts: one packet, one copy back and one
+ * synchronisation as before, the Normal slots' propagation in launches of its own on the same stream; a slot gives the same bits whatever its neighbours' charts.
+ * The call launches nothing and does not synchronise: the chart travels in the slot's packet entry like the other settings. Refusals, checked in this order
+ * and before any device is looked at, the slot then untouched bit for bit:
+ *   EQF_E_BAD_ARG      null batch or bad slot index; a chart outside the enum; a chart other than the slot's while the slot holds landmarks
+ *                      (eqf_batch_set_slot_settings's rule). The slot's own chart is accepted on a slot with landmarks and does nothing.
+ * eqf_batch_get_slot_settings then reports the chart in coordinateChoice; a later accepted eqf_batch_set_slot_settings replaces it with its own (under the same
+ * rule; Normal still refused there); eqf_batch_copy_slots and the bridge apply their chart rules to it as to the other two - a Normal slot with landmarks copies
+ * into Normal slots only, and eqf_batch_store_ctx of it into a Euclidean or InvDepth context is the chart mismatch EQF_E_BAD_ARG. Moving a filter between a
+ * Normal-chart CONTEXT and Normal slots is not built: eqf_batch_load_ctx / _store_ctx refuse such a context (EQF_E_UNSUPPORTED) as before.
+ * get returns the slot's chart, or EQF_E_BAD_ARG (< 0) for a null batch or a bad slot. */
+int eqf_batch_set_slot_chart(eqf_batch* b, int slot, int chart);
+int eqf_batch_get_slot_chart(const eqf_batch* b, int slot);
 
 /* The slot's xi0 / X / landmarks (eqf_set_state's layout: ids, q0 3 and Q 5 doubles per landmark). N <= max_landmarks. Sigma is NOT changed by set_state:
  * set it afterwards with eqf_batch_set_sigma (n = 21 + 3 N). get_state returns N or < 0. */

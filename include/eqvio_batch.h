@@ -54,6 +54,16 @@ int eqvio_batch_get_slot_riccati(const eqvio_batch* b, int slot);     /* mode, o
 enum { EQVIO_BATCH_STATE_MATRIX_CONTINUOUS = 0, EQVIO_BATCH_STATE_MATRIX_DISCRETE = 1 };
 int eqvio_batch_set_slot_state_matrix(eqvio_batch* b, int slot, int kind); /* slot < 0: every slot */
 int eqvio_batch_get_slot_state_matrix(const eqvio_batch* b, int slot);     /* kind, or EQF_E_BAD_ARG */
+/* The slot's coordinate chart on its own: EQVIO_COORD_EUCLIDEAN, EQVIO_COORD_INVDEPTH or EQVIO_COORD_NORMAL (eqf_batch_set_slot_chart, include/eqf_batch.h) -
+ * the way to the reference's third chart, which eqvio_batch_create and eqvio_batch_set_slot_settings keep refusing in the settings. From the slot's next frame
+ * on; eqvio_batch_get_slot_settings then reports it in coordinateChoice, and a later accepted eqvio_batch_set_slot_settings replaces it with its own. A step
+ * whose slots mix charts and modes makes one device call per (mode, Normal or not) group that is present, in the order fast, accurate, discrete and the Normal
+ * slots of a mode behind its others. set: slot < 0 means every slot, and then nothing changes unless every slot takes the chart; a chart outside the enum, a
+ * slot index past the last slot, a null batch, or a slot that holds landmarks under another chart (its Sigma is in that chart's coordinates) gives
+ * EQF_E_BAD_ARG, nothing changed, no device looked at. get returns the chart, or EQF_E_BAD_ARG. eqvio_batch_load_filter / _store_filter keep refusing a
+ * Normal-chart filter (eqf_batch_load_ctx / _store_ctx). */
+int eqvio_batch_set_slot_chart(eqvio_batch* b, int slot, int chart); /* slot < 0: every slot */
+int eqvio_batch_get_slot_chart(const eqvio_batch* b, int slot);     /* chart, or EQF_E_BAD_ARG */
 /* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56), with the slot's settings */
 int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time);
 void eqvio_batch_destroy(eqvio_batch* b);
