@@ -127,6 +127,7 @@ def load_batch_protos():
         "eqf_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqf_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
         "eqf_batch_copy_slots": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
+        "eqf_batch_convert_chart": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
         "eqf_batch_load_ctx": (C.c_int, [vp, vp, C.c_int, c_int_p, c_int_p]),
         "eqf_batch_store_ctx": (C.c_int, [vp, C.c_int, vp]),
     }
@@ -167,6 +168,7 @@ def load_batch_protos():
         "eqvio_batch_innovation_totals": (C.c_int, [vp, C.c_int, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqvio_batch_reset_innovation_totals": (C.c_int, [vp, C.c_int]),
         "eqvio_batch_copy_slots": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
+        "eqvio_batch_convert_chart": (C.c_int, [vp, C.c_int, c_int_p, c_int_p, c_int_p]),
         "eqvio_batch_load_filter": (C.c_int, [vp, vp, C.c_int, c_int_p, c_int_p]),
         "eqvio_batch_store_filter": (C.c_int, [vp, C.c_int, vp]),
     }
@@ -175,7 +177,8 @@ def load_batch_protos():
             if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_batch_load_ctx", "eqf_batch_store_ctx", "eqvio_batch_load_filter", "eqvio_batch_store_filter", "eqf_batch_step_accurate", "eqf_batch_last_riccati",
                                                                    "eqvio_batch_set_slot_riccati", "eqvio_batch_get_slot_riccati", "eqf_batch_step_discrete",
                                                                    "eqvio_batch_set_slot_state_matrix", "eqvio_batch_get_slot_state_matrix", "eqf_batch_set_slot_chart",
-                                                                   "eqf_batch_get_slot_chart", "eqvio_batch_set_slot_chart", "eqvio_batch_get_slot_chart") and not hasattr(lib, name):
+                                                                   "eqf_batch_get_slot_chart", "eqvio_batch_set_slot_chart", "eqvio_batch_get_slot_chart", "eqf_batch_convert_chart",
+                                                                   "eqvio_batch_convert_chart") and not hasattr(lib, name):
                 continue  # same-box A/B against the libraries of an older commit (as capi.load_eqf_lib): entry points that commit did not have yet
             fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
@@ -243,6 +246,16 @@ class BatchCore:
         if rc < 0:
             self._chk(rc)
         return rc
+
+    def convert_chart(self, pairs):
+        """pairs: list of (slot, chart). Slot `slot` is re-expressed in `chart` while it holds landmarks, Sigma <- T Sigma T^T, in ONE launch and without a
+        transfer (eqf_batch_convert_chart): state, ids, other settings, totals and last result are kept. Returns the per-pair status codes (EQF_E_BAD_ARG: bad
+        index, repeated slot, or a chart outside the enum; that slot is untouched); raises BatchError when the call itself failed."""
+        n = len(pairs)
+        slots, charts = _i32([p[0] for p in pairs]), _i32([p[1] for p in pairs])
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.elib.eqf_batch_convert_chart(self.h, n, _ip(slots), _ip(charts), _ip(status)))
+        return [int(v) for v in status[:n]]
 
     def __del__(self):
         try:
@@ -597,6 +610,17 @@ class VIOFilterBatch:
         self._chk(self.lib.eqvio_batch_copy_slots(self.h, n, _ip(src), _ip(dst), _ip(status)))
         return [int(v) for v in status[:n]]
 
+    def convert_chart(self, pairs):
+        """pairs: list of (slot, chart). Slot `slot` is re-expressed in `chart` (COORD_*) while it holds landmarks - Sigma <- T Sigma T^T on the device, ONE
+        launch, no transfer (eqvio_batch_convert_chart). It stays the same filter: state, ids, other settings, Riccati mode, state-matrix choice, innovation
+        totals, last result, IMU buffer and time are kept. Returns the per-pair status codes (EQF_E_BAD_ARG: bad index, repeated slot, or a chart outside the
+        enum; that slot is untouched); raises BatchError when the call itself failed."""
+        n = len(pairs)
+        slots, charts = _i32([p[0] for p in pairs]), _i32([p[1] for p in pairs])
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqvio_batch_convert_chart(self.h, n, _ip(slots), _ip(charts), _ip(status)))
+        return [int(v) for v in status[:n]]
+
     def load_filter(self, filter, slots):
         """Every listed slot becomes the capi.VIOFilter `filter` - EqF state, IMU buffer, time, initialised flag - in ONE launch, without Sigma or the
         landmarks crossing to the host (eqvio_batch_load_filter). The slots keep their own settings and innovation totals; the filter is unchanged. Returns the
@@ -664,6 +688,12 @@ class BatchSlot:
     @chart.setter
     def chart(self, chart):
         self.b.set_slot_chart(self.k, chart)
+
+    def convert_chart(self, chart):
+        """This slot re-expressed in `chart` while it holds landmarks (VIOFilterBatch.convert_chart); a refusal raises BatchError with its code."""
+        rc = self.b.convert_chart([(self.k, int(chart))])[0]
+        if rc != 0:
+            raise BatchError(f"convert_chart({self.k}, {chart}): " + self.b.elib.eqf_error_string(rc).decode(), rc)
 
     def copy_to(self, dsts):
         """This slot into every slot of dsts (one slot or a list), one launch (VIOFilterBatch.copy_slots); returns the status codes."""

@@ -1223,4 +1223,127 @@ __global__ void __launch_bounds__(BATCH_PRED_T) k_batch_predict(const PredArgs p
     rec->out_cov[4 * i] = v[0], rec->out_cov[4 * i + 1] = v[1], rec->out_cov[4 * i + 2] = v[2], rec->out_cov[4 * i + 3] = v[3];
 }
 
+// ===================================================================================================
+// eqf_batch_convert_chart (include/eqf_batch.h): entry e's workgroup re-expresses its slot's Sigma in another chart, Sigma' = T Sigma T^T with T = M_to M_from^-1.
+// The charts' changes of coordinates against the Euclidean one are constant and block diagonal (coordinateDifferential_invdepth_euclid / _normal_euclid,
+// VIOState.cpp:355-401): M_euclid = I, M_invdepth = blockdiag(I_21, conv_euc2ind(q0_i)), M_normal = the M of k_batch_normal (NormalM's sensor block, normal_M(q0_i)).
+// So T's sensor block is the identity unless one side is Normal (sdir +1: M's, to Normal; -1: M^-1's, from Normal; 0: the identity), and landmark i's 3 x 3 block
+// is one of conv_euc2ind, conv_ind2euc, normal_M, normal_Minv at q0_i or, between InvDepth and Normal, the product of two of them through Euclidean.
+// The kernel reads the slot's CURRENT Sigma and landmark buffers and writes the OTHER ones, which the host then names current (k_batch_augment's and
+// k_batch_copy's rule: no launch reads a slot's other pair before it has written it). q0, Qq and Qa are copied; the chart constants are formed from q0 by
+// store_chart_constants, the one function every kernel that creates a landmark calls. A workgroup touches its own slot only and sums in a fixed order, so a
+// slot's result has the same bytes whatever launch it is part of. The helpers below are this kernel's own: no other kernel's text changes.
+struct RechartIn {
+    int slot, cur, N;
+    int from, to; // charts
+    int sdir;     // the sensor block of T: +1 M (to Normal), -1 M^-1 (from Normal), 0 the identity
+    double v0[3];  // xi0's velocity (NormalM::v0)
+    double Ad[36]; // Ad(T0^-1) of xi0's camera offset, row-major (NormalM::Ad)
+};
+struct RechartArgs {
+    BatchBufs buf;
+    const RechartIn* in;
+};
+// a chart's 3 x 3 block against Euclidean at q0: M (inv false) or M^-1
+__device__ __forceinline__ M3 rechart_chart_block(int chart, V3 q0, bool inv) {
+    if (chart == EQVIO_COORD_INVDEPTH)
+        return inv ? conv_ind2euc(q0) : conv_euc2ind(q0);
+    return inv ? normal_Minv(q0) : normal_M(q0); // Normal: the Euclidean chart never gets here
+}
+// Landmark block of T = M_to M_from^-1 at q0, row-major into t[9]. One side Euclidean: the other side's block as it is; else the product through Euclidean.
+__device__ __forceinline__ void rechart_landmark_block(int from, int to, V3 q0, double* t) {
+    M3 T;
+    if (from == EQVIO_COORD_EUCLIDEAN)
+        T = rechart_chart_block(to, q0, false);
+    else if (to == EQVIO_COORD_EUCLIDEAN)
+        T = rechart_chart_block(from, q0, true);
+    else
+        T = rechart_chart_block(to, q0, false) * rechart_chart_block(from, q0, true);
+    t[0] = T.a00, t[1] = T.a01, t[2] = T.a02, t[3] = T.a10, t[4] = T.a11, t[5] = T.a12, t[6] = T.a20, t[7] = T.a21, t[8] = T.a22;
+}
+// Row i of T in batch_normal_row's form (indices and coefficients, at most 7): the sensor rows from the entry, a landmark row from the table sT (LDS, 9 per landmark)
+__device__ __forceinline__ int rechart_row(const RechartIn& in, const double* sT, int i, int (&idx)[7], double (&co)[7]) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        idx[k] = 0;
+        co[k] = 0.0;
+    }
+    if (i < 21) {
+        idx[0] = i;
+        co[0] = 1.0;
+        if (i < 12 || in.sdir == 0)
+            return 1;
+        const double sg = in.sdir > 0 ? 1.0 : -1.0;
+        if (i < 15) { // [12:15, 6:9] = -skew(v0) (inverse: +skew(v0))
+            const V3 r = row(skew(V3{in.v0[0], in.v0[1], in.v0[2]}), i - 12);
+            idx[1] = 6, idx[2] = 7, idx[3] = 8;
+            co[1] = -sg * r.x, co[2] = -sg * r.y, co[3] = -sg * r.z;
+            return 4;
+        }
+        const double* ad = in.Ad + 6 * (i - 15); // [15:21, 6:12] = Ad(T0^-1) (inverse: -Ad(T0^-1))
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            idx[1 + c] = 6 + c;
+            co[1 + c] = sg * ad[c];
+        }
+        return 7;
+    }
+    const int l = (i - 21) / 3, r = (i - 21) % 3;
+    idx[0] = 21 + 3 * l, idx[1] = idx[0] + 1, idx[2] = idx[0] + 2;
+    co[0] = sT[9 * l + 3 * r], co[1] = sT[9 * l + 3 * r + 1], co[2] = sT[9 * l + 3 * r + 2];
+    return 3;
+}
+__global__ void __launch_bounds__(BATCH_T) k_batch_rechart(const RechartArgs ra) {
+    __shared__ double sT[9 * BATCH_L];
+    const RechartIn& in = ra.in[blockIdx.x];
+    const int tid = threadIdx.x, L = BATCH_L, ld = ra.buf.ld;
+    const int N = in.N, n = 21 + 3 * N;
+    const double* S0 = ra.buf.sig_of(in.slot, in.cur);
+    double* S1 = ra.buf.sig_of(in.slot, in.cur ^ 1);
+    const double* L0 = ra.buf.lm_of(in.slot, in.cur);
+    double* L1 = ra.buf.lm_of(in.slot, in.cur ^ 1);
+    // the landmarks: their block of T into the table, their planes into the other buffer (a lane per landmark)
+    if (tid < N) {
+        const int i = tid;
+        const double px = L0[i], py = L0[L + i], pz = L0[2 * L + i];
+        rechart_landmark_block(in.from, in.to, V3{px, py, pz}, sT + 9 * i);
+        L1[i] = px;
+        L1[L + i] = py;
+        L1[2 * L + i] = pz;
+        store_chart_constants(L1 + (size_t)CC_OFF * L, L, i, px, py, pz, nullptr);
+        for (int c = 0; c < 4; ++c)
+            L1[(BATCH_QQ + c) * L + i] = L0[(BATCH_QQ + c) * L + i];
+        L1[BATCH_QA * L + i] = L0[BATCH_QA * L + i];
+    }
+    __syncthreads();
+    // Sigma' = T Sigma T^T: entry (i, j), i >= j, is sum_b T[j, b] (sum_a T[i, a] Sigma[a, b]) - (T_i Sigma_ij) first, then (. T_j^T) - and is mirrored
+    for (int t = tid; t < n * n; t += BATCH_T) {
+        const int i = t % n, j = t / n;
+        if (in.sdir == 0 && i < 21 && j < 21) { // T's sensor block is the identity: Sigma's is copied, both halves as they are
+            S1[i + (size_t)j * ld] = S0[i + (size_t)j * ld];
+            continue;
+        }
+        if (i < j)
+            continue;
+        int ii[7], jj[7];
+        double ci[7], cj[7];
+        const int ni = rechart_row(in, sT, i, ii, ci), nj = rechart_row(in, sT, j, jj, cj);
+        double acc = 0.0;
+#pragma unroll
+        for (int b = 0; b < 7; ++b) {
+            if (b < nj) {
+                const double* col = S0 + (size_t)jj[b] * ld;
+                double s = 0.0;
+#pragma unroll
+                for (int a = 0; a < 7; ++a)
+                    if (a < ni)
+                        s = fma(ci[a], col[ii[a]], s);
+                acc = fma(cj[b], s, acc);
+            }
+        }
+        S1[i + (size_t)j * ld] = acc;
+        S1[j + (size_t)i * ld] = acc;
+    }
+}
+
 } // namespace eqf

@@ -62,6 +62,7 @@ struct eqf_batch {
     BatchPacket<eqf_batch_consistency_record> rec;
     BatchPacket<AugIn> ain;  // eqf_batch_augment
     BatchPacket<CopyIn> cin; // eqf_batch_copy_slots
+    BatchPacket<RechartIn> rin; // eqf_batch_convert_chart
     BatchPacket<BridgeIn> brin; // eqf_batch_load_ctx
     BatchPacket<EstIn> ein;  // eqf_batch_estimates
     BatchPacket<eqf_batch_estimate_record> erec;
@@ -232,6 +233,7 @@ void eqf_batch_destroy(eqf_batch* b) {
     b->rec.release();
     b->ain.release();
     b->cin.release();
+    b->rin.release();
     b->brin.release();
     b->ein.release();
     b->erec.release();
@@ -1153,6 +1155,75 @@ int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst
         to.inn_dof = 0;
         to.inn_nis = to.inn_logdet = 0.0;
         to.ric_samples = to.ric_squarings = 0;
+    }
+    return 0;
+}
+
+// One launch of k_batch_rechart over the entries that change something on the device, one synchronisation; nothing of Sigma crosses to the host. The host
+// supplies what M_normal's sensor block needs of xi0 (batch_normal_pack's values). An entry whose slot holds no landmark while neither chart is Normal changes
+// no number - T is the identity on the 21 sensor coordinates - and is eqf_batch_set_slot_chart's relabelling.
+int eqf_batch_convert_chart(eqf_batch* b, int count, const int* slots, const int* charts, int* status) {
+    if (!b || count < 0 || !slots || !charts || !status)
+        return EQF_E_BAD_ARG;
+    if (count == 0)
+        return 0;
+    BatchScreen scr(b, count);
+    std::vector<char> relabel(count, 0);
+    for (int e = 0; e < count; ++e) { // the refusals, before any device is looked at
+        status[e] = 0;
+        if (!scr.fresh(b, slots[e])) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        scr.list(slots[e]);
+        const int to = charts[e];
+        if (to != EQVIO_COORD_EUCLIDEAN && to != EQVIO_COORD_INVDEPTH && to != EQVIO_COORD_NORMAL) {
+            status[e] = EQF_E_BAD_ARG;
+            continue;
+        }
+        const eqf_batch::Slot& sl = b->s[slots[e]];
+        const int from = sl.set.coordinateChoice;
+        if (to == from)
+            continue; // the slot's own chart: nothing to do
+        if (sl.ids.empty() && to != EQVIO_COORD_NORMAL && from != EQVIO_COORD_NORMAL)
+            relabel[e] = 1;
+        else
+            scr.accept(e);
+    }
+    const int nin = scr.nin;
+    if (nin > 0) {
+        BatchDevice dev(b);
+        if (int rc = b->rin.grow(nin))
+            return rc;
+        for (int e = 0; e < count; ++e) {
+            if (scr.in_of[e] < 0)
+                continue;
+            const eqf_batch::Slot& sl = b->s[slots[e]];
+            RechartIn& in = b->rin.h[scr.in_of[e]];
+            in.slot = slots[e];
+            in.cur = sl.cur;
+            in.N = (int)sl.ids.size();
+            in.from = sl.set.coordinateChoice;
+            in.to = charts[e];
+            in.sdir = in.to == EQVIO_COORD_NORMAL ? +1 : (in.from == EQVIO_COORD_NORMAL ? -1 : 0);
+            BatchNormalIn nb;
+            batch_normal_pack(sl.xi0, nullptr, nb);
+            std::memcpy(in.v0, nb.fwd.v0, sizeof(in.v0));
+            std::memcpy(in.Ad, nb.fwd.Ad, sizeof(in.Ad));
+        }
+        const RechartArgs ra{b->buf, b->rin.d};
+        const auto launch = [&] { hipLaunchKernelGGL(k_batch_rechart, dim3(nin), dim3(BATCH_T), 0, b->stream, ra); };
+        if (int rc = batch_round_trip(b, b->rin, nin, launch))
+            return rc;
+    }
+    for (int e = 0; e < count; ++e) {
+        if (scr.in_of[e] < 0 && !relabel[e])
+            continue;
+        eqf_batch::Slot& sl = b->s[slots[e]];
+        sl.set.coordinateChoice = charts[e];
+        sl.ss.chart = charts[e];
+        if (scr.in_of[e] >= 0)
+            sl.cur ^= 1;
     }
     return 0;
 }

@@ -172,6 +172,7 @@ int VIOFilterBatch::setChart(int k, int chart) {
     return 0;
 }
 int VIOFilterBatch::chart(int k) const { return eqf_batch_get_slot_chart(batch, k); }
+int VIOFilterBatch::convertChart(int count, const int* slots, const int* charts, int* status) { return eqf_batch_convert_chart(batch, count, slots, charts, status); }
 VIOFilterBatch::InnovationTotals VIOFilterBatch::innovationTotals(int k) const {
     InnovationTotals t;
     check(eqf_batch_innovation_totals(batch, k, &t.updates, &t.dof, &t.nis, &t.logdet), "eqf_batch_innovation_totals");
@@ -537,6 +538,13 @@ int eqvio_batch_set_slot_state_matrix(eqvio_batch* b, int slot, int kind) { retu
 int eqvio_batch_get_slot_state_matrix(const eqvio_batch* b, int slot) { return b ? b->f->stateMatrix(slot) : EQF_E_BAD_ARG; }
 int eqvio_batch_set_slot_chart(eqvio_batch* b, int slot, int chart) { return b ? b->f->setChart(slot, chart) : EQF_E_BAD_ARG; }
 int eqvio_batch_get_slot_chart(const eqvio_batch* b, int slot) { return b ? b->f->chart(slot) : EQF_E_BAD_ARG; }
+int eqvio_batch_convert_chart(eqvio_batch* b, int count, const int* slots, const int* charts, int* status) {
+    if (!b || count < 0 || !slots || !charts || !status)
+        return EQF_E_BAD_ARG;
+    int code = 0;
+    const int rc = guarded(b, [&] { code = b->f->convertChart(count, slots, charts, status); });
+    return rc ? rc : code;
+}
 int eqvio_batch_get_slot_settings(const eqvio_batch* b, int slot, eqvio_settings* out) {
     return b ? eqf_batch_get_slot_settings(b->f->core(), slot, out) : EQF_E_BAD_ARG;
 }

@@ -66,6 +66,10 @@ class VIOFilterBatch {
     // slot, or a slot that holds landmarks under another chart); chart returns the slot's chart or EQF_E_BAD_ARG.
     int setChart(int slot, int chart);
     int chart(int slot) const;
+    // Entry e: slot slots[e] is re-expressed in chart charts[e] while it holds landmarks, on the device (eqf_batch_convert_chart: one launch, same status codes
+    // and refusals; Sigma <- T Sigma T^T). The host half (IMU buffer, time, flags) is not involved; the Riccati mode and the state-matrix choice are kept.
+    // Returns eqf_batch_convert_chart's code.
+    int convertChart(int count, const int* slots, const int* charts, int* status);
     // Entry e: slot dst[e] becomes slot src[e] as it was before the call - the EqF state on the device (eqf_batch_copy_slots: one launch, same status codes)
     // and the host half: IMU buffer, current time, initialised flag. The destination keeps its settings and innovation totals. A refused entry changes nothing.
     void copySlots(int count, const int* src, const int* dst, int* status);

@@ -224,6 +224,35 @@ inline std::string batchChartRefusal(const std::string& text, int B, std::vector
 inline std::string batchChartSweepRefusal(const Sweep& sw) {
     return sw.name == "coordinateChoice" ? "--batchChart with --sweep coordinateChoice: both name the slots' charts; give one of them" : "";
 }
+// --rechart C[,C...] with --batch B --warmup F: slot k is converted to chart C_k at the branch (eqvio_batch_convert_chart), C = euclidean | invdepth | normal; one
+// value for every slot, or B values, one per slot. What the flag is refused for on its own words and beside the other chart flags, before any file or device is
+// opened (empty: nothing); charts then holds B entries. That it needs a warm-up is rechartWarmupRefusal's to say, once --warmup has been read.
+inline std::string rechartRefusal(const std::string& text, int B, bool haveBatchChart, const Sweep& sw, std::vector<int>& charts) {
+    if (B == 0)
+        return "--rechart needs --batch B (the slots branch into the charts)";
+    std::vector<int> given;
+    for (size_t p = 0; p <= text.size();) {
+        const size_t c = std::min(text.find(',', p), text.size());
+        const std::string w = text.substr(p, c - p);
+        if (w != "euclidean" && w != "invdepth" && w != "normal")
+            return "--rechart: '" + w + "' is neither euclidean nor invdepth nor normal";
+        given.push_back(w == "normal" ? EQVIO_COORD_NORMAL : w == "invdepth" ? EQVIO_COORD_INVDEPTH : EQVIO_COORD_EUCLIDEAN);
+        p = c + 1;
+    }
+    if (given.size() != 1 && (int)given.size() != B)
+        return "--rechart has " + std::to_string(given.size()) + " values for --batch " + std::to_string(B) + ": one value, or one per slot";
+    if (haveBatchChart)
+        return "--rechart with --batchChart: --batchChart names the charts the slots start in, and a warm-up runs under the settings' chart; give one of them";
+    if (sw.name == "coordinateChoice")
+        return "--rechart with --sweep coordinateChoice: both name the slots' charts; give one of them";
+    charts.assign(std::max(B, 0), given[0]);
+    for (int k = 0; k < B && given.size() > 1; ++k)
+        charts[k] = given[k];
+    return "";
+}
+inline std::string rechartWarmupRefusal(int warmup) {
+    return warmup > 0 ? "" : "--rechart needs --warmup F with F > 0 (the slots are converted where they branch from the warm-up)";
+}
 inline const char* batchChartName(int chart) { return chart == EQVIO_COORD_NORMAL ? "normal" : chart == EQVIO_COORD_INVDEPTH ? "invdepth" : "euclidean"; }
 
 // the filter settings as the C-ABI's eqvio_settings

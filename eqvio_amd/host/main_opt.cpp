@@ -6,6 +6,7 @@
 // slot 0 under the command line's settings, and slot 0 is then copied into the other slots on the device (eqf_batch_copy_slots): every tuning starts from the
 // same converged filter, and the scores count the frames after the warm-up only. With --warmupOnFilter the F frames run on one VIOFilter instead (the context
 // path, the fastest way this repository runs a single filter), which is then loaded into all B slots on the device (eqf_batch_load_ctx).
+// --batch B --warmup F --rechart c0[,c1,...] converts slot k to chart ck at the branch (eqf_batch_convert_chart): one warm-up, B charts from the same belief.
 // --batch B --record DIR writes every slot's trajectory (the four state files of --output) to DIR/run_<k>/, and --batch B --groundtruth FILE scores every slot's
 // trajectory against ground truth: both from ONE estimates call per vision measurement over the live slots (eqf_batch_estimates).
 // --batch B --predictions scores every slot by how far a frame's measured features lie from where the slot predicted them (getFeaturePredictions at the
@@ -35,7 +36,8 @@ static void usage() {
               "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]\n"
               "                 [--nis]\n"
               "                            [--batchRiccati fast|accurate|discrete[,...]]\n"
-              "                            [--batchChart euclidean|invdepth|normal[,...]]]\n"
+              "                            [--batchChart euclidean|invdepth|normal[,...]]\n"
+              "                            [--warmup F --rechart euclidean|invdepth|normal[,...]]]\n"
               "                 [--<eqf setting> VALUE ...]   (names of VIOFilter::Settings, e.g. --fastRiccati 1 --coordinateChoice InvDepth)\n"
               "  --batch B   replays the dataset in B slots of one filter batch (include/eqvio_batch.h): per measurement every slot's IMU samples, then ONE\n"
               "              vision step over all slots. Prints one line per slot: vision updates, mean normalised innovation squared per degree of freedom\n"
@@ -66,13 +68,17 @@ static void usage() {
               "  --batchChart C[,C...]   with --batch B: the slots' coordinate chart, C = euclidean, invdepth or normal (the reference's third chart, which\n"
               "              --coordinateChoice and --sweep coordinateChoice=... do not take with --batch); one value for every slot, or B values, one per slot.\n"
               "              Combines with --batchRiccati and --sweep, not with --warmup F > 0 (the chart cannot change under a filter that holds landmarks).\n"
-              "              Each slot's lines name its chart.");
+              "              Each slot's lines name its chart.\n"
+              "  --rechart C[,C...]   with --batch B --warmup F (F > 0; --sweep is not needed, and may stand beside it): the warm-up runs under the settings'\n"
+              "              chart and is copied or loaded into the B slots as above; slot k is then converted to chart C_k on the device (Sigma goes into the new\n"
+              "              chart's coordinates; the state does not change) and the frames after F are scored. One value for every slot, or B values, one per\n"
+              "              slot. Not with --batchChart or --sweep coordinateChoice=.... Each slot's lines name its chart.");
 }
 
 // --batch B: the loop of main() for B slots of one filter batch over the same measurements; slot k with the sweep's k-th value
 static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs, int B, const Sweep& sweep, int warmup, double startTime, double stopTime,
                     const std::string& recordDir, const std::vector<StampedPose>* groundtruth, bool predictions, bool warmupOnFilter, const std::vector<int>& riccati,
-                    const std::vector<int>& charts) {
+                    const std::vector<int>& charts, const std::vector<int>& rechart) {
     const bool swept = !sweep.name.empty();
     const eqvio_settings es = batchSettings(fs);
     eqf_batch* core = nullptr;
@@ -85,7 +91,8 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
         check_rc(filters.setRiccatiMode(k, batchCliRiccati(riccati[k])), "--batchRiccati"), check_rc(filters.setStateMatrix(k, batchCliStateMatrix(riccati[k])), "--batchRiccati");
     auto label = [&](int k) {
         return (swept ? " " + sweep.name + "=" + sweep.values[k] : std::string()) + (riccati.empty() ? std::string() : std::string(" riccati ") + batchRiccatiName(riccati[k])) +
-               (charts.empty() ? std::string() : std::string(" chart ") + batchChartName(charts[k]));
+               (charts.empty() ? std::string() : std::string(" chart ") + batchChartName(charts[k])) +
+               (rechart.empty() ? std::string() : std::string(" chart ") + batchChartName(rechart[k]));
     };
     // --warmupOnFilter: the warm-up's frames run here, on the context path, and no slot runs before the branch
     std::unique_ptr<VIOFilter> warm;
@@ -140,6 +147,15 @@ static int runBatch(TrackReplayServer& dataServer, const VIOFilter::Settings& fs
                     throw std::runtime_error("--warmup: copying slot 0 into slot " + std::to_string(k) + ": " + eqf_error_string(st[k - 1]));
         }
         applySweep();
+        if (!rechart.empty()) { // --rechart: every slot into its chart, one call; behind the sweep's settings, which carry the warm-up's chart
+            std::vector<int> all(B), st(B, 0);
+            for (int k = 0; k < B; ++k)
+                all[k] = k;
+            check_rc(filters.convertChart(B, all.data(), rechart.data(), st.data()), "--rechart");
+            for (int k = 0; k < B; ++k)
+                if (st[k] != 0)
+                    throw std::runtime_error("--rechart: converting slot " + std::to_string(k) + ": " + eqf_error_string(st[k]));
+        }
         check_rc(eqf_batch_reset_innovation_totals(filters.core(), -1), "eqf_batch_reset_innovation_totals");
         live = B;
         branched = true;
@@ -267,9 +283,9 @@ int main(int argc, char** argv) {
     double cameraLag = 0, startTime = -1, stopTime = -1;
     bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false, nisLine = false;
     int batch = 0;
-    std::string warmupText, riccatiText, chartText;
-    bool haveRiccati = false, haveChart = false;
-    std::vector<int> riccati, charts;
+    std::string warmupText, riccatiText, chartText, rechartText;
+    bool haveRiccati = false, haveChart = false, haveRechart = false;
+    std::vector<int> riccati, charts, rechart;
     Sweep sweep;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -332,6 +348,9 @@ int main(int argc, char** argv) {
             } else if (a == "--batchChart") {
                 chartText = val();
                 haveChart = true;
+            } else if (a == "--rechart") {
+                rechartText = val();
+                haveRechart = true;
             }
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
@@ -378,11 +397,18 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        if (haveRechart) { // before any file or device is opened
+            const std::string refusal = rechartRefusal(rechartText, batch < 0 ? 0 : batch, haveChart, sweep, rechart);
+            if (!refusal.empty()) {
+                std::fprintf(stderr, "eqvio_opt: %s\n", refusal.c_str());
+                return 2;
+            }
+        }
         int warmup = 0;
         if (haveWarmup) { // before any file or device is opened, as the refusals of --batch
             char* end = nullptr;
             const long f = std::strtol(warmupText.c_str(), &end, 10);
-            const std::string why = batch == 0 || !haveSweep ? "needs --batch B and --sweep NAME=v0,... (the warm-up is what the swept slots branch from)"
+            const std::string why = batch == 0 || (!haveSweep && !haveRechart) ? "needs --batch B and --sweep NAME=v0,... or --rechart C,... (the warm-up is what the slots branch from)"
                                     : warmupText.empty() || *end ? "'" + warmupText + "' is not a number of frames"
                                     : f < 0 ? "needs F >= 0"
                                     : f > 1000000000 ? "is more frames than any sequence has"
@@ -392,6 +418,10 @@ int main(int argc, char** argv) {
                 return 2;
             }
             warmup = (int)f;
+        }
+        if (haveRechart && !rechartWarmupRefusal(warmup).empty()) { // before any file or device is opened
+            std::fprintf(stderr, "eqvio_opt: %s\n", rechartWarmupRefusal(warmup).c_str());
+            return 2;
         }
         if (warmupOnFilter && warmup == 0) { // before any file or device is opened
             std::fprintf(stderr, "eqvio_opt: --warmupOnFilter needs --warmup F with F > 0 (it says where the warm-up's frames run)\n");
@@ -406,7 +436,7 @@ int main(int argc, char** argv) {
                               : "";
             if (why.empty() && haveSweep)
                 why = sweepRefusal(sweep, batch, batchSettings(fs));
-            if (why.empty() && warmup > 0)
+            if (why.empty() && warmup > 0 && haveSweep)
                 why = warmupSweepRefusal(sweep);
             if (why.empty() && haveSweep && haveChart)
                 why = batchChartSweepRefusal(sweep);
@@ -461,7 +491,7 @@ int main(int argc, char** argv) {
             std::vector<StampedPose> gt;
             if (!gtName.empty())
                 gt = TrackReplayServer::groundtruth(gtName, format);
-            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter, riccati, charts);
+            return runBatch(dataServer, fs, batch, sweep, warmup, startTime, stopTime, recordDir, gtName.empty() ? nullptr : &gt, predictions, warmupOnFilter, riccati, charts, rechart);
         }
         loopTimer.initialise({"correction", "features", "preprocessing", "propagation", "total", "total vision update", "write output"});
         VIOFilter filter(fs); // main_opt.cpp:150

@@ -70,6 +70,7 @@ int eqf_batch_max_landmarks(const eqf_batch* b);
  *   EQF_E_UNSUPPORTED  fastRiccati == 0 or the Normal chart (as eqf_batch_create);
  *   EQF_E_BAD_ARG      bad slot index, or a chart other than the slot's while the slot holds landmarks: its Sigma is expressed in the old chart's
  *                      coordinates. On a slot without landmarks the chart may change (the sensor chart is the same for Euclidean and InvDepth).
+ *                      eqf_batch_convert_chart changes the chart of a slot that holds landmarks, Sigma with it.
  * get returns what the slot runs with: the last accepted set, or eqf_batch_create's settings. */
 int eqf_batch_set_slot_settings(eqf_batch* b, int slot, const eqvio_settings* s);
 int eqf_batch_get_slot_settings(const eqf_batch* b, int slot, eqvio_settings* out);
@@ -87,6 +88,7 @@ int eqf_batch_check_settings(const eqvio_settings* s);
  * and before any device is looked at, the slot then untouched bit for bit:
  *   EQF_E_BAD_ARG      null batch or bad slot index; a chart outside the enum; a chart other than the slot's while the slot holds landmarks
  *                      (eqf_batch_set_slot_settings's rule). The slot's own chart is accepted on a slot with landmarks and does nothing.
+ *                      eqf_batch_convert_chart changes the chart of a slot that holds landmarks, Sigma with it.
  * eqf_batch_get_slot_settings then reports the chart in coordinateChoice; a later accepted eqf_batch_set_slot_settings replaces it with its own (under the same
  * rule; Normal still refused there); eqf_batch_copy_slots and the bridge apply their chart rules to it as to the other two - a Normal slot with landmarks copies
  * into Normal slots only, and eqf_batch_store_ctx of it into a Euclidean or InvDepth context is the chart mismatch EQF_E_BAD_ARG. Moving a filter between a
@@ -307,11 +309,36 @@ int eqf_batch_augment(eqf_batch* b, int count, const eqf_batch_augment_entry* en
  *   0                  done;
  *   EQF_E_BAD_ARG      bad slot index; a destination that an earlier entry of the call names already; or a source that holds landmarks while the
  *                      destination's coordinateChoice is not the source's: Sigma is expressed in the chart's coordinates (the rule of
- *                      eqf_batch_set_slot_settings; a source without landmarks copies into either chart).
+ *                      eqf_batch_set_slot_settings; a source without landmarks copies into either chart). eqf_batch_convert_chart on the
+ *                      destination afterwards, or on the source before, takes a filter across charts.
  * Refusals are decided before any device work and leave the refused destination untouched, bit for bit; the other entries are still done.
  * Returns 0 when the launch ran (whatever the per-entry codes), EQF_E_BAD_ARG for a null batch, src, dst or status or count < 0 (no device is looked at),
  * or a HIP error. */
 int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst, int* status);
+
+/* Changes the chart of slots that hold landmarks, on the device: entry e re-expresses slot slots[e] in chart charts[e] (EQVIO_COORD_*). The three charts differ
+ * by a constant, block-diagonal change of coordinates that depends on xi0 alone (coordinateDifferential_invdepth_euclid / _normal_euclid, VIOState.cpp:355-401):
+ * with M_euclid = I, M_invdepth = blockdiag(I_21, conv_euc2ind(q0_i)) and M_normal the Normal chart's M (sensor block from xi0's velocity and Ad(T0^-1), landmark
+ * blocks normal_M(q0_i)), Sigma <- T Sigma T^T with T = M_to M_from^-1. It is the same filter, described differently:
+ *   - xi0, X, the ids, q0 and Q do not change, bit for bit; the landmark planes the new chart reads are rebuilt from q0 by the function every landmark-creating
+ *     kernel calls;
+ *   - the slot's coordinateChoice becomes the new chart (eqf_batch_get_slot_chart, _get_slot_settings); every other setting, the innovation totals, the last
+ *     result, the last innovation, the last Riccati counters and the eqf_batch_nees_lu_fallbacks count are kept.
+ * One launch of k_batch_rechart for the whole call (one workgroup per entry that changes something on the device) and one synchronisation; nothing of Sigma
+ * crosses to the host. The kernel reads the slot's current buffers and writes its other ones, which then become current. The lower half of Sigma' is computed in
+ * a fixed order - (T_i Sigma_ij), then (. T_j^T) - and mirrored, so Sigma' is symmetric bit for bit; when neither chart is Normal the 21 x 21 sensor block is
+ * copied bit for bit. A slot's result has the same bytes whichever call and batch it is part of.
+ * Launching nothing: an entry whose chart is the slot's already does nothing, bit for bit; an entry on a slot without landmarks, neither chart Normal, is
+ * eqf_batch_set_slot_chart's relabelling (a slot without landmarks still goes to the device when one chart is Normal: the sensor block of Sigma changes).
+ * The process noise P is diagonal in each chart's own coordinates, so two filters that differ by a conversion stop being the same filter with their next
+ * propagation. With useEquivariantOutput = 0 the innovation covariance S = C Sigma C^T + R is unchanged by a conversion to rounding; the Normal chart's
+ * equivariant output is not the transported Euclidean one.
+ * status[e], decided before any device is looked at - a refused slot is untouched bit for bit, the other entries are still done:
+ *   0                  done;
+ *   EQF_E_BAD_ARG      bad slot index, a slot an earlier entry of the call names, or a chart outside the enum.
+ * Returns 0 when it ran (whatever the per-entry codes) or count == 0, EQF_E_BAD_ARG for a null batch, slots, charts or status or count < 0 (no device is looked
+ * at), or a HIP error. */
+int eqf_batch_convert_chart(eqf_batch* b, int count, const int* slots, const int* charts, int* status);
 
 /* The bridge between a context (eqf_hip.h: one filter at low latency) and the slots, on the device: to fork a running filter into B what-if slots, to warm a
  * sweep up on the fast path, to put the best of B tunings back into the filter that runs in real time.
@@ -342,6 +369,7 @@ int eqf_batch_copy_slots(eqf_batch* b, int count, const int* src, const int* dst
  * EQF_OPT_SIGMA_FP32 = 1 rounds Sigma behind it, as eqf_set_sigma does). The slot is unchanged. Refusals, the context untouched:
  *   EQF_E_BAD_ARG      null b or dst, a bad slot, a context on another device; a slot with landmarks whose coordinateChoice is not the context's chart;
  *   EQF_E_UNSUPPORTED  a Normal-chart or float-store context.
+ * A slot of another chart is stored after eqf_batch_convert_chart has taken it to the context's chart.
  * Returns 0, one of these codes, EQF_E_CAPACITY when the context could not grow, or a HIP error. */
 int eqf_batch_load_ctx(eqf_batch* b, eqf_ctx* src, int count, const int* slots, int* status);
 int eqf_batch_store_ctx(eqf_batch* b, int slot, eqf_ctx* dst);

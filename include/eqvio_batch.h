@@ -61,9 +61,16 @@ int eqvio_batch_get_slot_state_matrix(const eqvio_batch* b, int slot);     /* ki
  * slots of a mode behind its others. set: slot < 0 means every slot, and then nothing changes unless every slot takes the chart; a chart outside the enum, a
  * slot index past the last slot, a null batch, or a slot that holds landmarks under another chart (its Sigma is in that chart's coordinates) gives
  * EQF_E_BAD_ARG, nothing changed, no device looked at. get returns the chart, or EQF_E_BAD_ARG. eqvio_batch_load_filter / _store_filter keep refusing a
- * Normal-chart filter (eqf_batch_load_ctx / _store_ctx). */
+ * Normal-chart filter (eqf_batch_load_ctx / _store_ctx). eqvio_batch_convert_chart changes the chart of a slot that holds landmarks, Sigma with it. */
 int eqvio_batch_set_slot_chart(eqvio_batch* b, int slot, int chart); /* slot < 0: every slot */
 int eqvio_batch_get_slot_chart(const eqvio_batch* b, int slot);     /* chart, or EQF_E_BAD_ARG */
+/* Changes the chart of slots that hold landmarks (eqf_batch_convert_chart, include/eqf_batch.h: one launch, Sigma <- T Sigma T^T on the device, the same
+ * per-entry status codes and refusals): entry e re-expresses slot slots[e] in chart charts[e]. It is the same filter, described differently: the state, the
+ * ids, every other setting, the Riccati mode, the state-matrix choice, the innovation totals and the last result are kept, and the host half of the slot (IMU
+ * buffer, current time, initialised flag) is not involved. To warm up once, eqvio_batch_copy_slots into B slots and branch into the three charts from the same
+ * belief. Returns 0 when it ran (whatever the per-entry codes), EQF_E_BAD_ARG (a null batch, slots, charts or status, count < 0; no device is looked at) or a
+ * HIP error. */
+int eqvio_batch_convert_chart(eqvio_batch* b, int count, const int* slots, const int* charts, int* status);
 /* slot starts as VIOFilter(const VIOState&, const Settings&, time) (VIOFilter.cpp:43-56), with the slot's settings */
 int eqvio_batch_create_slot_from_state(eqvio_batch* b, int slot, const double* sensor, const int* ids, const double* p, int N, double time);
 void eqvio_batch_destroy(eqvio_batch* b);
