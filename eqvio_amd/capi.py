@@ -239,9 +239,13 @@ def load_eqf_lib():
         "eqf_last_innovation": (C.c_int, [vp, c_int_p, c_double_p, c_double_p]),
         "eqf_innovation_totals": (C.c_int, [vp, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqf_reset_innovation_totals": (C.c_int, [vp]),
+        "eqf_chart": (C.c_int, [vp]),
+        "eqf_copy_ctx": (C.c_int, [vp, vp]),
+        "eqf_convert_chart": (C.c_int, [vp, C.c_int]),
+        "eqf_fork_stats": (C.c_int, [vp, P(C.c_long), P(C.c_long), C.c_int]),
     }
     for name, (res, args) in protos.items():
-        if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_lookahead_home", "eqf_device_to_itself", "eqf_early_doorbell_stats", "eqf_update_unsettled", "eqf_remove_invalid_at_update", "eqf_gather_stats", "eqf_remove_unmeasured_landmarks", "eqf_find_unknown_ids", "eqf_add_landmarks_held", "eqf_hold_supported", "eqf_hold_stats", "eqf_same_as_mapped", "eqf_live_columns_stats", "eqf_own_hardware_queue", "eqf_last_innovation", "eqf_innovation_totals", "eqf_reset_innovation_totals") and not hasattr(lib, name):
+        if os.environ.get("EQVIO_AMD_LIB_DIR") and name in ("eqf_chart", "eqf_copy_ctx", "eqf_convert_chart", "eqf_fork_stats", "eqf_lookahead_home", "eqf_device_to_itself", "eqf_early_doorbell_stats", "eqf_update_unsettled", "eqf_remove_invalid_at_update", "eqf_gather_stats", "eqf_remove_unmeasured_landmarks", "eqf_find_unknown_ids", "eqf_add_landmarks_held", "eqf_hold_supported", "eqf_hold_stats", "eqf_same_as_mapped", "eqf_live_columns_stats", "eqf_own_hardware_queue", "eqf_last_innovation", "eqf_innovation_totals", "eqf_reset_innovation_totals") and not hasattr(lib, name):
             continue  # same-box A/B against the libraries of an older commit (scripts/ab_builds.sh): entry points that commit did not have yet
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
@@ -286,6 +290,25 @@ class EqfCore:
     @property
     def cap(self):  # size of the output arrays: the context grows on demand (eqf_add_landmarks / eqf_set_state), so ask it
         return max(self._cap0, self.N + 16)
+
+    @property
+    def chart(self):
+        """eqf_chart: the chart Sigma's coordinates are in (COORD_*)"""
+        return self.lib.eqf_chart(self.h)
+
+    def copy_from(self, other):
+        """eqf_copy_ctx: this context comes to hold other's whole filter (state and Sigma), on the device; it keeps its own options and counters"""
+        self._chk0(self.lib.eqf_copy_ctx(self.h, other.h))
+
+    def convert_chart(self, chart):
+        """eqf_convert_chart: Sigma into another chart's coordinates under the landmarks, on the device; the state does not change"""
+        self._chk0(self.lib.eqf_convert_chart(self.h, int(chart)))
+
+    def fork_stats(self, reset=False):
+        """eqf_fork_stats: (copies this context received, conversion launches it ran)"""
+        a, b = C.c_long(), C.c_long()
+        self._chk0(self.lib.eqf_fork_stats(self.h, C.byref(a), C.byref(b), int(reset)))
+        return a.value, b.value
 
     def set_option(self, opt, val):
         self._chk0(self.lib.eqf_set_option(self.h, opt, val))
@@ -535,9 +558,11 @@ def load_filter_lib():
         "eqvio_filter_last_innovation": (C.c_int, [vp, c_int_p, c_double_p, c_double_p]),
         "eqvio_filter_innovation_totals": (C.c_int, [vp, P(C.c_long), P(C.c_long), c_double_p, c_double_p]),
         "eqvio_filter_reset_innovation_totals": (C.c_int, [vp]),
+        "eqvio_filter_copy": (C.c_int, [vp, vp]),
+        "eqvio_filter_convert_chart": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in protos.items():
-        if os.environ.get("EQVIO_AMD_LIB_DIR") and "innovation" in name and not hasattr(lib, name):
+        if os.environ.get("EQVIO_AMD_LIB_DIR") and ("innovation" in name or name in ("eqvio_filter_copy", "eqvio_filter_convert_chart")) and not hasattr(lib, name):
             continue  # same-box A/B against the libraries of an older commit, as in load_eqf_lib
         fn = getattr(lib, name)
         fn.restype = res
@@ -682,6 +707,14 @@ class VIOFilter:
 
     def reset_innovation_totals(self):
         self._chk(self.lib.eqvio_filter_reset_innovation_totals(self.h))
+
+    def copy_from(self, other):
+        """eqvio_filter_copy: this filter becomes other - EqF state and Sigma on the device, IMU buffer, time and initialised flag; it keeps its settings"""
+        self._chk(self.lib.eqvio_filter_copy(self.h, other.h))
+
+    def convert_chart(self, chart):
+        """eqvio_filter_convert_chart: Sigma into the chart's coordinates on the device, the settings' coordinateChoice with it"""
+        self._chk(self.lib.eqvio_filter_convert_chart(self.h, int(chart)))
 
     def last_timing(self):
         a, b, c = C.c_double(), C.c_double(), C.c_double()

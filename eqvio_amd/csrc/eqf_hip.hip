@@ -5,6 +5,7 @@
 #include "eqf_lookahead.hpp"
 #include "eqf_innovation.hpp"
 #include "eqf_batch.hpp"
+#include "eqf_fork.hpp"
 #include "eqf_batch.h"
 #include "host_prof.hpp"
 #include <algorithm>
@@ -198,6 +199,7 @@ struct CtxCounters {
     int innov_last_kind = 0;                 // INNOV_NONE: no update yet; INNOV_VALUE; INNOV_FAILED: m, NaN, NaN; INNOV_OFF: the last applied update ran without the option
     int innov_last_dof = 0;
     double innov_last_nis = 0.0, innov_last_logdet = 0.0;
+    long fork_copies_in = 0, fork_rechart_launches = 0; // eqf_fork_stats: copies received (eqf_copy_ctx's dst), launches of k_ctx_rechart (eqf_convert_chart)
 };
 enum { INNOV_NONE = 0, INNOV_VALUE, INNOV_FAILED, INNOV_OFF };
 // an update whose innovation statistics have not been taken into the counters yet (innov_harvest): in update order
@@ -1524,6 +1526,104 @@ static int grow_capacity(eqf_ctx* c, int new_cap) {
     std::swap(*c, *t);
     eqf_destroy(t);
     return 0;
+}
+
+// ---- branching from one belief on the device (kernels: eqf_fork.hpp)
+int eqf_chart(const eqf_ctx* c) { return c ? c->chart : EQF_E_BAD_ARG; }
+int eqf_fork_stats(eqf_ctx* c, long* copies_in, long* rechart_launches, int reset) {
+    if (!c)
+        return EQF_E_BAD_ARG;
+    if (copies_in)
+        *copies_in = c->fork_copies_in;
+    if (rechart_launches)
+        *rechart_launches = c->fork_rechart_launches;
+    if (reset)
+        c->fork_copies_in = c->fork_rechart_launches = 0;
+    return 0;
+}
+// a context's current buffers as k_ctx_copy takes them: read after enter() and after any growth, which exchange them
+static CtxCopySide copy_side(eqf_ctx* c) { return CtxCopySide{c->sigma(), c->q0(), c->d_lm[c->lmcur], c->ld, c->Ncap}; }
+static bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+// eqf_set_state + eqf_set_sigma with src's values, Sigma and the landmark planes arriving by one launch instead of four copies across the bus: eqf_batch_store_ctx's
+// sequence with a context as the source. The launch goes onto src's stream, behind whatever src has queued; dst's stream is drained before it (eqf_set_state's
+// sync_ctx) and src's behind it, so the rounding pass of EQF_OPT_SIGMA_FP32 = 1 on dst's stream and every later call of dst see the copy.
+int eqf_copy_ctx(eqf_ctx* dst, eqf_ctx* src) {
+    if (!dst || !src)
+        return EQF_E_BAD_ARG;
+    if (dst == src)
+        return 0;
+    if (dst->device != src->device)
+        return EQF_E_BAD_ARG;
+    if (dst->chart != src->chart && (src->N > 0 || dst->chart == EQVIO_COORD_NORMAL || src->chart == EQVIO_COORD_NORMAL))
+        return EQF_E_BAD_ARG; // Sigma is in its chart's coordinates: the landmark rows always, the sensor block under the Normal chart
+    if (dst->sig32 || src->sig32)
+        return EQF_E_UNSUPPORTED;
+    EQFCHK(enter(src));
+    EQFCHK(join_observer(src));
+    EQFCHK(enter(dst));
+    const int N = src->N;
+    if (N > dst->Ncap)
+        EQFCHK(grow_capacity(dst, std::max(N, 2 * dst->Ncap)));
+    EQFCHK(join_observer(dst));
+    EQFCHK(sync_ctx(dst));
+    CtxCopyArgs ca{copy_side(src), copy_side(dst), N, 0, 0};
+    // 16-byte accesses: every column of Sigma and every plane starts on 16 bytes on both sides (pick_ld and the capacity's rounding give that today)
+    ca.vec_sigma = src->ld % 2 == 0 && dst->ld % 2 == 0 && aligned16(ca.src.sigma) && aligned16(ca.dst.sigma);
+    ca.vec_planes = src->Ncap % 2 == 0 && dst->Ncap % 2 == 0 && aligned16(ca.src.st) && aligned16(ca.dst.st) && aligned16(ca.src.lm) && aligned16(ca.dst.lm);
+    const int n = 21 + 3 * N;
+    hipLaunchKernelGGL(k_ctx_copy, dim3(blocks(blocks(n, 2), CTX_COPY_T), blocks(n, CTX_COPY_COLS) + 1), dim3(CTX_COPY_T), 0, src->stream, ca);
+    HIPCHK(hipGetLastError());
+    EQFCHK(sync_ctx(src));
+    dst->est_valid = false, ++dst->est_epoch; // eqf_set_state's lines
+    dst->meas_valid = false;
+    dst->n_held = 0, dst->held_in_memory = false;
+    dst->xi0 = src->xi0;
+    dst->X = src->X;
+    dst->ids = src->ids;
+    dst->N = N;
+    dst->dev_N = N;
+    ++dst->lm_gen;
+    ++dst->fork_copies_in;
+    EQFCHK(round_sigma(dst)); // eqf_set_sigma's (a launch of its own, only with EQF_OPT_SIGMA_FP32 = 1)
+    return sync_ctx(dst);
+}
+// The context's eqf_batch_convert_chart. The host supplies what M_normal's sensor block needs of xi0, as normal_congruence does.
+int eqf_convert_chart(eqf_ctx* c, int chart) {
+    if (!c || (chart != EQVIO_COORD_EUCLIDEAN && chart != EQVIO_COORD_INVDEPTH && chart != EQVIO_COORD_NORMAL))
+        return EQF_E_BAD_ARG;
+    if (c->sig32)
+        return EQF_E_UNSUPPORTED;
+    if (chart == c->chart)
+        return 0;
+    if (chart == EQVIO_COORD_NORMAL && c->n_held > 0)
+        return EQF_E_UNSUPPORTED; // held landmarks wait for a propagation that the Normal chart does not have (eqf_hold_supported)
+    EQFCHK(enter(c));
+    EQFCHK(join_observer(c));
+    const int from = c->chart, N = c->N;
+    if (N > 0 || from == EQVIO_COORD_NORMAL || chart == EQVIO_COORD_NORMAL) { // otherwise T is the identity on the 21 sensor coordinates: a relabelling
+        CtxRechartArgs ra{};
+        ra.S0 = c->d_sigma[c->cur], ra.S1 = c->d_sigma[1 - c->cur], ra.q0 = c->q0();
+        ra.N = N, ra.Ncap = c->Ncap, ra.ld = c->ld;
+        ra.from = from, ra.to = chart;
+        ra.sdir = chart == EQVIO_COORD_NORMAL ? +1 : (from == EQVIO_COORD_NORMAL ? -1 : 0);
+        ra.v0[0] = c->xi0.vel.x, ra.v0[1] = c->xi0.vel.y, ra.v0[2] = c->xi0.vel.z;
+        const M6 Ad = se3_Adjoint(pose_inv(c->xi0.cam));
+        for (int k = 0; k < 36; ++k)
+            ra.Ad[k] = Ad.a[k];
+        const int ng = rc_groups(N);
+        hipLaunchKernelGGL(k_ctx_rechart, dim3(ng * (ng + 1) / 2), dim3(RC_T), 0, c->stream, ra);
+        HIPCHK(hipGetLastError());
+        c->cur = 1 - c->cur;
+        ++c->fork_rechart_launches;
+    }
+    c->chart = chart;
+    // what was evaluated in the old chart's coordinates: the output blocks on the device (the update's own and the propagation kernel's), a staged measurement
+    // (the propagation would evaluate its blocks for it); enter() has dropped the output-covariance cache
+    c->meas_valid = false;
+    c->me_valid = false;
+    c->staged_valid = c->stage_pending = c->stage_requested = false;
+    EQFCHK(round_sigma(c));
+    return sync_ctx(c);
 }
 
 // (all three below: see reshape_pending in eqf_ctx)

@@ -580,6 +580,22 @@ void VIOFilter::adoptHostState(const std::vector<IMUVelocity>& buffer, double ti
     filterState.currentTime = time;
     initialisedFlag = initialised;
 }
+void VIOFilter::copyFrom(VIOFilter& src) {
+    if (&src == this)
+        return;
+    src.filterState.settleInvalid(); // what every view of the filter's state does first
+    filterState.settleInvalid();     // a deferred removal belongs to the state that is about to be replaced: done, not carried over
+    if (const int rc = eqf_copy_ctx(filterState.ctx, src.filterState.ctx))
+        throw std::runtime_error(std::string("eqf_hip: eqf_copy_ctx: ") + eqf_error_string(rc));
+    adoptHostState(src.velocityBuffer, src.filterState.currentTime, src.initialisedFlag);
+}
+void VIOFilter::convertChart(int chart) {
+    filterState.settleInvalid();
+    if (const int rc = eqf_convert_chart(filterState.ctx, chart))
+        throw std::runtime_error(std::string("eqf_hip: eqf_convert_chart: ") + eqf_error_string(rc));
+    filterState.coordinateChoice = (CoordinateChoice)chart;
+    settings->coordinateChoice = (CoordinateChoice)chart;
+}
 void VIOFilter::processIMUData(const IMUVelocity& imu) { // :58-63
     if (!initialisedFlag)
         initialiseFromIMUData(imu);

@@ -286,6 +286,10 @@ class VIOFilter {
     // what the filter keeps on the host beside the EqF state, for moving a whole filter in or out (VIOFilterBatch::loadFilter / storeFilter)
     const std::vector<IMUVelocity>& imuBuffer() const { return velocityBuffer; }
     void adoptHostState(const std::vector<IMUVelocity>& buffer, double time, bool initialised); // after the context was given another filter's EqF state
+    // Branching from one belief (eqf_copy_ctx / eqf_convert_chart): this filter becomes src - EqF state and Sigma on the device, IMU buffer, time and initialised flag
+    // on the host; it keeps its settings. convertChart: Sigma into the chart's coordinates, settings->coordinateChoice with it. Both throw what the device call refuses.
+    void copyFrom(VIOFilter& src);
+    void convertChart(int chart);
 };
 
 // VIOFilter::Settings (include/eqvio/VIOFilterSettings.h:58-124): same fields and defaults; the gain matrices

@@ -254,6 +254,34 @@ inline std::string rechartWarmupRefusal(int warmup) {
     return warmup > 0 ? "" : "--rechart needs --warmup F with F > 0 (the slots are converted where they branch from the warm-up)";
 }
 inline const char* batchChartName(int chart) { return chart == EQVIO_COORD_NORMAL ? "normal" : chart == EQVIO_COORD_INVDEPTH ? "invdepth" : "euclidean"; }
+// --branchAt F --branchCharts C[,C...] on the single-filter path: F vision frames on one filter, which is then copied into one fresh filter per chart
+// (VIOFilter::copyFrom), each copy converted (VIOFilter::convertChart); every branch runs the remaining frames. What the pair is refused for, the flag named,
+// before any file or device is opened (empty: nothing); frames and charts are then set.
+inline std::string branchRefusal(bool haveAt, const std::string& atText, bool haveCharts, const std::string& chartsText, int batch, int& frames, std::vector<int>& charts) {
+    if (batch != 0)
+        return std::string(haveAt ? "--branchAt" : "--branchCharts") + " is the single filter's branch; with --batch B the slots branch by --warmup F --rechart C,...";
+    if (!haveCharts)
+        return "--branchAt needs --branchCharts C[,C...] (the charts the filter branches into)";
+    if (!haveAt)
+        return "--branchCharts needs --branchAt F (the vision frame the filter branches at)";
+    char* end = nullptr;
+    const long f = std::strtol(atText.c_str(), &end, 10);
+    if (atText.empty() || *end)
+        return "--branchAt: '" + atText + "' is not a number of frames";
+    if (f <= 0 || f > 1000000000)
+        return "--branchAt " + atText + ": needs 0 < F, and no more frames than a sequence has";
+    charts.clear();
+    for (size_t p = 0; p <= chartsText.size();) {
+        const size_t c = std::min(chartsText.find(',', p), chartsText.size());
+        const std::string w = chartsText.substr(p, c - p);
+        if (w != "euclidean" && w != "invdepth" && w != "normal")
+            return "--branchCharts: '" + w + "' is neither euclidean nor invdepth nor normal";
+        charts.push_back(w == "normal" ? EQVIO_COORD_NORMAL : w == "invdepth" ? EQVIO_COORD_INVDEPTH : EQVIO_COORD_EUCLIDEAN);
+        p = c + 1;
+    }
+    frames = (int)f;
+    return "";
+}
 
 // the filter settings as the C-ABI's eqvio_settings
 inline eqvio_settings batchSettings(const VIOFilter::Settings& fs) {

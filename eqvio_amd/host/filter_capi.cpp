@@ -244,6 +244,16 @@ int eqvio_filter_reset_innovation_totals(eqvio_filter* f) {
         return -1;
     return guarded(f, [&] { f->filter->resetInnovationTotals(); });
 }
+int eqvio_filter_copy(eqvio_filter* dst, eqvio_filter* src) {
+    if (!dst || !src)
+        return -1;
+    return guarded(dst, [&] { dst->filter->copyFrom(*src->filter); });
+}
+int eqvio_filter_convert_chart(eqvio_filter* f, int chart) {
+    if (!f)
+        return -1;
+    return guarded(f, [&] { f->filter->convertChart(chart); });
+}
 eqvio_frames* eqvio_frames_create(const eqvio_camera* cam, int nframes, const int* imu_counts, const double* imu13_all, const double* stamps, const int* meas_counts,
                                   const int* ids_all, const double* y_all) {
     if (!cam || nframes < 0 || (nframes > 0 && (!imu_counts || !stamps || !meas_counts)))

@@ -11,6 +11,8 @@
 // trajectory against ground truth: both from ONE estimates call per vision measurement over the live slots (eqf_batch_estimates).
 // --batch B --predictions scores every slot by how far a frame's measured features lie from where the slot predicted them (getFeaturePredictions at the
 // measurement's stamp, before the step): ONE predictions call per vision measurement over the live slots (eqf_batch_predictions).
+// --branchAt F --branchCharts c0[,c1,...] (no --batch): F vision frames on one filter, which is then copied on the device into one fresh filter per chart
+// (eqf_copy_ctx), each copy converted to its chart (eqf_convert_chart); every branch runs the remaining frames and prints its scores, labelled with its chart.
 #include "DatasetReplay.hpp"
 #include "VIOFilterBatch.hpp"
 #include "VIOWriter.hpp"
@@ -34,7 +36,7 @@ static void usage() {
               "                 [--camera fx fy cx cy width height] [--distortion radtan k1 k2 p1 p2 k3 | --distortion equidistant k1 k2 k3 k4]\n"
               "                 [--cameraOffset qw qx qy qz x y z] [--cameraLag S] [--start S] [--stop S] [--output DIR] [--sigmaFP32] [--quiet]\n"
               "                 [--batch B [--sweep NAME=v0,v1,... [--warmup F [--warmupOnFilter]]] [--record DIR] [--predictions]\n"
-              "                 [--nis]\n"
+              "                 [--nis] [--branchAt F --branchCharts euclidean|invdepth|normal[,...]]\n"
               "                            [--batchRiccati fast|accurate|discrete[,...]]\n"
               "                            [--batchChart euclidean|invdepth|normal[,...]]\n"
               "                            [--warmup F --rechart euclidean|invdepth|normal[,...]]]\n"
@@ -46,6 +48,11 @@ static void usage() {
               "              RMSE of the slot's trajectory against the ground-truth poses nearest in time, after aligning the first poses.\n"
               "  --nis   a single-filter run (no --batch): switches the device context's innovation statistics on (EQF_OPT_INNOVATION_STATS) and prints, after the\n"
               "              run, the frames updated, the mean NIS per degree of freedom and the total innovation log-likelihood, in the wording of --batch's slot lines\n"
+              "  --branchAt F --branchCharts C[,C...]   a single-filter run (no --batch): the first F vision frames run on one filter under the settings' chart; that\n"
+              "              filter is then copied on the device into one fresh filter per chart C_k, each copy is converted to its chart (Sigma goes into the new\n"
+              "              chart's coordinates; the state does not change), and every branch runs the remaining frames. Prints per branch, labelled with its chart,\n"
+              "              the final state and, with --nis / --groundtruth, the single filter's scores over the frames after the branch. Any landmark count the\n"
+              "              single filter runs. --output, --dumpStates and --sigmaFP32 are refused beside it.\n"
               "  --record DIR   with --batch B: slot k's IMUState.csv, camera.csv, bias.csv and points.csv (the formats of --output) go to DIR/run_<k>/, one row per\n"
               "              vision measurement per live slot, from one estimates call over the live slots per measurement. With --warmup F slots 1 .. B-1 start\n"
               "              their files at the branch.\n"
@@ -283,9 +290,10 @@ int main(int argc, char** argv) {
     double cameraLag = 0, startTime = -1, stopTime = -1;
     bool quiet = false, dump = false, sigmaFP32 = false, printCamera = false, haveSweep = false, haveWarmup = false, predictions = false, warmupOnFilter = false, nisLine = false;
     int batch = 0;
-    std::string warmupText, riccatiText, chartText, rechartText;
-    bool haveRiccati = false, haveChart = false, haveRechart = false;
-    std::vector<int> riccati, charts, rechart;
+    std::string warmupText, riccatiText, chartText, rechartText, branchAtText, branchChartsText;
+    bool haveRiccati = false, haveChart = false, haveRechart = false, haveBranchAt = false, haveBranchCharts = false;
+    std::vector<int> riccati, charts, rechart, branchCharts;
+    int branchAt = 0;
     Sweep sweep;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -352,6 +360,13 @@ int main(int argc, char** argv) {
                 rechartText = val();
                 haveRechart = true;
             }
+            else if (a == "--branchAt") {
+                branchAtText = val();
+                haveBranchAt = true;
+            } else if (a == "--branchCharts") {
+                branchChartsText = val();
+                haveBranchCharts = true;
+            }
             else if (a == "--sweep") {
                 sweep = parseSweep(val());
                 haveSweep = true;
@@ -367,6 +382,16 @@ int main(int argc, char** argv) {
         if (nisLine && batch != 0) { // before any file or device is opened
             std::fprintf(stderr, "eqvio_opt: --nis is the single filter's score; with --batch B every slot's line carries it already\n");
             return 2;
+        }
+        if (haveBranchAt || haveBranchCharts) { // before any file or device is opened
+            std::string refusal = branchRefusal(haveBranchAt, branchAtText, haveBranchCharts, branchChartsText, batch, branchAt, branchCharts);
+            if (refusal.empty())
+                refusal = !outputDir.empty() ? "--branchAt does not support --output" : !statesName.empty() ? "--branchAt does not support --dumpStates"
+                          : sigmaFP32 ? "--branchAt does not support --sigmaFP32 (the float Sigma store is neither copied nor converted)" : "";
+            if (!refusal.empty()) {
+                std::fprintf(stderr, "eqvio_opt: %s\n", refusal.c_str());
+                return 2;
+            }
         }
         if (haveSweep && batch == 0) {
             std::fprintf(stderr, "eqvio_opt: --sweep needs --batch B (one value per slot)\n");
@@ -508,6 +533,18 @@ int main(int argc, char** argv) {
         if (!statesName.empty() && !statesFile)
             throw std::runtime_error("cannot open " + statesName);
         int imuDataCounter = 0, visionDataCounter = 0;
+        // --branchAt F: empty until F frames have run; then one filter per chart, each a converted copy of `filter`, which runs no further frame
+        std::vector<std::unique_ptr<VIOFilter>> branches;
+        auto branch = [&] {
+            for (const int chart : branchCharts) {
+                auto b = std::make_unique<VIOFilter>(fs); // fresh, in the warm-up's chart: its innovation totals count the frames after the branch
+                if (nisLine)
+                    b->setInnovationStats(true);
+                b->copyFrom(filter);
+                b->convertChart(chart);
+                branches.push_back(std::move(b));
+            }
+        };
         const auto loopStartTime = std::chrono::steady_clock::now();
         while (true) {
             const MeasurementType measType = dataServer.nextMeasurementType();
@@ -519,6 +556,16 @@ int main(int argc, char** argv) {
                 VisionMeasurement measData = dataServer.getSimVision();
                 if (startTime > 0 && measData.stamp < startTime)
                     continue;
+                if (branchAt > 0 && branches.empty() && visionDataCounter == branchAt)
+                    branch(); // before the first frame after the warm-up, and behind every IMU sample that came before it
+                if (!branches.empty()) {
+                    for (auto& b : branches)
+                        b->processVisionData(measData);
+                    ++visionDataCounter;
+                    if (stopTime > 0 && branches[0]->getTime() > stopTime)
+                        break;
+                    continue;
+                }
                 loopTimer.startTiming("total vision update");
                 filter.processVisionData(measData);
                 loopTimer.endTiming("total vision update");
@@ -550,10 +597,13 @@ int main(int argc, char** argv) {
                 const IMUVelocity imuData = dataServer.getIMU();
                 if (startTime > 0 && imuData.stamp < startTime)
                     continue;
-                filter.processIMUData(imuData);
+                if (branches.empty())
+                    filter.processIMUData(imuData);
+                for (auto& b : branches)
+                    b->processIMUData(imuData);
                 ++imuDataCounter;
             }
-            if (stopTime > 0 && filter.getTime() > stopTime)
+            if (stopTime > 0 && (branches.empty() ? filter : *branches[0]).getTime() > stopTime)
                 break;
         }
         const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopStartTime).count();
@@ -561,6 +611,39 @@ int main(int argc, char** argv) {
             std::fclose(statesFile);
         std::cout << "Processed " << imuDataCounter << " IMU and " << visionDataCounter << " vision measurements.\n"
                   << "Time taken: " << elapsed << " seconds." << std::endl;
+        if (branchAt > 0) { // every branch's lines, labelled with its chart: what the single filter prints, over the frames after the branch
+            if (branches.empty())
+                throw std::runtime_error("--branchAt " + std::to_string(branchAt) + ": the sequence has only " + std::to_string(visionDataCounter) + " vision frames");
+            std::printf("branch: %d frames on a single filter (chart %s), then copied into %zu filters and converted; scores over the %d frames after the branch\n", branchAt,
+                        batchChartName((int)fs.coordinateChoice), branches.size(), visionDataCounter - branchAt);
+            std::vector<StampedPose> gt;
+            if (!gtName.empty())
+                gt = TrackReplayServer::groundtruth(gtName, format);
+            for (size_t k = 0; k < branches.size(); ++k) {
+                VIOFilter& b = *branches[k];
+                const std::string what = "branch " + std::to_string(k) + " chart " + batchChartName(branchCharts[k]);
+                const VIOState est = b.stateEstimate();
+                std::printf("%s: final time %.9g  position %.9g %.9g %.9g  landmarks %d\n", what.c_str(), b.getTime(), est.sensor.pose.x.x, est.sensor.pose.x.y, est.sensor.pose.x.z,
+                            b.viewEqFState().numLandmarks());
+                if (nisLine) {
+                    long updates = 0, dof = 0;
+                    double nis = 0, logdet = 0;
+                    b.innovationTotals(updates, dof, nis, logdet);
+                    std::printf("%s: frames updated %ld  mean NIS/dof %.9g  log-likelihood %.9g\n", what.c_str(), updates, nis / (double)dof,
+                                -0.5 * (nis + logdet + (double)dof * std::log(2.0 * M_PI)));
+                }
+                if (!gt.empty()) { // distance to the ground-truth pose nearest in time
+                    size_t j = 0;
+                    for (size_t i = 0; i < gt.size(); ++i)
+                        if (std::fabs(gt[i].t - b.getTime()) < std::fabs(gt[j].t - b.getTime()))
+                            j = i;
+                    const V3 d{est.sensor.pose.x.x - gt[j].pose.x.x, est.sensor.pose.x.y - gt[j].pose.x.y, est.sensor.pose.x.z - gt[j].pose.x.z};
+                    std::printf("%s: groundtruth poses %zu  nearest stamp %.9g  position %.6g %.6g %.6g  distance %.9g\n", what.c_str(), gt.size(), gt[j].t, gt[j].pose.x.x,
+                                gt[j].pose.x.y, gt[j].pose.x.z, std::sqrt(d.x * d.x + d.y * d.y + d.z * d.z));
+                }
+            }
+            return 0;
+        }
         const VIOState est = filter.stateEstimate();
         std::printf("final time %.9g  position %.6g %.6g %.6g  landmarks %d  vision updates/s %.1f\n", filter.getTime(), est.sensor.pose.x.x, est.sensor.pose.x.y,
                     est.sensor.pose.x.z, filter.viewEqFState().numLandmarks(), visionDataCounter / elapsed);

@@ -183,6 +183,38 @@ void* eqf_stream(eqf_ctx* ctx);
 int eqf_set_state(eqf_ctx* ctx, const double* xi0_sensor, const double* X_sensor, const int* ids, const double* q0, const double* Q, int N);
 int eqf_get_state(eqf_ctx* ctx, double* xi0_sensor, double* X_sensor, int* ids, double* q0, double* Q, int cap); /* returns N or <0 */
 
+/* Branching from one belief on the device: a context's chart, a copy of a whole filter into another context, and the change of a context's chart under landmarks.
+ * Argument checks come before any device is looked at; a refused call leaves both contexts exactly as they were.
+ *
+ * eqf_chart: the context's chart (EQVIO_COORD_*), EQF_E_BAD_ARG for null.
+ *
+ * eqf_copy_ctx: dst comes to hold what src holds - xi0, X, the ids in state order, q0, Qq, Qa and Sigma - exactly as eqf_set_state + eqf_set_sigma with src's
+ * eqf_get_state / eqf_get_sigma values would leave it, by ONE launch (k_ctx_copy) that reads src's current buffers with src's leading dimension and plane stride
+ * and writes dst's with dst's: neither Sigma nor the landmark planes cross the bus (the 46 sensor doubles and the ids are host data on both sides). src is entered as
+ * eqf_get_state enters it (an update taken from the early doorbell settled, held landmarks and a pending reshape applied, the observer's stream joined) and is otherwise
+ * unchanged. dst gets eqf_set_state's aftermath (estimate cache, device measurement, held landmarks and id lookups dropped, the landmark generation moves on), grows
+ * when src holds more landmarks than it has room for, rounds Sigma behind the copy with EQF_OPT_SIGMA_FP32 = 1, and keeps its own options, counters and innovation
+ * totals. The launch runs behind everything queued on src's stream, dst's stream is drained before it, and the call returns when dst may be used. dst == src: 0,
+ * nothing done. EQF_E_BAD_ARG: a null pointer, contexts on different devices, src holds landmarks and dst's chart is not src's, or src holds none and exactly one of the
+ * two charts is Normal (the sensor block of Sigma is in other coordinates there). EQF_E_UNSUPPORTED: the float Sigma store (EQF_OPT_SIGMA_FP32 = 2) on either side.
+ * EQF_E_CAPACITY: dst could not grow.
+ *
+ * eqf_convert_chart: Sigma <- T Sigma T^T with T = M_to M_from^-1, M_euclid = I, M_invdepth = blockdiag(I_21, conv_euc2ind(q0_i)), M_normal = the Normal chart's M
+ * (eqf_batch_convert_chart's T), out of place into the other Sigma buffer by one launch (k_ctx_rechart: one workgroup per tile of the lower triangle, tiles cut along
+ * landmark boundaries, the mirror image written from the same values: Sigma' is symmetric bit for bit and does not depend on the capacity). xi0, X, the ids, q0 and Q do
+ * not change; the landmark planes hold every chart's constants of q0 already (store_chart_constants writes all of them, whatever the chart) and stay. eqf_chart then reports
+ * the new chart. Options, counters, innovation totals and the last Gamma are kept; a staged measurement, the output blocks a propagation evaluated and the output
+ * covariance cache are dropped (C depends on the chart). The context is entered as eqf_get_state enters it. With neither chart Normal the 21 x 21 sensor block is copied
+ * bit for bit. The context's own chart: 0, no launch. No landmarks and neither chart Normal: relabelled on the host, no launch. EQF_OPT_SIGMA_FP32 = 1 rounds behind the
+ * conversion. EQF_E_BAD_ARG: null, or a chart outside the enum. EQF_E_UNSUPPORTED: the float Sigma store (EQF_OPT_SIGMA_FP32 = 2); or a conversion to the Normal
+ * chart while landmarks are held (eqf_add_landmarks_held: they wait for a propagation the Normal chart does not have).
+ *
+ * eqf_fork_stats: copies this context received (as dst), conversion launches it ran. Null outputs are skipped. */
+int eqf_chart(const eqf_ctx* ctx);
+int eqf_copy_ctx(eqf_ctx* dst, eqf_ctx* src);
+int eqf_convert_chart(eqf_ctx* ctx, int chart);
+int eqf_fork_stats(eqf_ctx* ctx, long* copies_in, long* rechart_launches, int reset);
+
 /* VIO_eqf::Sigma (VIO_eqf.h:39-40); n must equal 21 + 3N. */
 int eqf_set_sigma(eqf_ctx* ctx, const double* sigma_colmajor, int n);
 int eqf_set_sigma_diag(eqf_ctx* ctx, const double* diag, int n);

@@ -58,6 +58,12 @@ int eqvio_filter_set_innovation_stats(eqvio_filter* f, int on);
 int eqvio_filter_last_innovation(eqvio_filter* f, int* dof, double* nis, double* logdet);
 int eqvio_filter_innovation_totals(eqvio_filter* f, long* updates, long* dof, double* nis, double* logdet);
 int eqvio_filter_reset_innovation_totals(eqvio_filter* f);
+/* Branching from one belief (eqf_copy_ctx / eqf_convert_chart, include/eqf_hip.h). eqvio_filter_copy: dst becomes src - the EqF state and Sigma on the device, and
+ * what the filter keeps on the host beside them: the IMU buffer, the time and the initialised flag; dst keeps its settings and its context's options and counters.
+ * eqvio_filter_convert_chart: the filter's Sigma into the chart's coordinates (EQVIO_COORD_*), and coordinateChoice of its settings with it. 0, or -1
+ * (eqvio_filter_last_error carries the device call's refusal). */
+int eqvio_filter_copy(eqvio_filter* dst, eqvio_filter* src);
+int eqvio_filter_convert_chart(eqvio_filter* f, int chart);
 
 /* Prepared replay. eqvio_frames_create builds, once, what the reference's tracker / data server hands to the filter: the IMU
  * samples and one VisionMeasurement (a std::map of pixel coordinates) per frame, from arrays concatenated over frames (frame j:
