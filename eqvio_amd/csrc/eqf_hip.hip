@@ -6,6 +6,7 @@
 #include "eqf_innovation.hpp"
 #include "eqf_batch.hpp"
 #include "eqf_fork.hpp"
+#include "eqf_ensemble.hpp"
 #include "eqf_batch.h"
 #include "host_prof.hpp"
 #include <algorithm>
@@ -4161,3 +4162,5 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 
 // Filter batch (include/eqf_batch.h): its host side, in this translation unit for the helpers above
 #include "eqf_batch_host.hpp"
+// Particle ensemble (include/eqf_ensemble.h): its host side, here for enter, launch_chain, nees_sensor_error and the context's Sigma
+#include "eqf_ensemble_host.hpp"

@@ -1,0 +1,143 @@
+"""ctypes binding of the particle ensemble: include/eqf_ensemble.h (libeqf_hip.so).
+
+ParticleEnsemble holds P hypotheses of the true state on the device and judges them against one context (an EqfCore, or the core of a VIOFilter):
+one factorisation of Sigma per nees() / sample() call, whatever P is. numpy arrays in, numpy arrays out, errors raised loudly (EqfError with the
+library's code). The prototypes are declared in a list of their own (_ensemble_declared), apart from the loader's _declared list of eqf_hip.h.
+"""
+import ctypes as C
+
+import numpy as np
+
+from eqvio_amd.capi import EqfError, _dp, _f64, _i32, _ip, c_double_p, c_int_p, load_eqf_lib
+
+
+def load_ensemble_protos():
+    """Declare the prototypes of include/eqf_ensemble.h on libeqf_hip.so."""
+    lib = load_eqf_lib()
+    if getattr(lib, "_ensemble_declared", None):
+        return lib
+    vp, P = C.c_void_p, C.POINTER
+    protos = {
+        "eqf_ensemble_create": (C.c_int, [P(vp), C.c_int, C.c_int, C.c_int]),
+        "eqf_ensemble_destroy": (None, [vp]),
+        "eqf_ensemble_size": (C.c_int, [vp, c_int_p, c_int_p]),
+        "eqf_ensemble_set": (C.c_int, [vp, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p]),
+        "eqf_ensemble_get": (C.c_int, [vp, c_int_p, c_double_p, c_double_p, C.c_int, C.c_int]),
+        "eqf_ensemble_sample": (C.c_int, [vp, vp, C.c_int, c_double_p]),
+        "eqf_ensemble_integrate": (C.c_int, [vp, c_double_p, C.c_double, c_double_p]),
+        "eqf_ensemble_errors": (C.c_int, [vp, vp, c_double_p]),
+        "eqf_ensemble_nees": (C.c_int, [vp, vp, c_double_p, c_double_p]),
+        "eqf_ensemble_covariance": (C.c_int, [vp, vp, c_double_p]),
+        "eqf_ensemble_resample": (C.c_int, [vp, C.c_int, c_int_p]),
+        "eqf_ensemble_stats": (C.c_int, [vp, P(C.c_long), P(C.c_long), C.c_int]),
+    }
+    for name, (res, args) in protos.items():
+        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    lib._ensemble_declared = sorted(protos)
+    return lib
+
+
+class ParticleEnsemble:
+    """One eqf_ensemble against one context. core_or_filter: an EqfCore, or a VIOFilter (its eqf_ctx is taken through core_handle())."""
+
+    def __init__(self, core_or_filter, max_particles, max_landmarks, device=0):
+        self.lib = load_ensemble_protos()
+        self.owner = core_or_filter  # keeps the context alive
+        self.h = C.c_void_p()
+        self.max_particles, self.max_landmarks = int(max_particles), int(max_landmarks)
+        self._chk(self.lib.eqf_ensemble_create(C.byref(self.h), device, self.max_particles, self.max_landmarks))
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise EqfError(rc, self.lib.eqf_error_string(rc).decode())
+
+    def _ctx(self):
+        o = self.owner
+        return C.c_void_p(o.core_handle()) if hasattr(o, "core_handle") else o.h
+
+    def _ctx_n(self):
+        return 21 + 3 * self.lib.eqf_num_landmarks(self._ctx())
+
+    def close(self):
+        if self.h:
+            self.lib.eqf_ensemble_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self):
+        """(P, N)"""
+        P, N = C.c_int(), C.c_int()
+        self._chk(self.lib.eqf_ensemble_size(self.h, C.byref(P), C.byref(N)))
+        return P.value, N.value
+
+    def set(self, ids, sensor, p):
+        """ids[N], sensor (P, 23), p (P, N, 3)"""
+        ids, sensor, p = _i32(ids), _f64(sensor).reshape(-1, 23), _f64(p)
+        P, N = sensor.shape[0], len(ids)
+        if p.size != 3 * N * P:
+            raise ValueError(f"p holds {p.size} doubles, {3 * N * P} expected")
+        self._chk(self.lib.eqf_ensemble_set(self.h, P, N, _ip(ids), _dp(sensor), _dp(p)))
+
+    def get(self):
+        """(ids[N], sensor (P, 23), p (P, N, 3))"""
+        P, N = self.size
+        ids, sensor, p = np.zeros(N, np.int32), np.zeros((P, 23)), np.zeros((P, N, 3))
+        rc = self.lib.eqf_ensemble_get(self.h, _ip(ids), _dp(sensor), _dp(p), P, N)
+        if rc < 0:
+            self._chk(rc)
+        return ids, sensor, p
+
+    def sample(self, xi):
+        """xi (n, P) standard normals: particle k = stateGroupAction(X, stateChart^-1(L xi[:, k])), Sigma = L L^T"""
+        xi = np.asfortranarray(xi, dtype=np.float64)
+        if xi.ndim != 2 or xi.shape[0] != self._ctx_n():
+            raise ValueError(f"xi must be (n, P) with n = {self._ctx_n()}")
+        self._chk(self.lib.eqf_ensemble_sample(self.h, self._ctx(), xi.shape[1], xi.ctypes.data_as(c_double_p)))
+
+    def integrate(self, imu, dt, offsets=None):
+        """integrateSystemFunction for every particle; offsets (P, 6): gyr and acc disturbances per particle"""
+        imu = _f64(imu)
+        if offsets is None:
+            self._chk(self.lib.eqf_ensemble_integrate(self.h, _dp(imu), float(dt), None))
+            return
+        offsets = _f64(offsets)
+        if offsets.shape != (self.size[0], 6):
+            raise ValueError("offsets must be (P, 6)")
+        self._chk(self.lib.eqf_ensemble_integrate(self.h, _dp(imu), float(dt), _dp(offsets)))
+
+    def errors(self):
+        """eps (n, P): computeNEES's error coordinates of every particle in the context's chart"""
+        out = np.zeros((self._ctx_n(), self.size[0]), order="F")
+        self._chk(self.lib.eqf_ensemble_errors(self.h, self._ctx(), out.ctypes.data_as(c_double_p)))
+        return out
+
+    def nees(self):
+        """(nees[P], mean)"""
+        out, mean = np.zeros(self.size[0]), C.c_double()
+        self._chk(self.lib.eqf_ensemble_nees(self.h, self._ctx(), _dp(out), C.byref(mean)))
+        return out, mean.value
+
+    def covariance(self):
+        """(1 / P) sum eps_k eps_k^T, (n, n), exactly symmetric"""
+        n = self._ctx_n()
+        out = np.zeros((n, n), order="F")
+        self._chk(self.lib.eqf_ensemble_covariance(self.h, self._ctx(), out.ctypes.data_as(c_double_p)))
+        return out
+
+    def resample(self, idx):
+        idx = _i32(idx)
+        self._chk(self.lib.eqf_ensemble_resample(self.h, len(idx), _ip(idx)))
+
+    def stats(self, reset=False):
+        """(kernel launches, factorisations of Sigma) since the last reset"""
+        a, b = C.c_long(), C.c_long()
+        self._chk(self.lib.eqf_ensemble_stats(self.h, C.byref(a), C.byref(b), int(reset)))
+        return a.value, b.value

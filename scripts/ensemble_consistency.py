@@ -1,0 +1,112 @@
+"""The reference's statistical suite (test/test_FilterStatistics.cpp:98-168) at any size, entirely through the particle ensemble:
+a planted filter (xi0 random, X = identity, Sigma0 = the fixture's initial covariance) of --landmarks N in --chart c, --particles P particles sampled by
+eqf_ensemble_sample from numpy's normals, and the four checks - initial distribution, true input (5 steps of 0.2 s at zero velocity), random input (5 steps of
+0.05 s) and output (measurement likelihood and weightedResample on the host from eqf_ensemble_get, eqf_ensemble_resample, one vision update) - each judged by the
+mean of ONE eqf_ensemble_nees call. The filter's side is the device's discrete Riccati step with zero gains, the observer step and the vision update, as in
+tests/test_gpu_reference_tests.py. Prints one JSON line per check with every mean NEES seen and the reference's band (0.1 / 1.0 / 0.1 / 0.5 at N = 2, P = 1000)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: F401,E402  (the HIP runtime of the torch wheel first, as bench.py)
+
+from eqvio_amd.capi import Camera, EqfCore, Settings  # noqa: E402
+from eqvio_amd.ensemble import ParticleEnsemble  # noqa: E402
+
+CHARTS = {"euclid": 0, "invdepth": 1, "normal": 2}
+BANDS = {"initial": 0.1, "true_input": 1.0, "random_input": 0.1, "output": 0.5}
+FX, FY, CX, CY = 458.654, 457.296, 367.215, 248.375
+
+
+def planted(N, chart, seed):
+    rng = np.random.default_rng([seed, N, chart])
+    s = Settings.defaults()
+    s.coordinateChoice = chart
+    s.initialPointVariance = s.initialPointDepthVariance = 0.01**2
+    s.initialBiasOmegaVariance = s.initialBiasAccelVariance = 0.01**2
+    s.initialVelocityVariance = 0.1**2
+    s.initialPositionVariance = 0.001**2
+    xi0 = np.zeros(23)
+    xi0[0:6] = rng.uniform(-1, 1, 6)
+    for lo in (6, 16):
+        q = rng.normal(size=4)
+        xi0[lo:lo + 4] = q / np.linalg.norm(q)
+    xi0[10:13], xi0[13:16], xi0[20:23] = rng.uniform(-1, 1, 3), rng.uniform(-1, 1, 3), rng.uniform(-1, 1, 3)
+    q0 = rng.uniform(-1, 1, (N, 3)) * 10.0
+    q0[:, 2] += 20.0
+    ident = np.zeros(23)
+    ident[6] = ident[16] = 1.0
+    core = EqfCore(max(N, 1), chart)
+    core.set_state(xi0, ident, np.arange(N, dtype=np.int32), q0, np.tile(np.array([1.0, 0, 0, 0, 1.0]), (N, 1)))
+    core.set_sigma(np.diag(s.initial_cov_diag(N)))
+    return rng, s, core, q0
+
+
+def pixels(p):
+    return np.stack([FX * p[..., 0] / p[..., 2] + CX, FY * p[..., 1] / p[..., 2] + CY], axis=-1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--landmarks", type=int, default=2)
+    ap.add_argument("--particles", type=int, default=1000)
+    ap.add_argument("--chart", choices=sorted(CHARTS), default="invdepth")
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    N, P, chart = a.landmarks, a.particles, CHARTS[a.chart]
+    n = 21 + 3 * N
+    for check in ("initial", "true_input", "random_input", "output"):
+        rng, s, core, q0 = planted(N, chart, a.seed)
+        ens = ParticleEnsemble(core, P, N)
+        t0 = time.perf_counter()
+        ens.sample(rng.normal(size=(n, P)))
+        means = []
+        if check == "initial":
+            means.append(ens.nees()[1])
+        elif check in ("true_input", "random_input"):
+            vel, dt = np.zeros(13), 0.2
+            if check == "random_input":
+                vel[1:7], dt = rng.uniform(-1, 1, 6), 0.05
+            for _ in range(5):
+                ens.integrate(vel, dt)
+                core.integrate_riccati_discrete(vel, dt, np.zeros(12), np.zeros(8))  # 0 * inputGain, 0 * stateGain (:110-111, :133-134)
+                core.integrate_observer(vel[None, :], np.array([dt]), True)
+                means.append(ens.nees()[1])
+        else:
+            var = s.measurementNoise**2
+            ids = np.arange(N, dtype=np.int32)
+            y = pixels(q0) + np.sqrt(var) * rng.normal(size=(N, 2))  # X = identity: the estimate's points are q0
+            _, _, p = ens.get()
+            err = (y[None, :, :] - pixels(p)).reshape(P, -1)
+            logw = -0.5 * np.einsum("ki,ki->k", err, err) / var
+            w = np.exp(logw - logw.max())
+            w /= w.sum()
+            idx, j, total = np.zeros(P, np.int32), 0, w[0]  # weightedResample (test/testing_utilities.h:55-74)
+            for k in range(P):
+                thr = (rng.uniform() + k) / P
+                while total < thr and j + 1 < P:
+                    j += 1
+                    total += w[j]
+                idx[k] = j
+            ens.resample(idx)
+            if N > 0:
+                core.vision_update(Camera.pinhole(FX, FY, CX, CY, 752, 480), ids, y.reshape(-1), var, True, False)
+            means.append(ens.nees()[1])
+            print(json.dumps({"check": check, "distinct_particles_after_resampling": int(len(set(idx.tolist())))}), flush=True)
+        launches, facts = ens.stats()
+        print(json.dumps({"check": check, "chart": a.chart, "N": N, "n": n, "P": P, "mean_nees": [round(float(m), 6) for m in means], "reference_band": BANDS[check],
+                          "inside": bool(all(abs(m - 1.0) <= BANDS[check] for m in means)), "seconds": round(time.perf_counter() - t0, 3), "launches": launches,
+                          "factorisations": facts}), flush=True)
+        ens.close()
+        core.close()
+
+
+if __name__ == "__main__":
+    main()
