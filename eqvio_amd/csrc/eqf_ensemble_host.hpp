@@ -19,6 +19,9 @@ struct eqf_ensemble {
     int cur = 0;
     double *d_E = nullptr, *d_Z = nullptr, *d_W = nullptr, *d_xi = nullptr, *d_out = nullptr, *d_cov = nullptr, *d_pose = nullptr;
     int* d_idx = nullptr;
+    // the measurement side (eqf_ensemble_output_host.hpp): results and kept weights, running sums, measurement / uniforms; the kept weights are valid
+    double *d_lw = nullptr, *d_cum = nullptr, *d_yu = nullptr;
+    bool w_valid = false;
     long launches = 0, factorisations = 0;
     std::vector<double> h; // host staging
     std::vector<void*> own;
@@ -196,6 +199,9 @@ int eqf_ensemble_create(eqf_ensemble** out, int device, int max_particles, int m
         EQFCHK(ens_alloc(e, e->d_cov, (size_t)ncap * ncap));
         EQFCHK(ens_alloc(e, e->d_pose, 7 * (size_t)e->ldp));
         EQFCHK(ens_alloc(e, e->d_idx, (size_t)std::max(e->Pcap, e->Nalloc())));
+        EQFCHK(ens_alloc(e, e->d_lw, 4 + 2 * (size_t)e->Pcap));
+        EQFCHK(ens_alloc(e, e->d_cum, (size_t)e->Pcap));
+        EQFCHK(ens_alloc(e, e->d_yu, (size_t)std::max(e->Pcap, 2 * e->Nalloc())));
         return 0;
     };
     if (!rc)
@@ -265,6 +271,7 @@ int eqf_ensemble_set(eqf_ensemble* e, int P, int N, const int* ids, const double
     }
     e->P = P;
     e->N = N;
+    e->w_valid = false;
     e->ids.assign(ids, ids + N);
     e->sensor.assign(sensor, sensor + 23 * (size_t)P);
     return 0;
@@ -330,6 +337,7 @@ int eqf_ensemble_sample(eqf_ensemble* e, eqf_ctx* c, int P, const double* xi) {
     }
     e->P = P;
     e->N = N;
+    e->w_valid = false;
     e->ids = c->ids;
     e->sensor.swap(sens);
     return 0;
@@ -379,6 +387,7 @@ int eqf_ensemble_integrate(eqf_ensemble* e, const double* imu13, double dt, cons
         EQFCHK(spin_stream(e->stream));
     }
     e->sensor.swap(sens);
+    e->w_valid = false;
     return 0;
 }
 
@@ -462,5 +471,6 @@ int eqf_ensemble_resample(eqf_ensemble* e, int P_new, const int* src) {
         std::copy(e->sensor.begin() + 23 * (size_t)src[k], e->sensor.begin() + 23 * (size_t)src[k] + 23, sens.begin() + 23 * (size_t)k);
     e->sensor.swap(sens);
     e->P = P_new;
+    e->w_valid = false;
     return 0;
 }

@@ -7,6 +7,7 @@
 #include "eqf_batch.hpp"
 #include "eqf_fork.hpp"
 #include "eqf_ensemble.hpp"
+#include "eqf_ensemble_output.hpp"
 #include "eqf_batch.h"
 #include "host_prof.hpp"
 #include <algorithm>
@@ -4164,3 +4165,5 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 #include "eqf_batch_host.hpp"
 // Particle ensemble (include/eqf_ensemble.h): its host side, here for enter, launch_chain, nees_sensor_error and the context's Sigma
 #include "eqf_ensemble_host.hpp"
+// ... and its measurement side (include/eqf_ensemble_output.h), which takes no context
+#include "eqf_ensemble_output_host.hpp"

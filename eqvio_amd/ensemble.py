@@ -2,7 +2,8 @@
 
 ParticleEnsemble holds P hypotheses of the true state on the device and judges them against one context (an EqfCore, or the core of a VIOFilter):
 one factorisation of Sigma per nees() / sample() call, whatever P is. numpy arrays in, numpy arrays out, errors raised loudly (EqfError with the
-library's code). The prototypes are declared in a list of their own (_ensemble_declared), apart from the loader's _declared list of eqf_hip.h.
+library's code). The prototypes are declared in a list of their own (_ensemble_declared), apart from the loader's _declared list of eqf_hip.h; those of
+include/eqf_ensemble_output.h (measure, likelihood, resample_weighted: the measurement side, on the device) in _ensemble_output_declared.
 """
 import ctypes as C
 
@@ -11,8 +12,12 @@ import numpy as np
 from eqvio_amd.capi import EqfError, _dp, _f64, _i32, _ip, c_double_p, c_int_p, load_eqf_lib
 
 
+def _cam_ptr(cam):
+    return None if cam is None else C.addressof(cam)
+
+
 def load_ensemble_protos():
-    """Declare the prototypes of include/eqf_ensemble.h on libeqf_hip.so."""
+    """Declare the prototypes of include/eqf_ensemble.h and include/eqf_ensemble_output.h on libeqf_hip.so."""
     lib = load_eqf_lib()
     if getattr(lib, "_ensemble_declared", None):
         return lib
@@ -36,6 +41,18 @@ def load_ensemble_protos():
         fn.restype = res
         fn.argtypes = args
     lib._ensemble_declared = sorted(protos)
+    # include/eqf_ensemble_output.h, a list of its own
+    cam_p = C.c_void_p
+    output_protos = {
+        "eqf_ensemble_measure": (C.c_int, [vp, cam_p, c_int_p, C.c_int, c_double_p]),
+        "eqf_ensemble_likelihood": (C.c_int, [vp, cam_p, c_int_p, c_double_p, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "eqf_ensemble_resample_weighted": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_int_p]),
+    }
+    for name, (res, args) in output_protos.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    lib._ensemble_output_declared = sorted(output_protos)
     return lib
 
 
@@ -135,6 +152,37 @@ class ParticleEnsemble:
     def resample(self, idx):
         idx = _i32(idx)
         self._chk(self.lib.eqf_ensemble_resample(self.h, len(idx), _ip(idx)))
+
+    # ---- include/eqf_ensemble_output.h: the measurement side, no context involved
+    def measure(self, cam, ids):
+        """(P, M, 2): cam.projectPoint of the points ids[M] of every particle"""
+        ids = _i32(ids)
+        out = np.zeros((self.size[0], len(ids), 2))
+        self._chk(self.lib.eqf_ensemble_measure(self.h, _cam_ptr(cam), _ip(ids), len(ids), _dp(out)))
+        return out
+
+    def likelihood(self, cam, ids, y, meas_var):
+        """(loglik[P], weights[P], logsumexp, ess) of the measurement y (M, 2) of the landmarks ids[M] under every particle; the weights are kept on the device"""
+        ids, y = _i32(ids), _f64(y).reshape(-1)
+        if y.size != 2 * len(ids):
+            raise ValueError(f"y holds {y.size} doubles, {2 * len(ids)} expected")
+        P = self.size[0]
+        ll, w, lse, ess = np.zeros(P), np.zeros(P), C.c_double(), C.c_double()
+        self._chk(self.lib.eqf_ensemble_likelihood(self.h, _cam_ptr(cam), _ip(ids), _dp(y), len(ids), float(meas_var), _dp(ll), _dp(w), C.byref(lse), C.byref(ess)))
+        return ll, w, lse.value, ess.value
+
+    def resample_weighted(self, u, weights=None):
+        """weightedResample with the uniforms u[P_new] by the kept weights (or weights[P]); returns the source index of every new particle"""
+        u = _f64(u).reshape(-1)
+        src = np.zeros(len(u), np.int32)
+        wp = None
+        if weights is not None:
+            weights = _f64(weights).reshape(-1)
+            if len(weights) != self.size[0]:
+                raise ValueError("weights must be (P,)")
+            wp = _dp(weights)
+        self._chk(self.lib.eqf_ensemble_resample_weighted(self.h, len(u), wp, _dp(u), _ip(src)))
+        return src
 
     def stats(self, reset=False):
         """(kernel launches, factorisations of Sigma) since the last reset"""

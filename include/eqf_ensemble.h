@@ -68,7 +68,8 @@ int eqf_ensemble_nees(eqf_ensemble* e, eqf_ctx* ctx, double* nees, double* mean)
 int eqf_ensemble_covariance(eqf_ensemble* e, eqf_ctx* ctx, double* cov);
 
 /* The ensemble becomes particles src[0 .. P_new) of the current one (any indices in [0, P), repeats allowed, 1 <= P_new <= capacity): a gather through the
- * second particle buffer. weightedResample's random draws and the measurement likelihood stay with the caller. */
+ * second particle buffer. weightedResample's random draws and the measurement likelihood stay with the caller (or: eqf_ensemble_output.h forms the likelihood
+ * and runs weightedResample on the device from the caller's uniforms). */
 int eqf_ensemble_resample(eqf_ensemble* e, int P_new, const int* src);
 
 /* kernel launches and factorisations of Sigma since the last reset (null outputs are skipped) */

@@ -2,7 +2,11 @@
 a planted filter (xi0 random, X = identity, Sigma0 = the fixture's initial covariance) of --landmarks N in --chart c, --particles P particles sampled by
 eqf_ensemble_sample from numpy's normals, and the four checks - initial distribution, true input (5 steps of 0.2 s at zero velocity), random input (5 steps of
 0.05 s) and output (measurement likelihood and weightedResample on the host from eqf_ensemble_get, eqf_ensemble_resample, one vision update) - each judged by the
-mean of ONE eqf_ensemble_nees call. The filter's side is the device's discrete Riccati step with zero gains, the observer step and the vision update, as in
+mean of ONE eqf_ensemble_nees call. --deviceOutput runs the output check through include/eqf_ensemble_output.h instead (eqf_ensemble_likelihood in the log
+domain, eqf_ensemble_resample_weighted from numpy's uniforms: no particle leaves the device); --measured M measures the first M landmarks only, on both sides
+(the filter's update takes the same ids), and --measVar v sets the measurement variance of both sides: the two knobs eqf_vision_update already has. With one of
+the three flags the output check also prints ess, the distinct particles, the mean NEES after resampling and the weighted mean sum_k w_k NEES_k before it.
+The filter's side is the device's discrete Riccati step with zero gains, the observer step and the vision update, as in
 tests/test_gpu_reference_tests.py. Prints one JSON line per check with every mean NEES seen and the reference's band (0.1 / 1.0 / 0.1 / 0.5 at N = 2, P = 1000)."""
 import argparse
 import json
@@ -59,10 +63,16 @@ def main():
     ap.add_argument("--particles", type=int, default=1000)
     ap.add_argument("--chart", choices=sorted(CHARTS), default="invdepth")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--checks", default="initial,true_input,random_input,output", help="which of the four checks to run")
+    ap.add_argument("--deviceOutput", action="store_true", help="the output check through eqf_ensemble_likelihood / eqf_ensemble_resample_weighted")
+    ap.add_argument("--measured", type=int, default=None, help="measure the first M landmarks only (both sides)")
+    ap.add_argument("--measVar", type=float, default=None, help="measurement variance of both sides (default measurementNoise^2)")
     a = ap.parse_args()
     N, P, chart = a.landmarks, a.particles, CHARTS[a.chart]
+    extended = a.deviceOutput or a.measured is not None or a.measVar is not None
+    M = N if a.measured is None else max(0, min(N, a.measured))
     n = 21 + 3 * N
-    for check in ("initial", "true_input", "random_input", "output"):
+    for check in [c for c in ("initial", "true_input", "random_input", "output") if c in a.checks.split(",")]:
         rng, s, core, q0 = planted(N, chart, a.seed)
         ens = ParticleEnsemble(core, P, N)
         t0 = time.perf_counter()
@@ -79,6 +89,32 @@ def main():
                 core.integrate_riccati_discrete(vel, dt, np.zeros(12), np.zeros(8))  # 0 * inputGain, 0 * stateGain (:110-111, :133-134)
                 core.integrate_observer(vel[None, :], np.array([dt]), True)
                 means.append(ens.nees()[1])
+        elif extended:
+            noise_var = s.measurementNoise**2  # the measurement is drawn as before; --measVar is what both sides believe
+            var = noise_var if a.measVar is None else a.measVar
+            ids = np.arange(M, dtype=np.int32)
+            cam = Camera.pinhole(FX, FY, CX, CY, 752, 480)
+            y = (pixels(q0) + np.sqrt(noise_var) * rng.normal(size=(N, 2)))[:M]
+            u = rng.uniform(size=P)
+            nees_before = ens.nees()[0]
+            if a.deviceOutput:
+                logw, w, lse, ess = ens.likelihood(cam, ids, y, var)
+                idx = ens.resample_weighted(u)
+            else:
+                _, _, p = ens.get()
+                err = (y[None, :, :] - pixels(p[:, :M])).reshape(P, -1)
+                logw = -0.5 * np.einsum("ki,ki->k", err, err) / var
+                w = np.exp(logw - logw.max())
+                w /= w.sum()
+                ess = 1.0 / np.sum(w * w)
+                idx = np.minimum(np.searchsorted(np.cumsum(w), (u + np.arange(P)) / P, side="left"), P - 1).astype(np.int32)
+                ens.resample(idx)
+            if M > 0:
+                core.vision_update(cam, ids, y.reshape(-1), var, True, False)
+            means.append(ens.nees()[1])
+            print(json.dumps({"check": check, "route": "device" if a.deviceOutput else "host", "measured": M, "meas_var": var, "ess": round(float(ess), 3),
+                              "distinct_particles_after_resampling": int(len(set(idx.tolist()))), "mean_nees_after_resampling": round(float(means[-1]), 6),
+                              "weighted_mean_nees_before_resampling": round(float(np.sum(w * nees_before)), 6)}), flush=True)
         else:
             var = s.measurementNoise**2
             ids = np.arange(N, dtype=np.int32)
