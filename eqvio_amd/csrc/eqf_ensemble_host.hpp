@@ -301,17 +301,11 @@ int eqf_ensemble_get(eqf_ensemble* e, int* ids, double* sensor, double* p, int c
     return P;
 }
 
-int eqf_ensemble_sample(eqf_ensemble* e, eqf_ctx* c, int P, const double* xi) {
-    EQFCHK(ens_check_ctx(e, c));
-    if (!xi || P < 1)
-        return EQF_E_BAD_ARG;
-    if (P > e->Pcap || c->N > e->Ncap)
-        return EQF_E_CAPACITY;
-    EQFCHK(enter(c));
-    EQFCHK(join_observer(c));
-    const EnsCountersKept keep(c);
+namespace {
+// eqf_ensemble_sample behind its copy of xi: d_xi holds the n x P standard normals (uploaded, or generated there by eqf_ensemble_sample_seeded); the context is
+// entered and its counters are kept by the caller
+int ens_sample_from_xi(eqf_ensemble* e, eqf_ctx* c, int P) {
     const int N = c->N, n = c->n(), np = n + (n & 1);
-    HIPCHK(hipMemcpy(e->d_xi, xi, sizeof(double) * (size_t)n * P, hipMemcpyHostToDevice));
     // L: the chain on [Sigma ; Sigma] leaves Sigma L^-T = L in rows [np, 2 np) of W
     EQFCHK(ens_factorise(e, c, np, 1));
     hipLaunchKernelGGL(k_ens_trmm, dim3(blocks(n, 16), blocks(P, 64)), dim3(256), 0, c->stream, n, np, P, e->ldz, e->d_W, e->d_xi, e->d_E, e->ldp);
@@ -341,6 +335,20 @@ int eqf_ensemble_sample(eqf_ensemble* e, eqf_ctx* c, int P, const double* xi) {
     e->ids = c->ids;
     e->sensor.swap(sens);
     return 0;
+}
+} // namespace
+
+int eqf_ensemble_sample(eqf_ensemble* e, eqf_ctx* c, int P, const double* xi) {
+    EQFCHK(ens_check_ctx(e, c));
+    if (!xi || P < 1)
+        return EQF_E_BAD_ARG;
+    if (P > e->Pcap || c->N > e->Ncap)
+        return EQF_E_CAPACITY;
+    EQFCHK(enter(c));
+    EQFCHK(join_observer(c));
+    const EnsCountersKept keep(c);
+    HIPCHK(hipMemcpy(e->d_xi, xi, sizeof(double) * (size_t)c->n() * P, hipMemcpyHostToDevice));
+    return ens_sample_from_xi(e, c, P);
 }
 
 int eqf_ensemble_integrate(eqf_ensemble* e, const double* imu13, double dt, const double* imu_offset) {

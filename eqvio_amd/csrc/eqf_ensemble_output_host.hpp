@@ -93,18 +93,12 @@ int eqf_ensemble_likelihood(eqf_ensemble* e, const eqvio_camera* cam, const int*
     return 0;
 }
 
-int eqf_ensemble_resample_weighted(eqf_ensemble* e, int P_new, const double* weights, const double* u, int* src_out) {
-    if (!e || !u || P_new < 1 || e->P < 1)
-        return EQF_E_BAD_ARG;
-    if (P_new > e->Pcap)
-        return EQF_E_CAPACITY;
-    const int P = e->P, N = e->N;
-    for (int k = 0; k < P_new; ++k)
-        if (!(u[k] >= 0.0 && u[k] < 1.0))
-            return EQF_E_BAD_ARG;
+namespace {
+// the weights eqf_ensemble_resample_weighted picks by: the caller's (finite, >= 0, not all zero) or the kept ones
+int ens_weights_ok(const eqf_ensemble* e, const double* weights) {
     if (weights) {
         double s = 0.0;
-        for (int j = 0; j < P; ++j) {
+        for (int j = 0; j < e->P; ++j) {
             if (!(weights[j] >= 0.0) || !std::isfinite(weights[j]))
                 return EQF_E_BAD_ARG;
             s += weights[j];
@@ -113,9 +107,11 @@ int eqf_ensemble_resample_weighted(eqf_ensemble* e, int P_new, const double* wei
             return EQF_E_BAD_ARG;
     } else if (!e->w_valid)
         return EQF_E_BAD_ARG;
-    HIPCHK(hipSetDevice(e->device));
-    e->w_valid = false;
-    HIPCHK(hipMemcpy(e->d_yu, u, sizeof(double) * P_new, hipMemcpyHostToDevice));
+    return 0;
+}
+// eqf_ensemble_resample_weighted behind its copy of u: d_yu holds the P_new uniforms (uploaded, or generated there by eqf_ensemble_resample_weighted_seeded)
+int ens_resample_from_u(eqf_ensemble* e, int P_new, const double* weights, int* src_out) {
+    const int P = e->P, N = e->N;
     if (weights) {
         double* d_w = e->d_lw + 4 + P;
         HIPCHK(hipMemcpy(d_w, weights, sizeof(double) * P, hipMemcpyHostToDevice));
@@ -144,4 +140,20 @@ int eqf_ensemble_resample_weighted(eqf_ensemble* e, int P_new, const double* wei
     if (src_out)
         std::copy(src.begin(), src.end(), src_out);
     return 0;
+}
+} // namespace
+
+int eqf_ensemble_resample_weighted(eqf_ensemble* e, int P_new, const double* weights, const double* u, int* src_out) {
+    if (!e || !u || P_new < 1 || e->P < 1)
+        return EQF_E_BAD_ARG;
+    if (P_new > e->Pcap)
+        return EQF_E_CAPACITY;
+    for (int k = 0; k < P_new; ++k)
+        if (!(u[k] >= 0.0 && u[k] < 1.0))
+            return EQF_E_BAD_ARG;
+    EQFCHK(ens_weights_ok(e, weights));
+    HIPCHK(hipSetDevice(e->device));
+    e->w_valid = false;
+    HIPCHK(hipMemcpy(e->d_yu, u, sizeof(double) * P_new, hipMemcpyHostToDevice));
+    return ens_resample_from_u(e, P_new, weights, src_out);
 }

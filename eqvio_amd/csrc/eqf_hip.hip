@@ -8,6 +8,7 @@
 #include "eqf_fork.hpp"
 #include "eqf_ensemble.hpp"
 #include "eqf_ensemble_output.hpp"
+#include "eqf_ensemble_random.hpp"
 #include "eqf_batch.h"
 #include "host_prof.hpp"
 #include <algorithm>
@@ -4167,3 +4168,5 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 #include "eqf_ensemble_host.hpp"
 // ... and its measurement side (include/eqf_ensemble_output.h), which takes no context
 #include "eqf_ensemble_output_host.hpp"
+// ... and its seeded draws (include/eqf_ensemble_random.h), generated on the device
+#include "eqf_ensemble_random_host.hpp"

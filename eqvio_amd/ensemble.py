@@ -3,7 +3,8 @@
 ParticleEnsemble holds P hypotheses of the true state on the device and judges them against one context (an EqfCore, or the core of a VIOFilter):
 one factorisation of Sigma per nees() / sample() call, whatever P is. numpy arrays in, numpy arrays out, errors raised loudly (EqfError with the
 library's code). The prototypes are declared in a list of their own (_ensemble_declared), apart from the loader's _declared list of eqf_hip.h; those of
-include/eqf_ensemble_output.h (measure, likelihood, resample_weighted: the measurement side, on the device) in _ensemble_output_declared.
+include/eqf_ensemble_output.h (measure, likelihood, resample_weighted: the measurement side, on the device) in _ensemble_output_declared, those of
+include/eqf_ensemble_random.h (the seeded draws, generated on the device) in _ensemble_random_declared.
 """
 import ctypes as C
 
@@ -17,7 +18,7 @@ def _cam_ptr(cam):
 
 
 def load_ensemble_protos():
-    """Declare the prototypes of include/eqf_ensemble.h and include/eqf_ensemble_output.h on libeqf_hip.so."""
+    """Declare the prototypes of include/eqf_ensemble.h, include/eqf_ensemble_output.h and include/eqf_ensemble_random.h on libeqf_hip.so."""
     lib = load_eqf_lib()
     if getattr(lib, "_ensemble_declared", None):
         return lib
@@ -53,7 +54,26 @@ def load_ensemble_protos():
         fn.restype = res
         fn.argtypes = args
     lib._ensemble_output_declared = sorted(output_protos)
+    # include/eqf_ensemble_random.h, a third list
+    u64 = C.c_ulonglong
+    random_protos = {
+        "eqf_ensemble_normals": (C.c_int, [vp, u64, u64, C.c_int, C.c_int, c_double_p]),
+        "eqf_ensemble_uniforms": (C.c_int, [vp, u64, u64, C.c_int, c_double_p]),
+        "eqf_ensemble_sample_seeded": (C.c_int, [vp, vp, C.c_int, u64, u64]),
+        "eqf_ensemble_resample_weighted_seeded": (C.c_int, [vp, C.c_int, c_double_p, u64, u64, c_int_p]),
+        "eqf_ensemble_integrate_seeded": (C.c_int, [vp, c_double_p, C.c_double, c_double_p, u64, u64]),
+    }
+    for name, (res, args) in random_protos.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    lib._ensemble_random_declared = sorted(random_protos)
     return lib
+
+
+def _u64(v):
+    """a seed or a stream: a Python int taken modulo 2^64"""
+    return int(v) & 0xFFFFFFFFFFFFFFFF
 
 
 class ParticleEnsemble:
@@ -183,6 +203,46 @@ class ParticleEnsemble:
             wp = _dp(weights)
         self._chk(self.lib.eqf_ensemble_resample_weighted(self.h, len(u), wp, _dp(u), _ip(src)))
         return src
+
+    # ---- include/eqf_ensemble_random.h: seeded draws generated on the device; seeds and streams are ints taken modulo 2^64
+    def normals(self, seed, stream, rows, P):
+        """(rows, P) standard normals of (seed, stream): entry (r, k) depends on seed, stream, r and k alone"""
+        out = np.zeros((max(int(rows), 0), max(int(P), 0)), order="F")
+        self._chk(self.lib.eqf_ensemble_normals(self.h, _u64(seed), _u64(stream), int(rows), int(P), out.ctypes.data_as(c_double_p)))
+        return out
+
+    def uniforms(self, seed, stream, count):
+        """count uniforms in (0, 1) of (seed, stream)"""
+        out = np.zeros(max(int(count), 0))
+        self._chk(self.lib.eqf_ensemble_uniforms(self.h, _u64(seed), _u64(stream), int(count), _dp(out)))
+        return out
+
+    def sample_seeded(self, P, seed, stream):
+        """sample(normals(seed, stream, n, P)) without the upload: the normals are generated where sample reads them"""
+        self._chk(self.lib.eqf_ensemble_sample_seeded(self.h, self._ctx(), int(P), _u64(seed), _u64(stream)))
+
+    def resample_weighted_seeded(self, P_new, seed, stream, weights=None):
+        """resample_weighted(uniforms(seed, stream, P_new), weights); returns the source index of every new particle"""
+        src = np.zeros(max(int(P_new), 0), np.int32)
+        wp = None
+        if weights is not None:
+            weights = _f64(weights).reshape(-1)
+            if len(weights) != self.size[0]:
+                raise ValueError("weights must be (P,)")
+            wp = _dp(weights)
+        self._chk(self.lib.eqf_ensemble_resample_weighted_seeded(self.h, int(P_new), wp, _u64(seed), _u64(stream), _ip(src)))
+        return src
+
+    def integrate_seeded(self, imu, dt, sigma6, seed, stream):
+        """integrate(imu, dt, offsets = (sigma6[:, None] * normals(seed, stream, 6, P)).T); sigma6: gyr xyz, acc xyz standard deviations (None is refused)"""
+        imu = _f64(imu)
+        sp = None
+        if sigma6 is not None:
+            sigma6 = _f64(sigma6).reshape(-1)
+            if len(sigma6) != 6:
+                raise ValueError("sigma6 must hold six standard deviations")
+            sp = _dp(sigma6)
+        self._chk(self.lib.eqf_ensemble_integrate_seeded(self.h, _dp(imu), float(dt), sp, _u64(seed), _u64(stream)))
 
     def stats(self, reset=False):
         """(kernel launches, factorisations of Sigma) since the last reset"""

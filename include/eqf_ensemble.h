@@ -22,6 +22,7 @@
  *  - the kernels of this header do not communicate between workgroups (no flags, no spinning, no co-residency); the factorisation is the launch chain
  *    (one launch per 32-column panel), never the look-ahead kernel.
  * An ensemble is bound to one device and must be used from one thread at a time; every call returns with its work complete.
+ * The random draws of sample, integrate and weighted resampling can be generated on the device from a seed: eqf_ensemble_random.h.
  */
 #ifndef EQF_ENSEMBLE_H
 #define EQF_ENSEMBLE_H

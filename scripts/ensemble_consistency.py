@@ -7,7 +7,11 @@ domain, eqf_ensemble_resample_weighted from numpy's uniforms: no particle leaves
 (the filter's update takes the same ids), and --measVar v sets the measurement variance of both sides: the two knobs eqf_vision_update already has. With one of
 the three flags the output check also prints ess, the distinct particles, the mean NEES after resampling and the weighted mean sum_k w_k NEES_k before it.
 The filter's side is the device's discrete Riccati step with zero gains, the observer step and the vision update, as in
-tests/test_gpu_reference_tests.py. Prints one JSON line per check with every mean NEES seen and the reference's band (0.1 / 1.0 / 0.1 / 0.5 at N = 2, P = 1000)."""
+tests/test_gpu_reference_tests.py. --deviceRandom SEED draws every per-particle random number on the device through include/eqf_ensemble_random.h, one stream
+per draw, numbered from 0 in the order the script draws: the particles (eqf_ensemble_sample_seeded), the resampling uniforms (eqf_ensemble_resample_weighted_seeded;
+the flag implies --deviceOutput) and, in the random-input check, an input disturbance per particle and step (eqf_ensemble_integrate_seeded with the standard
+deviations sqrt(inputGain / dt) of gyr and acc - the noisy input the reference samples at :129 - against a filter whose Riccati step then carries that input gain
+instead of zero). numpy keeps drawing the planted filter and the measurement noise. Prints one JSON line per check with every mean NEES seen and the reference's band (0.1 / 1.0 / 0.1 / 0.5 at N = 2, P = 1000)."""
 import argparse
 import json
 import os
@@ -65,10 +69,14 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--checks", default="initial,true_input,random_input,output", help="which of the four checks to run")
     ap.add_argument("--deviceOutput", action="store_true", help="the output check through eqf_ensemble_likelihood / eqf_ensemble_resample_weighted")
+    ap.add_argument("--deviceRandom", type=int, default=None, metavar="SEED", help="draw particles, input disturbances and resampling uniforms on the device from this seed")
     ap.add_argument("--measured", type=int, default=None, help="measure the first M landmarks only (both sides)")
     ap.add_argument("--measVar", type=float, default=None, help="measurement variance of both sides (default measurementNoise^2)")
     a = ap.parse_args()
     N, P, chart = a.landmarks, a.particles, CHARTS[a.chart]
+    seeded = a.deviceRandom is not None
+    a.deviceOutput = a.deviceOutput or seeded
+    streams = iter(range(1 << 30))  # one stream per draw, in the order of the draws
     extended = a.deviceOutput or a.measured is not None or a.measVar is not None
     M = N if a.measured is None else max(0, min(N, a.measured))
     n = 21 + 3 * N
@@ -76,7 +84,10 @@ def main():
         rng, s, core, q0 = planted(N, chart, a.seed)
         ens = ParticleEnsemble(core, P, N)
         t0 = time.perf_counter()
-        ens.sample(rng.normal(size=(n, P)))
+        if seeded:
+            ens.sample_seeded(P, a.deviceRandom, next(streams))
+        else:
+            ens.sample(rng.normal(size=(n, P)))
         means = []
         if check == "initial":
             means.append(ens.nees()[1])
@@ -84,9 +95,15 @@ def main():
             vel, dt = np.zeros(13), 0.2
             if check == "random_input":
                 vel[1:7], dt = rng.uniform(-1, 1, 6), 0.05
+            gain = np.zeros(12)  # 0 * inputGain, 0 * stateGain (:110-111, :133-134)
+            if seeded and check == "random_input":
+                gain[0:6] = s.input_gain_diag12()[0:6]  # the gyr and acc noise the particles are driven with; no bias walk
             for _ in range(5):
-                ens.integrate(vel, dt)
-                core.integrate_riccati_discrete(vel, dt, np.zeros(12), np.zeros(8))  # 0 * inputGain, 0 * stateGain (:110-111, :133-134)
+                if seeded and check == "random_input":
+                    ens.integrate_seeded(vel, dt, np.sqrt(gain[0:6] / dt), a.deviceRandom, next(streams))
+                else:
+                    ens.integrate(vel, dt)
+                core.integrate_riccati_discrete(vel, dt, gain, np.zeros(8))
                 core.integrate_observer(vel[None, :], np.array([dt]), True)
                 means.append(ens.nees()[1])
         elif extended:
@@ -95,11 +112,11 @@ def main():
             ids = np.arange(M, dtype=np.int32)
             cam = Camera.pinhole(FX, FY, CX, CY, 752, 480)
             y = (pixels(q0) + np.sqrt(noise_var) * rng.normal(size=(N, 2)))[:M]
-            u = rng.uniform(size=P)
+            u = None if seeded else rng.uniform(size=P)
             nees_before = ens.nees()[0]
             if a.deviceOutput:
                 logw, w, lse, ess = ens.likelihood(cam, ids, y, var)
-                idx = ens.resample_weighted(u)
+                idx = ens.resample_weighted_seeded(P, a.deviceRandom, next(streams)) if seeded else ens.resample_weighted(u)
             else:
                 _, _, p = ens.get()
                 err = (y[None, :, :] - pixels(p[:, :M])).reshape(P, -1)
@@ -112,7 +129,7 @@ def main():
             if M > 0:
                 core.vision_update(cam, ids, y.reshape(-1), var, True, False)
             means.append(ens.nees()[1])
-            print(json.dumps({"check": check, "route": "device" if a.deviceOutput else "host", "measured": M, "meas_var": var, "ess": round(float(ess), 3),
+            print(json.dumps({"check": check, "route": ("device, seeded" if seeded else "device") if a.deviceOutput else "host", "measured": M, "meas_var": var, "ess": round(float(ess), 3),
                               "distinct_particles_after_resampling": int(len(set(idx.tolist()))), "mean_nees_after_resampling": round(float(means[-1]), 6),
                               "weighted_mean_nees_before_resampling": round(float(np.sum(w * nees_before)), 6)}), flush=True)
         else:
