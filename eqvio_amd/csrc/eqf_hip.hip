@@ -4170,3 +4170,6 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 #include "eqf_ensemble_output_host.hpp"
 // ... and its seeded draws (include/eqf_ensemble_random.h), generated on the device
 #include "eqf_ensemble_random_host.hpp"
+// Particle ensembles against batch slots (include/eqf_batch_ensemble.h): the kernels and the host side, behind the batch and the single-filter ensemble
+#include "eqf_batch_ensemble.hpp"
+#include "eqf_batch_ensemble_host.hpp"

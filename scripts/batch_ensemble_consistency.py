@@ -1,0 +1,75 @@
+"""The reference's initial-distribution and true-input checks (test/test_FilterStatistics.cpp:90-118) for a whole filter batch at once: nine slots - the
+three charts times the three Riccati modes (fast, accurate, discrete state matrix) - are planted with FilterStatisticsTest's filter at N landmarks
+(tests/ensemble_cases.py's StatFixture: its variances, 0 x inputGain and 0 x stateGain as the true-input check sets them, removeLostLandmarks off), ONE
+eqf_bens_sample_seeded call draws P particles from every slot's Sigma, and every frame is one propagation-only step per mode (no measurement) with the true
+input, ONE eqf_bens_integrate call with the same sample and ONE eqf_bens_nees call. Prints every slot's mean NEES per frame (frame 0: the initial check, band
+0.1 of 1; frames 1 .. 5: the true-input check, band 1.0 of 1) and one JSON line with the worst distance from 1 per Riccati mode. The reference runs its true-input
+check with the discrete state matrix; the fast and the accurate mode linearise a 0.2 s step of free fall and are reported for what they are."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: F401,E402  (the HIP runtime of the torch wheel first, as bench.py)
+
+from ensemble_cases import CHART_NAMES, PINHOLE, STAT_BANDS, StatFixture  # noqa: E402
+from eqvio_amd.batch import BatchCore  # noqa: E402
+from eqvio_amd.batch_ensemble import BatchEnsemble  # noqa: E402
+from eqvio_amd.capi import Camera  # noqa: E402
+
+MODES = ("fast", "accurate", "discrete")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--landmarks", type=int, default=2)
+    ap.add_argument("--particles", type=int, default=1000)
+    ap.add_argument("--frames", type=int, default=5)
+    ap.add_argument("--dt", type=float, default=0.2)
+    ap.add_argument("--seed", type=int, default=2026)
+    a = ap.parse_args()
+    f = StatFixture(a.landmarks, a.particles, 1)
+    s = f.settings
+    s.fastRiccati, s.removeLostLandmarks = 1, 0
+    B = 9
+    core = BatchCore(s, B)
+    label = []
+    for k in range(B):
+        chart, mode = k // 3, MODES[k % 3]
+        core.set_slot_chart(k, chart)
+        core.set_state(k, f.xi0f, f.Xsf, f.ids, f.q0, f.Q)
+        core.set_sigma(k, f.sigma0)
+        label.append(f"{CHART_NAMES[chart]}/{mode}")
+    ens = BatchEnsemble(core, a.particles)
+    slots = list(range(B))
+    assert not any(ens.sample_seeded([(k, a.particles, a.seed, k) for k in slots]))
+    cam = Camera.pinhole(*PINHOLE, 752, 480)
+    vel, none_i, none_d = f.true_vel, np.zeros(0, np.int32), np.zeros(0)
+    rows = []
+
+    def judge(frame):
+        _, mean, status = ens.nees(slots)
+        assert not any(status), status
+        rows.append([float(v) for v in mean])
+        print(f"frame {frame}: " + "  ".join(f"{label[k]} {mean[k]:.4f}" for k in slots), flush=True)
+
+    judge(0)
+    for frame in range(1, a.frames + 1):
+        for mode, step in zip(MODES, (core.step, core.step_accurate, core.step_discrete)):
+            entries = [(k, cam, vel[None, :], np.array([a.dt]), none_i, none_d, vel, a.dt) for k in slots if MODES[k % 3] == mode]
+            assert not any(step(entries))
+        assert not any(ens.integrate([(k, vel, a.dt) for k in slots]))
+        judge(frame)
+    arr = np.array(rows)
+    print(json.dumps({"metric": "batch_ensemble_consistency", "N": a.landmarks, "P": a.particles, "slots": label, "initial_worst": float(np.max(np.abs(arr[0] - 1.0))),
+                      "initial_band": STAT_BANDS["initial"], "true_input_worst": {m: float(np.max(np.abs(arr[1:, i::3] - 1.0))) for i, m in enumerate(MODES)}, "true_input_band": STAT_BANDS["true_input"],
+                      "launches_factorisations": ens.stats()}))
+
+
+if __name__ == "__main__":
+    main()
