@@ -4,7 +4,10 @@ BatchEnsemble(batch, max_particles) holds one cloud of up to max_particles hypot
 VIOFilterBatch through core_handle()), entirely on the device. One call samples a cloud from every listed slot's Sigma, one call moves every listed cloud with
 its slot's IMU sample, one call returns every particle's NEES against its slot; launches and copies per call depend on neither the entries nor any P. numpy
 arrays in and out; the compute calls return per-entry status codes, a failing call raises EqfError. The prototypes are declared in a list of their own
-(_batch_ensemble_declared)."""
+(_batch_ensemble_declared).
+
+The measurement side, include/eqf_batch_ensemble_output.h - likelihood, resample_weighted_seeded, covariance per slot - is declared in a second list
+(_batch_ensemble_output_declared)."""
 import ctypes as C
 
 import numpy as np
@@ -19,6 +22,17 @@ class BensSampleEntry(C.Structure):
 
 class BensIntegrateEntry(C.Structure):
     _fields_ = [("slot", C.c_int), ("imu13", c_double_p), ("dt", C.c_double), ("sigma6", c_double_p), ("seed", C.c_ulonglong), ("stream", C.c_ulonglong)]
+
+
+class BensLikelihoodEntry(C.Structure):
+    _fields_ = [("slot", C.c_int), ("cam", C.c_void_p), ("ids", c_int_p), ("y", c_double_p), ("M", C.c_int), ("meas_var", C.c_double)]
+
+
+class BensResampleEntry(C.Structure):
+    _fields_ = [("slot", C.c_int), ("P_new", C.c_int), ("seed", C.c_ulonglong), ("stream", C.c_ulonglong)]
+
+
+NMAX = 213  # 21 + 3 * 64: eqf_bens_covariance's block per entry is NMAX * NMAX doubles
 
 
 def load_batch_ensemble_protos():
@@ -44,6 +58,16 @@ def load_batch_ensemble_protos():
         fn.restype = res
         fn.argtypes = args
     lib._batch_ensemble_declared = sorted(protos)
+    output_protos = {
+        "eqf_bens_likelihood": (C.c_int, [vp, C.c_int, P(BensLikelihoodEntry), c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+        "eqf_bens_resample_weighted_seeded": (C.c_int, [vp, C.c_int, P(BensResampleEntry), c_int_p, c_int_p]),
+        "eqf_bens_covariance": (C.c_int, [vp, C.c_int, c_int_p, c_double_p, c_int_p]),
+    }
+    for name, (res, args) in output_protos.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    lib._batch_ensemble_output_declared = sorted(output_protos)
     return lib
 
 
@@ -156,6 +180,62 @@ class BatchEnsemble:
         status = np.zeros(max(n, 1), np.int32)
         self._chk(self.lib.eqf_bens_nees(self.h, n, _ip(slots), _dp(vals), _dp(mean), _ip(status)))
         return vals[:n], mean[:n], [int(v) for v in status[:n]]
+
+    def likelihood(self, entries, out=None):
+        """entries: list of (slot, cam, ids, y, meas_var) - one measurement per slot: cam a capi.Camera, ids[M] the measured landmark ids (matched by id to the
+        cloud's), y (M, 2). Returns (loglik (count, max_particles), weights (count, max_particles), logsumexp[count], ess[count], status[count]): row e holds the
+        slot's P values, the rest of the row and everything of a refused entry are left as they were (NaN in fresh arrays; pass `out` = (loglik, weights,
+        logsumexp, ess) to see that they are not written). The normalised weights are kept per slot on the device for resample_weighted_seeded."""
+        n = len(entries)
+        arr = (BensLikelihoodEntry * max(n, 1))()
+        keep = []
+        for t, (slot, cam, ids, y, var) in enumerate(entries):
+            ids = None if ids is None else _i32(ids)
+            y = None if y is None else _f64(y).reshape(-1)
+            M = 0 if ids is None else len(ids)
+            if y is not None and ids is not None and y.size != 2 * M:
+                raise ValueError(f"y holds {y.size} doubles, {2 * M} expected")
+            keep.append((cam, ids, y))
+            arr[t].slot, arr[t].M, arr[t].meas_var = int(slot), M, float(var)
+            arr[t].cam = None if cam is None else C.cast(C.pointer(cam), C.c_void_p)
+            arr[t].ids = None if ids is None else _ip(ids)
+            arr[t].y = None if y is None else _dp(y)
+        if out is None:
+            m = max(n, 1)
+            out = (np.full((m, self.max_particles), np.nan), np.full((m, self.max_particles), np.nan), np.full(m, np.nan), np.full(m, np.nan))
+        ll, w, lse, ess = out
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqf_bens_likelihood(self.h, n, arr, _dp(ll), _dp(w), _dp(lse), _dp(ess), _ip(status)))
+        return ll[:n], w[:n], lse[:n], ess[:n], [int(v) for v in status[:n]]
+
+    def resample_weighted_seeded(self, entries, out=None):
+        """entries: list of (slot, P_new, seed, stream): weightedResample on the slot's kept weights with uniforms(seed, stream, P_new) of
+        include/eqf_ensemble_random.h, generated on the device; the slot's cloud becomes the P_new chosen particles. Returns (src (count, max_particles) int32,
+        status[count]): row e holds the P_new source indices, the rest (and the rows of refused entries) are left as they were (-1 in a fresh array)."""
+        n = len(entries)
+        arr = (BensResampleEntry * max(n, 1))()
+        for t, (slot, P_new, seed, stream) in enumerate(entries):
+            arr[t].slot, arr[t].P_new, arr[t].seed, arr[t].stream = int(slot), int(P_new), _u64(seed), _u64(stream)
+        src = np.full((max(n, 1), self.max_particles), -1, np.int32) if out is None else out
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqf_bens_resample_weighted_seeded(self.h, n, arr, _ip(src), _ip(status)))
+        return src[:n], [int(v) for v in status[:n]]
+
+    def covariance(self, slots):
+        """([C_e (n_e, n_e) or None for a refused entry], status[count]): estimateParticleCovariance of every listed slot's cloud in the slot's chart"""
+        slots = _i32(slots)
+        n = len(slots)
+        buf = np.full(max(n, 1) * NMAX * NMAX, np.nan)
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqf_bens_covariance(self.h, n, _ip(slots), _dp(buf), _ip(status)))
+        mats = []
+        for e in range(n):
+            if status[e]:
+                mats.append(None)
+                continue
+            d = self._slot_n(slots[e])
+            mats.append(buf[e * NMAX * NMAX:e * NMAX * NMAX + d * d].reshape(d, d).T.copy())
+        return mats, [int(v) for v in status[:n]]
 
     def stats(self, reset=False):
         """(kernel launches, factorisations of Sigma) since the last reset"""

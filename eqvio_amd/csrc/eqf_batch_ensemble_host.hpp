@@ -8,6 +8,11 @@
 #pragma once
 #include "eqf_batch_ensemble.h"
 
+namespace {
+struct BensOutState; // the device memory of include/eqf_batch_ensemble_output.h's calls (eqf_batch_ensemble_output_host.hpp), made at their first use
+void bens_output_free(BensOutState* s);
+} // namespace
+
 struct eqf_bens {
     struct Cloud {
         int P = 0, N = 0;
@@ -22,6 +27,8 @@ struct eqf_bens {
     std::vector<Cloud> c;
     long launches = 0, factorisations = 0;
     std::vector<void*> own;
+    std::vector<char> w_valid;  // per slot: eqf_bens_likelihood's kept weights stand; every call that changes the slot's cloud clears it
+    BensOutState* os = nullptr;
 };
 
 namespace {
@@ -98,6 +105,7 @@ int eqf_bens_create(eqf_bens** out, eqf_batch* batch, int max_particles) {
     e->b = batch;
     e->Pcap = max_particles;
     e->c.resize(batch->slots);
+    e->w_valid.assign(batch->slots, 0);
     BensBufs& eb = e->eb;
     eb.ldp = pick_ld(max_particles);
     const size_t B = (size_t)batch->slots, ldp = (size_t)eb.ldp;
@@ -129,6 +137,7 @@ void eqf_bens_destroy(eqf_bens* e) {
         (void)hipFree(p);
     e->in.release();
     e->flag.release();
+    bens_output_free(e->os);
     delete e;
 }
 
@@ -186,6 +195,7 @@ int eqf_bens_set(eqf_bens* e, int slot, int P, int N, const int* ids, const doub
     e->c[slot].P = P;
     e->c[slot].N = N;
     e->c[slot].ids.assign(ids, ids + N);
+    e->w_valid[slot] = 0;
     return 0;
 }
 
@@ -277,6 +287,7 @@ int eqf_bens_sample_seeded(eqf_bens* e, int count, const eqf_bens_sample_entry* 
         e->c[slot].P = e->in.h[q].P;
         e->c[slot].N = e->in.h[q].N;
         e->c[slot].ids = e->b->s[slot].ids;
+        e->w_valid[slot] = 0;
     }
     return 0;
 }
@@ -311,6 +322,7 @@ int eqf_bens_integrate(eqf_bens* e, int count, const eqf_bens_integrate_entry* e
         }
         status[t] = 0;
         scr.accept(t);
+        e->w_valid[ie.slot] = 0;
     }
     const int nin = scr.nin;
     if (nin == 0)

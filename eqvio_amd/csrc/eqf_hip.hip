@@ -4173,3 +4173,6 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 // Particle ensembles against batch slots (include/eqf_batch_ensemble.h): the kernels and the host side, behind the batch and the single-filter ensemble
 #include "eqf_batch_ensemble.hpp"
 #include "eqf_batch_ensemble_host.hpp"
+// ... and their measurement side (include/eqf_batch_ensemble_output.h)
+#include "eqf_batch_ensemble_output.hpp"
+#include "eqf_batch_ensemble_output_host.hpp"

@@ -4,7 +4,12 @@ three charts times the three Riccati modes (fast, accurate, discrete state matri
 eqf_bens_sample_seeded call draws P particles from every slot's Sigma, and every frame is one propagation-only step per mode (no measurement) with the true
 input, ONE eqf_bens_integrate call with the same sample and ONE eqf_bens_nees call. Prints every slot's mean NEES per frame (frame 0: the initial check, band
 0.1 of 1; frames 1 .. 5: the true-input check, band 1.0 of 1) and one JSON line with the worst distance from 1 per Riccati mode. The reference runs its true-input
-check with the discrete state matrix; the fast and the accurate mode linearise a 0.2 s step of free fall and are reported for what they are."""
+check with the discrete state matrix; the fast and the accurate mode linearise a 0.2 s step of free fall and are reported for what they are.
+
+--checks output runs the reference's fourth check instead (outputDistribution, :140-168; the knobs of scripts/ensemble_consistency.py --deviceOutput): after
+sampling, every slot gets a measurement of its xi0's first --measured landmarks with pixel noise of variance --measVar (numpy), then ONE eqf_bens_likelihood
+call, ONE eqf_bens_resample_weighted_seeded call, ONE vision step of the batch with that measurement (no IMU sample) and ONE eqf_bens_nees call. Prints ess, the
+distinct particles and the mean NEES per slot (band 0.5 of 1) and one JSON line."""
 import argparse
 import json
 import os
@@ -25,6 +30,35 @@ from eqvio_amd.capi import Camera  # noqa: E402
 MODES = ("fast", "accurate", "discrete")
 
 
+def output_check(a, f, core, ens, cam, slots, label):
+    """the reference's outputDistribution for every slot: likelihood, weightedResample, the filter's vision update, mean NEES"""
+    from eqvio_ref import Camera as RCam  # noqa: E402
+    from ensemble_cases import R  # noqa: E402
+
+    M = a.landmarks if a.measured is None else min(a.measured, a.landmarks)
+    var = f.settings.measurementNoise**2
+    rng = np.random.default_rng([a.seed, 77])
+    y0 = R.measure(f.xi0, RCam(0, *PINHOLE))
+    mids = np.ascontiguousarray(f.ids[:M])
+    meas = [np.array([y0[int(i)] for i in mids], float).reshape(M, 2) + np.sqrt(var) * rng.normal(size=(M, 2)) for _ in slots]
+    _, mean0, status = ens.nees(slots)
+    assert not any(status), status
+    _, w, _, ess, status = ens.likelihood([(k, cam, mids, meas[k], var) for k in slots])
+    assert not any(status), status
+    src, status = ens.resample_weighted_seeded([(k, a.particles, a.seed, 100 + k) for k in slots])
+    assert not any(status), status
+    none13, none = np.zeros((0, 13)), np.zeros(0)
+    assert not any(core.step_accurate([(k, cam, none13, none, mids, meas[k]) for k in slots]))  # no IMU sample: the vision update alone, whatever the slot's Riccati mode
+    _, mean, status = ens.nees(slots)
+    assert not any(status), status
+    distinct = [len(set(src[k, :a.particles].tolist())) for k in slots]
+    for k in slots:
+        print(f"{label[k]}: ess {ess[k]:.1f} distinct {distinct[k]} mean NEES before {mean0[k]:.4f} after {mean[k]:.4f}", flush=True)
+    print(json.dumps({"metric": "batch_ensemble_output_consistency", "N": a.landmarks, "P": a.particles, "measured": M, "meas_var": var, "slots": label,
+                      "ess": [float(v) for v in ess], "distinct": distinct, "mean_nees": [float(v) for v in mean], "worst": float(np.max(np.abs(mean - 1.0))),
+                      "band": STAT_BANDS["output"], "launches_factorisations": ens.stats()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--landmarks", type=int, default=2)
@@ -32,9 +66,14 @@ def main():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--dt", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=2026)
+    ap.add_argument("--checks", choices=("propagation", "output"), default="propagation")
+    ap.add_argument("--measured", type=int, default=None, help="--checks output: measured landmarks (default: all)")
+    ap.add_argument("--measVar", type=float, default=None, help="--checks output: measurement variance in px^2 (default: measurementNoise^2)")
     a = ap.parse_args()
     f = StatFixture(a.landmarks, a.particles, 1)
     s = f.settings
+    if a.checks == "output" and a.measVar is not None:
+        s.measurementNoise = float(np.sqrt(a.measVar))  # the filter's update and the likelihood weigh the measurement alike
     s.fastRiccati, s.removeLostLandmarks = 1, 0
     B = 9
     core = BatchCore(s, B)
@@ -58,6 +97,9 @@ def main():
         rows.append([float(v) for v in mean])
         print(f"frame {frame}: " + "  ".join(f"{label[k]} {mean[k]:.4f}" for k in slots), flush=True)
 
+    if a.checks == "output":
+        output_check(a, f, core, ens, cam, slots, label)
+        return
     judge(0)
     for frame in range(1, a.frames + 1):
         for mode, step in zip(MODES, (core.step, core.step_accurate, core.step_discrete)):
