@@ -316,6 +316,22 @@ class BatchCore:
         """eqf_batch_step_discrete: the frame with one discrete-state-matrix Riccati step per IMU sample. entries as step_accurate's."""
         return self._step(self.elib.eqf_batch_step_discrete, entries)
 
+    def augment(self, entries):
+        """eqf_batch_augment. entries: list of (slot, new_ids, provided_ids, provided_p[n, 3]): augmentLandmarkStates of every listed slot in one launch - the
+        landmarks whose id is not in new_ids leave, the ids of new_ids the slot does not hold are appended with their provided points. Returns the per-entry
+        status codes."""
+        n = len(entries)
+        arr = (BatchAugmentEntry * max(n, 1))()
+        keep = []
+        for e, (slot, new_ids, prov_ids, prov_p) in enumerate(entries):
+            new_ids, prov_ids, prov_p = _i32(new_ids), _i32(prov_ids), _f64(prov_p).reshape(-1)
+            keep.append((new_ids, prov_ids, prov_p))
+            arr[e].slot, arr[e].n_new, arr[e].new_ids, arr[e].n_prov = int(slot), len(new_ids), _ip(new_ids), len(prov_ids)
+            arr[e].prov_ids, arr[e].prov_p = _ip(prov_ids), _dp(prov_p)
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.elib.eqf_batch_augment(self.h, n, arr, _ip(status)))
+        return status[:n].copy()
+
     def last_riccati(self, k):
         """(samples with dt > 0, most squarings) of slot k's last accurate or discrete step (eqf_batch_last_riccati)."""
         n, sq = C.c_int(), C.c_int()

@@ -7,7 +7,8 @@ arrays in and out; the compute calls return per-entry status codes, a failing ca
 (_batch_ensemble_declared).
 
 The measurement side, include/eqf_batch_ensemble_output.h - likelihood, resample_weighted_seeded, covariance per slot - is declared in a second list
-(_batch_ensemble_output_declared)."""
+(_batch_ensemble_output_declared); follow, eqvio_amd/csrc/eqf_batch_ensemble_follow.h - clouds that follow their slot's landmark turnover - in a third
+(_batch_ensemble_follow_declared)."""
 import ctypes as C
 
 import numpy as np
@@ -30,6 +31,10 @@ class BensLikelihoodEntry(C.Structure):
 
 class BensResampleEntry(C.Structure):
     _fields_ = [("slot", C.c_int), ("P_new", C.c_int), ("seed", C.c_ulonglong), ("stream", C.c_ulonglong)]
+
+
+class BensFollowEntry(C.Structure):
+    _fields_ = [("slot", C.c_int), ("seed", C.c_ulonglong), ("stream", C.c_ulonglong)]
 
 
 NMAX = 213  # 21 + 3 * 64: eqf_bens_covariance's block per entry is NMAX * NMAX doubles
@@ -68,6 +73,12 @@ def load_batch_ensemble_protos():
         fn.restype = res
         fn.argtypes = args
     lib._batch_ensemble_output_declared = sorted(output_protos)
+    follow_protos = {"eqf_bens_follow": (C.c_int, [vp, C.c_int, P(BensFollowEntry), c_int_p, c_int_p, c_int_p])}
+    for name, (res, args) in follow_protos.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    lib._batch_ensemble_follow_declared = sorted(follow_protos)
     return lib
 
 
@@ -236,6 +247,20 @@ class BatchEnsemble:
             d = self._slot_n(slots[e])
             mats.append(buf[e * NMAX * NMAX:e * NMAX * NMAX + d * d].reshape(d, d).T.copy())
         return mats, [int(v) for v in status[:n]]
+
+    def follow(self, entries, out=None):
+        """entries: list of (slot, seed, stream). Every listed cloud becomes a cloud over its slot's current landmark ids, in the slot's order: the kept landmarks'
+        points moved byte for byte, the dropped ones gone, the added ones drawn on the device from the slot's Sigma conditional on the particle's sensor state and
+        kept landmarks, with rows of normals(seed, stream, n, P) of include/eqf_ensemble_random.h. Returns (dropped[count], added[count], status[count]); the
+        counts of a refused entry are left as they were (-1 in fresh arrays; pass `out` = (dropped, added) to see that they are not written)."""
+        n = len(entries)
+        arr = (BensFollowEntry * max(n, 1))()
+        for t, (slot, seed, stream) in enumerate(entries):
+            arr[t].slot, arr[t].seed, arr[t].stream = int(slot), _u64(seed), _u64(stream)
+        dropped, added = (np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)) if out is None else out
+        status = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.eqf_bens_follow(self.h, n, arr, _ip(dropped), _ip(added), _ip(status)))
+        return dropped[:n], added[:n], [int(v) for v in status[:n]]
 
     def stats(self, reset=False):
         """(kernel launches, factorisations of Sigma) since the last reset"""

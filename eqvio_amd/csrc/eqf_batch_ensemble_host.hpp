@@ -29,6 +29,7 @@ struct eqf_bens {
     std::vector<void*> own;
     std::vector<char> w_valid;  // per slot: eqf_bens_likelihood's kept weights stand; every call that changes the slot's cloud clears it
     BensOutState* os = nullptr;
+    void* fd = nullptr;         // eqf_bens_follow's packets on the device (eqf_batch_ensemble_follow_host.hpp), made at its first use; one of `own`
 };
 
 namespace {

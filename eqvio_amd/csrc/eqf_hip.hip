@@ -4176,3 +4176,6 @@ int eqf_last_kernel_times(eqf_ctx* c, int* which, float* usec, int cap) {
 // ... and their measurement side (include/eqf_batch_ensemble_output.h)
 #include "eqf_batch_ensemble_output.hpp"
 #include "eqf_batch_ensemble_output_host.hpp"
+// ... and the call that lets a cloud follow its slot's landmark turnover (eqvio_amd/csrc/eqf_batch_ensemble_follow.h)
+#include "eqf_batch_ensemble_follow.hpp"
+#include "eqf_batch_ensemble_follow_host.hpp"

@@ -31,9 +31,9 @@
  *    and read by the launches behind it;
  *  - every sum has a fixed order and A PARTICLE'S VALUE DEPENDS ON ITS SLOT'S DATA AND ITS OWN DATA ALONE: the same bytes from run to run, at any P, at any
  *    place in the cloud, at any entry position and whatever else the call lists.
- * Out of scope: caller-supplied normals; clouds that follow a slot's landmark turnover (after a step has changed the slot's ids, nees and errors match by
- * id as stated below and refuse an entry whose cloud lacks one). The measurement likelihood, weightedResample and the particle covariance against slots are
- * the three calls of eqf_batch_ensemble_output.h on the same object.
+ * Out of scope: caller-supplied normals. After a step has changed the slot's ids, nees and errors match by id as stated below and refuse an entry whose
+ * cloud lacks one: clouds that follow a slot's landmark turnover are the call of eqf_batch_ensemble_follow.h on the same object. The measurement likelihood,
+ * weightedResample and the particle covariance against slots are the three calls of eqf_batch_ensemble_output.h on the same object.
  */
 #ifndef EQF_BATCH_ENSEMBLE_H
 #define EQF_BATCH_ENSEMBLE_H

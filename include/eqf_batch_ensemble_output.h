@@ -27,8 +27,8 @@
  * MEMORY PER SLOT, on top of eqf_batch_ensemble.h's and allocated at the first of these calls: 8 (215 + 1 + 2) ldp + 4 ldp bytes - the gather's second place
  * (23 + 192 planes), the running sums, and the slot's share of the per-entry rows (log-likelihoods, weights, indices): 1.8 MB at max_particles = 1000, 0.5 MB at
  * 256. eqf_bens_covariance stages count * 213 * 213 doubles, allocated on first use and grown to the largest count seen.
- * Out of scope: caller-supplied uniforms or weights; a weighted (un-resampled) covariance or NEES; clouds that follow a slot's landmark turnover; P beyond what
- * one workgroup per entry normalises in a few microseconds.
+ * Out of scope: caller-supplied uniforms or weights; a weighted (un-resampled) covariance or NEES; P beyond what one workgroup per entry normalises in a few
+ * microseconds. Clouds that follow a slot's landmark turnover are the call of eqf_batch_ensemble_follow.h, which shares the gather's second place.
  */
 #ifndef EQF_BATCH_ENSEMBLE_OUTPUT_H
 #define EQF_BATCH_ENSEMBLE_OUTPUT_H

@@ -9,7 +9,13 @@ check with the discrete state matrix; the fast and the accurate mode linearise a
 --checks output runs the reference's fourth check instead (outputDistribution, :140-168; the knobs of scripts/ensemble_consistency.py --deviceOutput): after
 sampling, every slot gets a measurement of its xi0's first --measured landmarks with pixel noise of variance --measVar (numpy), then ONE eqf_bens_likelihood
 call, ONE eqf_bens_resample_weighted_seeded call, ONE vision step of the batch with that measurement (no IMU sample) and ONE eqf_bens_nees call. Prints ess, the
-distinct particles and the mean NEES per slot (band 0.5 of 1) and one JSON line."""
+distinct particles and the mean NEES per slot (band 0.5 of 1) and one JSON line.
+
+--checks turnover lets the clouds follow their slots' landmark turnover (eqvio_amd/csrc/eqf_batch_ensemble_follow.h): after sampling, for --rounds rounds, ONE
+eqf_batch_augment call makes the oldest landmark of every slot leave and one or two new ones arrive with provided points, ONE eqf_bens_follow call brings every
+cloud back in step and ONE eqf_bens_nees call judges it (band 0.1 of 1: the followed cloud is a draw from the slot's belief). A last round runs the output
+check on the changed landmark set: likelihood, resample_weighted_seeded, a vision step, follow, nees (band 0.5 of 1). Prints the mean NEES per round and slot and
+one JSON line."""
 import argparse
 import json
 import os
@@ -59,6 +65,62 @@ def output_check(a, f, core, ens, cam, slots, label):
                       "band": STAT_BANDS["output"], "launches_factorisations": ens.stats()}))
 
 
+def turnover_check(a, f, core, ens, cam, slots, label):
+    """clouds that follow their slots' landmark turnover (eqvio_amd/csrc/eqf_batch_ensemble_follow.h): every round the oldest landmark leaves every slot and one or two
+    new ones arrive, then follow, then nees; the last round is an output check on the landmark set the turnover has left"""
+    rng = np.random.default_rng([a.seed, 78])
+    var = f.settings.measurementNoise**2
+    next_id = 1000
+    rows = []
+
+    def judge(what):
+        _, mean, status = ens.nees(slots)
+        assert not any(status), status
+        rows.append([float(v) for v in mean])
+        print(f"{what}: " + "  ".join(f"{label[k]} {mean[k]:.4f}" for k in slots), flush=True)
+
+    judge("round 0 (sampled)")
+    for r in range(1, a.rounds + 1):
+        entries = []
+        for k in slots:
+            ids = core.get_state(k)[2]
+            n_new = min(1 + (r + k) % 2, 64 - max(len(ids) - 1, 0))
+            new = np.arange(next_id, next_id + n_new, dtype=np.int32)
+            next_id += n_new
+            pts = rng.uniform(-1, 1, (n_new, 3)) * 10.0 + np.array([0, 0, 20.0])
+            entries.append((k, np.concatenate([ids[1:], new]), new, pts))
+        assert not any(core.augment(entries))
+        assert ens.nees(slots)[2] == [-3] * len(slots)  # what every call answered before follow existed: a filter id the cloud does not hold
+        dropped, added, status = ens.follow([(k, a.seed, 200 + 16 * r + k) for k in slots])
+        assert not any(status), status
+        sizes = [ens.size(k)[1] for k in slots]
+        judge(f"round {r} (dropped {int(dropped.min())} .. {int(dropped.max())}, added {int(added.min())} .. {int(added.max())}, N = {min(sizes)} .. {max(sizes)})")
+    # the output check on the changed landmark set: a measurement of every landmark the slot now holds (X is the identity: the estimate is q0)
+    meas = []
+    for k in slots:
+        _, _, ids, q0, _ = core.get_state(k)
+        y = np.stack([PINHOLE[0] * q0[:, 0] / q0[:, 2] + PINHOLE[2], PINHOLE[1] * q0[:, 1] / q0[:, 2] + PINHOLE[3]], axis=1) + np.sqrt(var) * rng.normal(size=(len(ids), 2))
+        meas.append((ids, y))
+    _, _, _, ess, status = ens.likelihood([(k, cam, meas[k][0], meas[k][1], var) for k in slots])
+    assert not any(status), status
+    src, status = ens.resample_weighted_seeded([(k, a.particles, a.seed, 100 + k) for k in slots])
+    assert not any(status), status
+    none13, none = np.zeros((0, 13)), np.zeros(0)
+    assert not any(core.step_accurate([(k, cam, none13, none, meas[k][0], meas[k][1]) for k in slots]))
+    dropped, added, status = ens.follow([(k, a.seed, 900 + k) for k in slots])
+    assert not any(status), status
+    _, mean, status = ens.nees(slots)
+    assert not any(status), status
+    distinct = [len(set(src[k, :a.particles].tolist())) for k in slots]
+    for k in slots:
+        print(f"{label[k]}: output round on N = {ens.size(k)[1]}: ess {ess[k]:.1f} distinct {distinct[k]} follow -{int(dropped[k])} +{int(added[k])} mean NEES {mean[k]:.4f}", flush=True)
+    arr = np.array(rows)
+    print(json.dumps({"metric": "batch_ensemble_turnover_consistency", "N": a.landmarks, "P": a.particles, "rounds": a.rounds, "slots": label,
+                      "turnover_worst": float(np.max(np.abs(arr - 1.0))), "turnover_band": STAT_BANDS["initial"], "output_mean_nees": [float(v) for v in mean],
+                      "output_worst": float(np.max(np.abs(mean - 1.0))), "output_band": STAT_BANDS["output"], "ess": [float(v) for v in ess],
+                      "launches_factorisations": ens.stats()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--landmarks", type=int, default=2)
@@ -66,7 +128,8 @@ def main():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--dt", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=2026)
-    ap.add_argument("--checks", choices=("propagation", "output"), default="propagation")
+    ap.add_argument("--checks", choices=("propagation", "output", "turnover"), default="propagation")
+    ap.add_argument("--rounds", type=int, default=5, help="--checks turnover: rounds of augment, follow, nees")
     ap.add_argument("--measured", type=int, default=None, help="--checks output: measured landmarks (default: all)")
     ap.add_argument("--measVar", type=float, default=None, help="--checks output: measurement variance in px^2 (default: measurementNoise^2)")
     a = ap.parse_args()
@@ -99,6 +162,9 @@ def main():
 
     if a.checks == "output":
         output_check(a, f, core, ens, cam, slots, label)
+        return
+    if a.checks == "turnover":
+        turnover_check(a, f, core, ens, cam, slots, label)
         return
     judge(0)
     for frame in range(1, a.frames + 1):
